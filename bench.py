@@ -14,9 +14,11 @@ not touch the halo run at once; the first frames follow when the halo has landed
 other communication.  `python bench.py --gpus N` starts its own N ranks (fresh child processes, before
 this process touches torch or the GPU); under torch.distributed.run it runs as the rank it is given.
 
-Prints ONE JSON line on rank 0.  At N = 1 the line also carries short timed passes of the other
-BASELINE configurations (`other_workloads`), a >= 2 s sustained window (`roofline.sustained_frac`) and
-the CPU baseline (the oracle's naive fp32 port, all host threads and one thread).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line.  With
+--full the line also carries, at N = 1, short timed passes of the other BASELINE configurations
+(`other_workloads`), a >= 2 s sustained window (`roofline.sustained_frac`), the copy-kernel yardsticks and
+the CPU baseline (the oracle's naive fp32 port, all host threads and one thread); at N > 1 a sharded pass
+of cfg4.  --dump-outputs DIR writes a fixed, seeded sample of the last timed step's output (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -45,7 +47,7 @@ WORKLOADS = {
     "ref56": (56, 12, 56, "int16", 12, 4, 28),     # the reference's own band counts at fs = 56 MHz
     "ref560": (560, 12, 560, "int16", 12, 4, 28),
 }
-# what the default N = 1 run times after the headline: (workload, channel_major)
+# what an N = 1 run with --full times after the headline: (workload, channel_major)
 OTHER_WORKLOADS = [("cfg1", False), ("cfg3", False), ("cfg4", False), ("cfg5", False), ("ref56", False), ("ref560", False),
                    ("cfg2", True), ("cfg3", True), ("cfg4", True), ("cfg5", True)]
 TRAFFIC_SOURCE = "profiles/r03_pmc_traffic.json"  # rocprofv3 --pmc passes of this command (never measured in-run)
@@ -67,6 +69,11 @@ def parse_args():
     ap.add_argument("--grid", type=int, default=-1)
     ap.add_argument("--tile-waves", type=int, default=-1)
     ap.add_argument("--variant", type=int, default=-1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements: other BASELINE configurations, the sustained "
+                         "window, the copy-kernel yardsticks and the CPU baseline (N = 1), the sharded cfg4 pass (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded sample of the last timed step's output to DIR/*.npy (float32/float64)")
     ap.add_argument("--cpu-budget-s", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the other BASELINE configurations")
@@ -76,7 +83,10 @@ def parse_args():
                     help="write MATLAB's column-major F x M matrix instead of frame-major rows (not the headline line)")
     ap.add_argument("--halo", default="p2p", choices=("p2p", "allgather"),
                     help="how the halos move: send/recv between neighbours (ncclSend/ncclRecv), or one all_gather of the tails")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -161,6 +171,26 @@ def cpu_baseline(iq_prefix, taps, M: int, P: int, D: int, bw: int, budget_s: flo
                       f"-march=native on this host), {dt_all:.2f} s wall = {dt_all * cores:.0f} core-seconds",
             "one_thread": {"value": v_one, "unit": "MS/s", "cores": 1,
                            "sample": f"first {n_one} samples x{r_one} passes of the same port on one thread, {dt_one:.2f} s"}}
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: the whole dump, all ranks together
+DUMP_SEED = 1234
+
+
+def dump_outputs(y, folder: str, channel_major: bool, rank: int, world: int) -> None:
+    """--dump-outputs: what the timed path returned in its last step (complex64 frames, as float32 [..., 2] = re, im).
+    One step's output is gigabytes, so a fixed, seeded sample of whole frames is written -- the same frames for the same
+    arguments -- with their indices beside it: DIR/<name>.npy and DIR/<name>_frames.npy (float64)."""
+    import numpy as np
+    import torch
+    frames, M = (y.shape[1], y.shape[0]) if channel_major else (y.shape[0], y.shape[1])
+    keep = min(frames, DUMP_BYTES // (world * M * y.element_size()))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(frames, size=keep, replace=False))
+    sel = y.index_select(1 if channel_major else 0, torch.from_numpy(idx).to(y.device))
+    name = "channelized" if world == 1 else f"channelized_rank{rank}"
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, name + ".npy"), torch.view_as_real(sel).cpu().numpy())
+    np.save(os.path.join(folder, name + "_frames.npy"), idx.astype(np.float64))
 
 
 def main() -> None:
@@ -250,9 +280,8 @@ def main() -> None:
 
     def step():
         if world > 1:
-            ch.process_shard(iq, out=out)  # exchange on the side stream, interior frames now, head frames after the halo
-        else:
-            ch(iq, out=out, sync=False)
+            return ch.process_shard(iq, out=out)  # exchange on the side stream, interior frames now, head frames after the halo
+        return ch(iq, out=out, sync=False)
 
     halo_mode = args.halo
     if world > 1:
@@ -291,7 +320,7 @@ def main() -> None:
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        y = step()
     ch.sync()  # the handle's stream: kernels and, behind the halo event, the transfers
     torch.cuda.synchronize(dev)
     if world > 1:
@@ -299,6 +328,9 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     kernel_ms = kernel_ms_per_step(ch, launches_per_step)
     ch.set_option(L.PFB_OPT_PROFILE, 0)
+    if args.dump_outputs:
+        dump_outputs(y, args.dump_outputs, args.channel_major, rank, world)
+    del y
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if args.backend != "nccl":
@@ -322,7 +354,7 @@ def main() -> None:
     # ---- N > 1: BASELINE's 8-GPU configuration is cfg4 (M = 1024, 16 taps, 2^30 samples per GPU, halo 61 440 B): a short
     # sharded pass of it after the headline, every rank taking part
     sharded_cfg4 = None
-    if world > 1 and not args.no_other_workloads and args.workload != "cfg4":
+    if world > 1 and args.full and not args.no_other_workloads and args.workload != "cfg4":
         ch.release()
         del iq, out
         torch.cuda.empty_cache()
@@ -422,7 +454,7 @@ def main() -> None:
             except Exception:
                 pass
 
-        if world == 1:
+        if world == 1 and args.full:
             # ---- sustained window: >= sustained_s seconds of back-to-back launches (clocks settle at sustained power)
             if args.sustained_s > 0:
                 m = int(min(4000, max(100, args.sustained_s / (k_ms * 1e-3)))) if k_ms == k_ms else 0
@@ -451,14 +483,14 @@ def main() -> None:
                     if L.load().pfb_measure_mix_copy(local_rank, 1 << 30, ratio, spw, 5, L.C.byref(bps)) == 0:
                         bounds[f"1_read_{ratio}_written_{spw}_rows_per_wave"] = round(bps.value / 1e9 / HBM_PEAK_GBS, 4)
             res["roofline"]["copy_kernel_frac_by_byte_mix"] = bounds
-        prefix = iq[: 1 << 28].cpu().numpy() if (world == 1 and not args.no_cpu_baseline and fmt == "int16") else None
+        prefix = iq[: 1 << 28].cpu().numpy() if (world == 1 and args.full and not args.no_cpu_baseline and fmt == "int16") else None
         if ch is not None:
             ch.release()
         del iq, out
         torch.cuda.empty_cache()
 
         # ---- the other BASELINE configurations, short timed passes (N = 1 only; cfg4 at its per-GPU size)
-        if world == 1 and not args.no_other_workloads and args.workload == "cfg2" and not args.channel_major:
+        if world == 1 and args.full and not args.no_other_workloads and args.workload == "cfg2" and not args.channel_major:
             others = []
             for name, cm in OTHER_WORKLOADS:
                 oM, oP, oD, ofmt, obw, obytes, olog2 = WORKLOADS[name]

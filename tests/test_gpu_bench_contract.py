@@ -25,7 +25,7 @@ def run_bench(args, env_extra=None, timeout=300):
 
 @pytest.mark.timeout(400)
 def test_single_gpu_line_has_the_contract_fields():
-    d = run_bench(["--log2-samples", "24", "--steps", "4", "--warmup", "2", "--no-other-workloads", "--sustained-s", "0",
+    d = run_bench(["--full", "--log2-samples", "24", "--steps", "4", "--warmup", "2", "--no-other-workloads", "--sustained-s", "0",
                    "--cpu-budget-s", "1"])
     assert d["metric"].startswith("input MS/s") and d["unit"] == "MS/s" and d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["data"] == "synthetic"
@@ -40,9 +40,31 @@ def test_single_gpu_line_has_the_contract_fields():
 
 
 @pytest.mark.timeout(400)
+def test_plain_line_is_the_headline_alone_and_dumps_the_same_output_twice(tmp_path):
+    """Without --full the line carries the headline and none of the side measurements.  --dump-outputs writes a fixed,
+    seeded sample of the last timed step's output; the same arguments give the same inputs, so two runs dump the same."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        folder = tmp_path / f"run{i}"
+        d = run_bench(["--log2-samples", "24", "--steps", "3", "--warmup", "2", "--dump-outputs", str(folder)])
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+        assert d["roofline"]["launches_timed"] == 3 and d["cpu_baseline"] is None and "other_workloads" not in d
+        assert "sustained_frac" not in d["roofline"] and "measured_stream_copy_gbs" not in d["roofline"]
+        dumps.append({f: np.load(folder / f) for f in sorted(os.listdir(folder))})
+    a, b = dumps
+    assert sorted(a) == ["channelized.npy", "channelized_frames.npy"]
+    y, frames = a["channelized.npy"], a["channelized_frames.npy"]
+    assert y.dtype == np.float32 and frames.dtype == np.float64 and y.shape == (frames.size, 64, 2)
+    assert 0 < frames.size < (1 << 24) // 64 and np.all(np.diff(frames) > 0)  # a sample of the 2^18 frames, in order
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20 and np.isfinite(y).all() and np.abs(y).max() > 0
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
+@pytest.mark.timeout(400)
 @pytest.mark.parametrize("halo", ["p2p", "allgather"])
 def test_two_ranks_start_themselves_and_print_one_line(halo):
-    d = run_bench(["--gpus", "2", "--backend", "gloo", "--halo", halo, "--log2-samples", "24", "--steps", "4", "--warmup", "2"],
+    d = run_bench(["--gpus", "2", "--backend", "gloo", "--halo", halo, "--log2-samples", "24", "--steps", "4", "--warmup", "2", "--full"],
                   env_extra={"PFB_BENCH_ONE_DEVICE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["scaling"] == "weak" and d["value"] > 0 and d["cpu_baseline"] is None
     assert "time-sharded x2" in d["config"]["parallelism"] and "704 raw samples" in d["config"]["parallelism"]

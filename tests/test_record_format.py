@@ -1,7 +1,9 @@
 """The .iq record format: our restatements (include/pfb_iq_packet.h via libpfb_channelizer.so,
 oracle/pfb_oracle.c, sdr_channelizer_amd/iqfile.py) pinned against the reference's own
-cpp/IqPacket.h + cpp/Helper.cpp compiled into oracle/_ref."""
+cpp/IqPacket.h + cpp/Helper.cpp: against what that code answered, recorded in
+tests/golden/record_format_ref.json, and against the live build in oracle/_ref where it exists."""
 import ctypes as C
+import json
 import os
 
 import numpy as np
@@ -11,7 +13,35 @@ from oracle.pfb_oracle import RefIqPacket
 from sdr_channelizer_amd import _lib as L
 from sdr_channelizer_amd import iqfile
 
-needs_ref = pytest.mark.skipif(not RefIqPacket.available(), reason="oracle/_ref not built")
+REF_RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "record_format_ref.json")
+
+
+class RecordedRef:
+    """RefIqPacket's questions answered from tests/golden/record_format_ref.json (tests/golden/make_record_format.py)."""
+
+    def __init__(self):
+        with open(REF_RECORD) as f:
+            self.rec = json.load(f)
+
+    def sizeof(self) -> int:
+        return self.rec["sizeof"]
+
+    def offsets(self) -> dict:
+        return self.rec["offsets"]
+
+    def make_header(self, *args) -> bytes:
+        want = [a.decode() if isinstance(a, bytes) else a for a in args]
+        (h,) = [h for h in self.rec["headers"] if h["args"] == want]
+        return bytes.fromhex(h["bytes"])
+
+    def filename(self, epoch_ms: int) -> str:
+        return self.rec["filenames"][str(epoch_ms)]
+
+
+def references():
+    """the recorded answers everywhere, and the live reference build as well where oracle/_ref is built"""
+    return [RecordedRef()] + ([RefIqPacket()] if RefIqPacket.available() else [])
+
 
 EXPECTED_OFFSETS = dict(endianness=0, linkSpeed=4, frequencyHz=8, bandwidthHz=16, sampleRateSps=20, rxGainDb=24,
                         numSamples=28, bitWidth=32, spare0=36, boardName=40, serialNumber=56, fpgaVersion=72,
@@ -24,19 +54,18 @@ def test_our_struct_layout():
         assert getattr(L.PfbIqPacket, name).offset == off, name
 
 
-@needs_ref
 def test_layout_matches_reference_build():
-    ref = RefIqPacket()
-    assert ref.sizeof() == C.sizeof(L.PfbIqPacket) == 112
-    assert ref.offsets() == EXPECTED_OFFSETS
+    for ref in references():
+        assert ref.sizeof() == C.sizeof(L.PfbIqPacket) == 112
+        assert ref.offsets() == EXPECTED_OFFSETS
 
 
-@needs_ref
 @pytest.mark.parametrize("marker,bw", [(0x02020202, 12), (0x03030303, 16), (0x03030303, 8), (0x02020202, 8)])
 def test_parse_reference_written_header(oracle, marker, bw):
-    ref = RefIqPacket()
-    raw = ref.make_header(marker, 5000, 2_412_000_000, 56_000_000, 56_000_000, 31.5, 123456, bw,
-                          b"bladerf", b"0123456789abcde", b"v0.15.0", b"v2.4.0", 1.7e9 + 0.25)
+    raws = [ref.make_header(marker, 5000, 2_412_000_000, 56_000_000, 56_000_000, 31.5, 123456, bw,
+                            b"bladerf", b"0123456789abcde", b"v0.15.0", b"v2.4.0", 1.7e9 + 0.25) for ref in references()]
+    assert all(r == raws[0] for r in raws)
+    raw = raws[0]
     assert len(raw) == 112
     info = iqfile.parse_header(raw)
     p = info.packet
@@ -98,10 +127,10 @@ def test_marker_zero_reads_as_format_2_in_native_byte_order():
         (2_412_000_000, 56_000_000, 1234, 12)
 
 
-@needs_ref
 @pytest.mark.parametrize("ms", [0, 1_700_000_000_123, 951_782_400_000, 1_709_251_199_999])
 def test_filename_matches_reference_helper(ms):
-    assert iqfile.filename_for(ms) == RefIqPacket().filename(ms)
+    for ref in references():
+        assert iqfile.filename_for(ms) == ref.filename(ms)
 
 
 def test_record_round_trip(tmp_path):
@@ -116,14 +145,14 @@ def test_record_round_trip(tmp_path):
         assert os.path.getsize(path) == 112 + iq.nbytes  # header then (n)*sizeof(complex<intX>) (:321-322)
 
 
-@needs_ref
 def test_our_writer_emits_the_reference_bytes(tmp_path):
-    ref = RefIqPacket().make_header(0x03030303, 0, 915_000_000, 20_000_000, 20_000_000, 12.0, 10, 16,
-                                    b"usrp", b"s1", b"", b"", 99.0)
     path = os.path.join(tmp_path, "w.iq")
     iqfile.write_iq(path, np.zeros((10, 2), np.int16), fs=20e6, fc=915e6, bit_width=16, gain_db=12.0,
                     start_time=99.0, board="usrp", serial="s1")
-    assert open(path, "rb").read()[:112] == ref
+    for ref in references():
+        want = ref.make_header(0x03030303, 0, 915_000_000, 20_000_000, 20_000_000, 12.0, 10, 16,
+                               b"usrp", b"s1", b"", b"", 99.0)
+        assert open(path, "rb").read()[:112] == want
 
 
 def test_fmt1_writer_matches_generate_training_iq_layout(tmp_path):

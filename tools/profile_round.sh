@@ -6,8 +6,8 @@ set -u
 rnd=${1:-r03}
 root=$(pwd); out=$root/gpurun_out/prof_$rnd; mkdir -p $out
 export TMPDIR=/tmp; cd /tmp
-# 1. the default bench command under the kernel trace: the bench line and the per-kernel stats of the SAME run
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_default -- python3 $root/bench.py > $out/bench_default.json 2> $out/bench_default.err
+# 1. the full bench command (--full) under the kernel trace: the bench line and the per-kernel stats of the SAME run
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_default -- python3 $root/bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 echo "bench default under rocprofv3: exit $?"
 # 2. HBM traffic of the headline kernel (cfg2) and of every other frame-major shape: FETCH_SIZE / WRITE_SIZE passes,
 #    then the issue-side counters the round's analysis uses (cfg4_v3 = the schedule-13 variant of M = 1024)
