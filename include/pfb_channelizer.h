@@ -370,6 +370,80 @@ int pfb_pdw_last_noise_floor_path(void);
  * serialised on it).  This frees it: device_id >= 0 for one device, < 0 for all. */
 int pfb_pdw_release_workspace(int32_t device_id);
 
+
+/* ---- short-time Fourier transform of an I/Q stream --------------------------------------------
+ * Replaces the spectrogram lines of the reference scripts:
+ *   matlab/spectrogram_my_iq.m:105-115   [s,f,t] = stft(iq,fs,'Window',hamming(768),'OverlapLength',0)
+ *                                         on iq = (I + jQ)/2^(bitWidth-1) (no conjugate), abs(s).^2 plotted
+ *   matlab/generate_pulsed_iq.m:105       spectrogram(iq,1024,0,1024,Fs,'centered','yaxis'): PSD in dB
+ * Arithmetic, with w[0..L-1] the caller's window, H the hop and nfft >= L the FFT length:
+ *   frame m covers x[mH .. mH+L-1]; N samples give F = floor((N-L)/H) + 1 frames (0 if N < L): partial
+ *   windows are never produced.
+ *   s[r,m] = sum_{n<L} w[n] x[mH+n] e^{-j 2 pi k_r n / nfft}       (phase origin: the frame's first sample)
+ *   PFB_STFT_CENTERED  k_r = r - nfft/2 + 1 (even nfft: (-pi, pi], Nyquist last), r - (nfft-1)/2 (odd):
+ *                      stft's default 'centered' -- NOT fftshift, which differs by one row at even nfft
+ *   PFB_STFT_TWOSIDED  k_r = r (FFT order)
+ * Output out[m*nfft + r]: MATLAB's column-major nfft x F matrix s.  PFB_STFT_POWER stores scale*|s|^2,
+ * PFB_STFT_DB 10*log10(scale*|s|^2 + db_floor) (float32); PFB_STFT_COMPLEX stores s (complex64).
+ * Unpinned (closed toolbox; pfb_stft_axes and DESIGN.md section 11 keep each in one place):
+ *   - the time axis: t_m = (m*H + L/2)/fs, the segment centre (spectrogram's colindex-1 + nwind/2);
+ *   - stft's default FFTLength when only 'Window' is given: fft_length = 0 means nfft = L;
+ *   - spectrogram's PSD scale 1/(fs*sum w^2) and the eps its plot adds: the caller's scale / db_floor.
+ * The handle is stateful: it carries the samples from the start of the next frame (fewer than L), so any
+ * cutting of a stream into calls gives the same bits as one call. */
+enum { PFB_STFT_COMPLEX = 0, PFB_STFT_POWER = 1, PFB_STFT_DB = 2 };
+enum { PFB_STFT_CENTERED = 0, PFB_STFT_TWOSIDED = 1 };
+enum { PFB_STFT_KERNEL_AUTO = 0, PFB_STFT_KERNEL_GENERIC = 1, PFB_STFT_KERNEL_FUSED = 2 };
+
+typedef struct pfb_stft_config {
+  uint32_t struct_size;    /* = sizeof(pfb_stft_config)                                              */
+  uint32_t window_length;  /* L >= 1                                                                 */
+  uint32_t hop;            /* H = L - OverlapLength, 1 <= H <= L; 0 = L (no overlap)                 */
+  uint32_t fft_length;     /* nfft, L <= nfft <= 4096 (zero padding); 0 = L                          */
+  const float* window;     /* L coefficients, copied at create                                       */
+  uint32_t sample_format;  /* pfb_sample_format                                                      */
+  uint32_t bit_width;      /* 8, 12 or 16: scale 2^-(bit_width-1); ignored for CF32                  */
+  uint32_t output;         /* PFB_STFT_COMPLEX / POWER / DB                                          */
+  uint32_t freq_order;     /* PFB_STFT_CENTERED (stft's default) / PFB_STFT_TWOSIDED                 */
+  double scale;            /* power and dB: multiplies |s|^2; 0 = 1                                  */
+  double db_floor;         /* dB: added before log10 (>= 0; 0 gives -inf for an all-zero bin)       */
+                           /* Both are applied in float32: nonzero values outside [FLT_MIN, FLT_MAX] */
+                           /* are PFB_ERR_BAD_ARG                                                   */
+  uint32_t kernel;         /* PFB_STFT_KERNEL_*: FUSED = fused kernel or PFB_ERR_UNSUPPORTED         */
+  int32_t device_id;       /* HIP device ordinal, -1 = current device                                */
+} pfb_stft_config;
+
+typedef struct pfb_stft_handle pfb_stft_handle;
+
+/* Lifecycle as pfb_create / pfb_destroy / pfb_reset / pfb_set_stream.  Every argument is validated before
+ * the device is touched: PFB_ERR_BAD_ARG, PFB_ERR_BAD_FORMAT, PFB_ERR_UNSUPPORTED (nfft > 4096, or FUSED
+ * asked for an nfft without a fused kernel), then PFB_ERR_NO_DEVICE without a HIP device. */
+int pfb_stft_create(const pfb_stft_config* cfg, pfb_stft_handle** out);
+int pfb_stft_destroy(pfb_stft_handle* h);
+int pfb_stft_reset(pfb_stft_handle* h);
+int pfb_stft_set_stream(pfb_stft_handle* h, void* hip_stream);
+/* Transform num_samples samples; frames = what pfb_stft_frames_for reports, written to *frames_out.
+ * `out` must hold out_capacity_frames * nfft values (PFB_ERR_CAPACITY otherwise, with *frames_out = the
+ * frames needed and no state change).  mem = PFB_MEM_HOST / PFB_MEM_DEVICE.  Synchronous.  Device pointers must be
+ * aligned to one sample (iq) and one output element (out): PFB_ERR_BAD_ARG otherwise. */
+int pfb_stft_process(pfb_stft_handle* h, const void* iq, uint64_t num_samples, void* out,
+                     uint64_t out_capacity_frames, uint64_t* frames_out, uint32_t mem);
+/* Same, device pointers, enqueued on the handle's stream without a host sync. */
+int pfb_stft_process_async(pfb_stft_handle* h, const void* d_iq, uint64_t num_samples, void* d_out,
+                           uint64_t out_capacity_frames, uint64_t* frames_out);
+int pfb_stft_sync(pfb_stft_handle* h);
+int pfb_stft_frames_for(const pfb_stft_handle* h, uint64_t num_samples, uint64_t* frames_out);
+/* One .iq record from disk (header checked as in pfb_process_iq_file, format and bit width against the
+ * handle), streamed in chunks; `out` is host memory. */
+int pfb_stft_process_iq_file(pfb_stft_handle* h, const char* path, void* out, uint64_t out_capacity_frames,
+                             uint64_t* frames_out, pfb_iq_info* info_out);
+/* Host-only axes: f_out[r] = k_r*fs/nfft (nfft values), t_out[m] = ((first_frame+m)*H + L/2)/fs (frames
+ * values).  Either pointer may be NULL. */
+int pfb_stft_axes(uint32_t fft_length, uint32_t window_length, uint32_t hop, double fs, uint32_t freq_order,
+                  uint64_t first_frame, uint64_t frames, double* f_out, double* t_out);
+/* Name of the kernel the last process call launched ("" before the first). */
+const char* pfb_stft_last_kernel(const pfb_stft_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

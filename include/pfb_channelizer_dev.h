@@ -42,6 +42,12 @@ int pfb_measure_stream_copy(int device_id, uint64_t bytes_in, int iters, double*
 int pfb_measure_mix_copy(int device_id, uint64_t bytes_in, uint32_t write_ratio, uint32_t rows_per_wave, int iters,
                          double* bytes_per_sec);
 
+/* STFT timing study (tools/stft_rate.py --variant loadstore): 1 = the handle's fused kernel with its loads and stores
+ * only -- the tile's span into LDS and the tile's outputs written from there, no window, no FFT -- so its time is the
+ * memory part of the kernel's; the output is not an STFT.  0 = the real kernel again.  PFB_ERR_UNSUPPORTED for a handle
+ * on the generic kernel.  Registered nowhere: pfb_stft_last_kernel names it pfb_stft_loadstore<...>. */
+int pfb_stft_set_experiment(pfb_stft_handle* h, int experiment);
+
 /* Diagnostic: throws a C++ exception of the given kind (0 = std::bad_alloc, 1 = std::runtime_error,
  * 2 = a non-std type) INSIDE the guard every entry point runs under and returns what the guard
  * returns (PFB_ERR_NO_MEMORY / PFB_ERR_INTERNAL): proof that nothing thrown crosses the C ABI. */

@@ -33,6 +33,9 @@ PFB_MEM_HOST, PFB_MEM_DEVICE = 0, 1
 PFB_OPT_KERNEL, PFB_OPT_FRAMES_PER_BLOCK, PFB_OPT_HOST_CHUNK_SAMPLES, PFB_OPT_NONTEMPORAL, PFB_OPT_PROFILE, PFB_OPT_XCD_REMAP = 0, 1, 2, 3, 4, 5
 PFB_OPT_SCHEDULE, PFB_OPT_GRID, PFB_OPT_TILE_WAVES, PFB_OPT_EXPERIMENT, PFB_OPT_VARIANT = 6, 7, 8, 9, 10
 PFB_OPT_SLAB_FRAMES = 11
+PFB_STFT_COMPLEX, PFB_STFT_POWER, PFB_STFT_DB = 0, 1, 2
+PFB_STFT_CENTERED, PFB_STFT_TWOSIDED = 0, 1
+PFB_STFT_KERNEL_AUTO, PFB_STFT_KERNEL_GENERIC, PFB_STFT_KERNEL_FUSED = 0, 1, 2
 
 
 class PfbConfig(C.Structure):
@@ -41,6 +44,15 @@ class PfbConfig(C.Structure):
         ("decimation", C.c_uint32), ("taps", C.POINTER(C.c_float)), ("sample_format", C.c_uint32),
         ("bit_width", C.c_uint32), ("output_layout", C.c_uint32), ("flags", C.c_uint32),
         ("input_offset", C.c_int32), ("device_id", C.c_int32),
+    ]
+
+
+class PfbStftConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("window_length", C.c_uint32), ("hop", C.c_uint32), ("fft_length", C.c_uint32),
+        ("window", C.POINTER(C.c_float)), ("sample_format", C.c_uint32), ("bit_width", C.c_uint32),
+        ("output", C.c_uint32), ("freq_order", C.c_uint32), ("scale", C.c_double), ("db_floor", C.c_double),
+        ("kernel", C.c_uint32), ("device_id", C.c_int32),
     ]
 
 
@@ -89,9 +101,12 @@ EXPORTS = (
     "pfb_iq_parse_header", "pfb_iq_fill_packet", "pfb_iq_filename",
     "pfb_shard_attach", "pfb_halo_samples", "pfb_shard_head_frames", "pfb_halo_recv_buffer", "pfb_process_shard_async",
     "pfb_center_frequencies_ordered",
+    "pfb_stft_create", "pfb_stft_destroy", "pfb_stft_reset", "pfb_stft_set_stream", "pfb_stft_process",
+    "pfb_stft_process_async", "pfb_stft_sync", "pfb_stft_frames_for", "pfb_stft_process_iq_file", "pfb_stft_axes",
+    "pfb_stft_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
-DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard")
+DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment")
 
 _lib = None
 
@@ -184,6 +199,19 @@ def load() -> C.CDLL:
                                        C.c_char_p, C.c_char_p, C.c_double]
     lib.pfb_iq_fill_packet.restype = None
     lib.pfb_iq_filename.argtypes = [i64, C.c_char_p, C.c_int]
+    lib.pfb_stft_create.argtypes = [C.POINTER(PfbStftConfig), C.POINTER(vp)]
+    lib.pfb_stft_destroy.argtypes = [vp]
+    lib.pfb_stft_reset.argtypes = [vp]
+    lib.pfb_stft_set_stream.argtypes = [vp, vp]
+    lib.pfb_stft_process.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_stft_process_async.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    lib.pfb_stft_sync.argtypes = [vp]
+    lib.pfb_stft_frames_for.argtypes = [vp, u64, C.POINTER(u64)]
+    lib.pfb_stft_process_iq_file.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(u64), C.POINTER(PfbIqInfo)]
+    lib.pfb_stft_axes.argtypes = [u32, u32, u32, C.c_double, u32, u64, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.pfb_stft_last_kernel.argtypes = [vp]
+    lib.pfb_stft_last_kernel.restype = C.c_char_p
+    lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     for name in EXPORTS + DEV_EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     _lib = lib

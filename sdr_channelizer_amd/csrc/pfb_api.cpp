@@ -10,6 +10,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1310,6 +1311,366 @@ int pfb_measure_mix_copy(int device_id, uint64_t bytes_in, uint32_t write_ratio,
   (void)hipFree(out);
   return rc;
   });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// short-time Fourier transform (pfb_stft_*; kernels in pfb_stft.hip)
+
+struct pfb_stft_handle {
+  int L = 0, H = 0, nfft = 0;
+  int fmt = 0, bit_width = 0, output = 0, order = 0, kernel_opt = 0;
+  float scale = 1.f, db_floor = 0.f;
+  int device = 0;
+  int bps = 0;               // bytes per input sample
+  int out_elem = 8;          // complex64, or float32 for power / dB
+  float* d_win = nullptr;    // L: window x 2^-(bit_width-1)
+  float2* d_tw = nullptr;    // nfft: e^{+j 2 pi m / nfft}
+  void* d_carry[2] = {nullptr, nullptr};  // L raw samples each; the last carry_len are the start of the next frame
+  int cur = 0;
+  uint64_t carry_len = 0;    // < L
+  hipStream_t stream = nullptr;
+  const pfb::StftKernelInfo* kern = nullptr;
+  const char* last_kernel = "";
+  int experiment = 0;          // pfb_stft_set_experiment (pfb_channelizer_dev.h): 1 = loads and stores only
+  void* d_stage_in = nullptr;  // host path
+  void* d_stage_out = nullptr;
+  size_t stage_in_bytes = 0, stage_out_bytes = 0;
+  hipEvent_t ev_switch = nullptr;
+};
+
+namespace {
+
+void free_stft(pfb_stft_handle* h) {
+  if (!h) return;
+  DeviceGuard g(h->device);
+  (void)hipFree(h->d_win);
+  (void)hipFree(h->d_tw);
+  (void)hipFree(h->d_carry[0]);
+  (void)hipFree(h->d_carry[1]);
+  (void)hipFree(h->d_stage_in);
+  (void)hipFree(h->d_stage_out);
+  if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
+  delete h;
+}
+
+uint64_t stft_frames_for(const pfb_stft_handle* h, uint64_t n) {
+  const uint64_t total = h->carry_len + n;
+  return total >= (uint64_t)h->L ? (total - (uint64_t)h->L) / (uint64_t)h->H + 1 : 0;
+}
+
+// kernel + carry update for device-resident buffers; no host sync
+int stft_enqueue(pfb_stft_handle* h, const void* d_iq, uint64_t n, void* d_out, uint64_t frames) {
+  if (frames > 0) {
+    pfb::StftParams p{};
+    p.in = d_iq;
+    p.carry = h->d_carry[h->cur];
+    p.out = d_out;
+    p.win = h->d_win;
+    p.tw = h->d_tw;
+    p.n_in = (long long)n;
+    p.frames = (long long)frames;
+    p.carry_len = (int)h->carry_len;
+    p.carry_cap = h->L;
+    p.L = h->L; p.H = h->H; p.nfft = h->nfft;
+    p.fmt = h->fmt; p.output = h->output; p.order = h->order;
+    p.scale = h->scale; p.db_floor = h->db_floor;
+    const bool study = h->experiment == 1;
+    HIP_TRY((study ? h->kern->launch_loadstore : h->kern->launch)(p, h->stream));
+    h->last_kernel = study ? h->kern->name_loadstore : h->kern->name;
+  }
+  if (n > 0) {  // the last L samples of [carry | in]: the next frame starts in them
+    HIP_TRY(pfb::launch_update_history(h->d_carry[h->cur], d_iq, (long long)n, h->d_carry[h->cur ^ 1], h->L, h->bps,
+                                       h->stream));
+    h->cur ^= 1;
+  }
+  h->carry_len = h->carry_len + n - frames * (uint64_t)h->H;
+  return PFB_OK;
+}
+
+int stft_ensure_stage(pfb_stft_handle* h, size_t in_bytes, size_t out_bytes) {
+  if (in_bytes > h->stage_in_bytes) {
+    (void)hipFree(h->d_stage_in);
+    h->d_stage_in = nullptr; h->stage_in_bytes = 0;
+    HIP_TRY(hipMalloc(&h->d_stage_in, in_bytes));
+    h->stage_in_bytes = in_bytes;
+  }
+  if (out_bytes > h->stage_out_bytes) {
+    (void)hipFree(h->d_stage_out);
+    h->d_stage_out = nullptr; h->stage_out_bytes = 0;
+    HIP_TRY(hipMalloc(&h->d_stage_out, out_bytes));
+    h->stage_out_bytes = out_bytes;
+  }
+  return PFB_OK;
+}
+
+// Host buffers (pageable or page-locked): chunks staged through one device buffer pair on the handle's stream, so each
+// chunk's copy-in, transform, carry update and copy-out are ordered behind the previous chunk's.  Chunks are sized
+// so that neither side of the staging exceeds 64 MiB (a hop of 1 makes nfft outputs per input sample).
+int stft_process_host_steps(pfb_stft_handle* h, const void* iq, uint64_t n, void* out) {
+  const uint64_t frame_bytes = (uint64_t)h->nfft * h->out_elem, budget = (uint64_t)64 << 20;
+  uint64_t chunk = std::min<uint64_t>((uint64_t)1 << 24, budget / h->bps);
+  chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, budget / frame_bytes) * (uint64_t)h->H);
+  const uint64_t max_frames = (h->L - 1 + chunk) / (uint64_t)h->H + 1;
+  int rc = stft_ensure_stage(h, (size_t)std::min<uint64_t>(chunk, n ? n : 1) * h->bps,
+                             (size_t)std::min<uint64_t>(max_frames, stft_frames_for(h, n) + 1) * frame_bytes);
+  if (rc != PFB_OK) return rc;
+  const char* src = static_cast<const char*>(iq);
+  char* dst = static_cast<char*>(out);
+  uint64_t done = 0, frames_done = 0;
+  while (done < n) {
+    const uint64_t m = std::min<uint64_t>(chunk, n - done);
+    const uint64_t f = stft_frames_for(h, m);
+    HIP_TRY(hipMemcpyAsync(h->d_stage_in, src + done * h->bps, (size_t)m * h->bps, hipMemcpyHostToDevice, h->stream));
+    rc = stft_enqueue(h, h->d_stage_in, m, h->d_stage_out, f);
+    if (rc != PFB_OK) return rc;
+    if (f > 0)
+      HIP_TRY(hipMemcpyAsync(dst + frames_done * frame_bytes, h->d_stage_out, (size_t)(f * frame_bytes),
+                             hipMemcpyDeviceToHost, h->stream));
+    done += m;
+    frames_done += f;
+  }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return PFB_OK;
+}
+
+int stft_process_host(pfb_stft_handle* h, const void* iq, uint64_t n, void* out) {
+  const int rc = stft_process_host_steps(h, iq, n, out);
+  if (rc != PFB_OK) {  // nothing may still touch the caller's buffers once it has the status
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfb_stft_create(const pfb_stft_config* cfg, pfb_stft_handle** out) {
+  return pfb::abi_guard([&]() -> int {
+  if (!cfg || !out) return PFB_ERR_BAD_ARG;
+  *out = nullptr;
+  if (cfg->struct_size != sizeof(pfb_stft_config) || !cfg->window) return PFB_ERR_BAD_ARG;
+  const uint32_t L = cfg->window_length;
+  const uint32_t H = cfg->hop ? cfg->hop : L;
+  const uint32_t nfft = cfg->fft_length ? cfg->fft_length : L;
+  if (L < 1 || H > L || nfft < L) return PFB_ERR_BAD_ARG;
+  if (cfg->output > PFB_STFT_DB || cfg->freq_order > PFB_STFT_TWOSIDED || cfg->kernel > PFB_STFT_KERNEL_FUSED)
+    return PFB_ERR_BAD_ARG;
+  // both are applied in float32: they must survive the conversion (no overflow to inf, no underflow to 0)
+  const auto in_float = [](double v) { return v == 0 || (v >= (double)FLT_MIN && v <= (double)FLT_MAX); };
+  if (!std::isfinite(cfg->scale) || cfg->scale < 0 || !std::isfinite(cfg->db_floor) || cfg->db_floor < 0 ||
+      !in_float(cfg->scale) || !in_float(cfg->db_floor))
+    return PFB_ERR_BAD_ARG;
+  if (nfft > 4096) return PFB_ERR_UNSUPPORTED;  // as pfb_create for M > 4096
+  if (cfg->sample_format > PFB_FMT_CF32) return PFB_ERR_BAD_FORMAT;
+  int bw = (int)cfg->bit_width;
+  if (cfg->sample_format == PFB_FMT_INT8_IQ && (bw < 1 || bw > 8)) return PFB_ERR_BAD_FORMAT;
+  if (cfg->sample_format == PFB_FMT_INT16_IQ && (bw < 1 || bw > 16)) return PFB_ERR_BAD_FORMAT;
+  if (cfg->sample_format == PFB_FMT_CF32) bw = 1;  // scale 1
+  const pfb::StftKernelInfo* fused = pfb::find_stft_fused((int)nfft, (int)cfg->sample_format);
+  if (cfg->kernel == PFB_STFT_KERNEL_FUSED && !fused) return PFB_ERR_UNSUPPORTED;
+
+  int ndev = 0;
+  const hipError_t ce = hipGetDeviceCount(&ndev);
+  if (ce != hipSuccess || ndev <= 0) {
+    g_detail = std::string("hipGetDeviceCount: ") + (ce == hipSuccess ? "0 devices" : hipGetErrorString(ce));
+    (void)hipGetLastError();
+    return PFB_ERR_NO_DEVICE;
+  }
+  int dev = cfg->device_id;
+  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+  if (dev >= ndev) return PFB_ERR_BAD_ARG;
+
+  pfb_stft_handle* h = new (std::nothrow) pfb_stft_handle();
+  if (!h) return PFB_ERR_NO_MEMORY;
+  h->L = (int)L; h->H = (int)H; h->nfft = (int)nfft;
+  h->fmt = (int)cfg->sample_format; h->bit_width = bw;
+  h->output = (int)cfg->output; h->order = (int)cfg->freq_order; h->kernel_opt = (int)cfg->kernel;
+  h->scale = cfg->scale == 0 ? 1.f : (float)cfg->scale;
+  h->db_floor = (float)cfg->db_floor;
+  h->device = dev;
+  h->bps = pfb::bytes_per_sample(h->fmt);
+  h->out_elem = cfg->output == PFB_STFT_COMPLEX ? 8 : 4;
+  h->kern = (cfg->kernel != PFB_STFT_KERNEL_GENERIC && fused) ? fused : pfb::stft_generic_kernel();
+
+  DeviceGuard g(dev);
+  std::vector<float> win(L);
+  const float scale = std::ldexp(1.0f, -(bw - 1));  // power of two: w*scale is exact
+  for (uint32_t i = 0; i < L; ++i) win[i] = cfg->window[i] * scale;
+  std::vector<float2> tw(nfft);
+  const double two_pi = 6.283185307179586476925286766559;
+  for (uint32_t m = 0; m < nfft; ++m) {
+    tw[m].x = (float)std::cos(two_pi * (double)m / (double)nfft);
+    tw[m].y = (float)std::sin(two_pi * (double)m / (double)nfft);
+  }
+  const size_t carry_bytes = (size_t)L * h->bps;
+  hipError_t e = hipMalloc((void**)&h->d_win, L * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&h->d_tw, nfft * sizeof(float2));
+  if (e == hipSuccess) e = hipMalloc(&h->d_carry[0], carry_bytes);
+  if (e == hipSuccess) e = hipMalloc(&h->d_carry[1], carry_bytes);
+  if (e == hipSuccess) e = hipMemcpy(h->d_win, win.data(), L * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(h->d_tw, tw.data(), nfft * sizeof(float2), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(h->d_carry[0], 0, carry_bytes);
+  if (e == hipSuccess) e = hipMemset(h->d_carry[1], 0, carry_bytes);
+  if (e != hipSuccess) {
+    const int rc = hip_fail(e, "pfb_stft_create allocation");
+    free_stft(h);
+    return rc;
+  }
+  *out = h;
+  return PFB_OK;
+  });
+}
+
+int pfb_stft_destroy(pfb_stft_handle* h) {
+  return pfb::abi_guard([&]() -> int {
+  if (!h) return PFB_ERR_BAD_ARG;
+  free_stft(h);
+  return PFB_OK;
+  });
+}
+
+int pfb_stft_reset(pfb_stft_handle* h) {
+  return pfb::abi_guard([&]() -> int {
+  if (!h) return PFB_ERR_BAD_ARG;
+  h->carry_len = 0;  // the carried samples are never read again; nothing on the device to clear
+  return PFB_OK;
+  });
+}
+
+int pfb_stft_set_stream(pfb_stft_handle* h, void* hip_stream) {
+  return pfb::abi_guard([&]() -> int {
+  if (!h) return PFB_ERR_BAD_ARG;
+  hipStream_t next = static_cast<hipStream_t>(hip_stream);
+  if (next != h->stream) {  // the carry update the old stream still has queued comes first
+    DeviceGuard g(h->device);
+    if (!h->ev_switch) HIP_TRY(hipEventCreateWithFlags(&h->ev_switch, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->ev_switch, h->stream));
+    HIP_TRY(hipStreamWaitEvent(next, h->ev_switch, 0));
+    h->stream = next;
+  }
+  return PFB_OK;
+  });
+}
+
+int pfb_stft_frames_for(const pfb_stft_handle* h, uint64_t n, uint64_t* frames_out) {
+  if (!h || !frames_out) return PFB_ERR_BAD_ARG;
+  *frames_out = stft_frames_for(h, n);
+  return PFB_OK;
+}
+
+int pfb_stft_process_async(pfb_stft_handle* h, const void* d_iq, uint64_t n, void* d_out, uint64_t cap,
+                           uint64_t* frames_out) {
+  return pfb::abi_guard([&]() -> int {
+  if (!h || (n > 0 && !d_iq)) return PFB_ERR_BAD_ARG;
+  const uint64_t f = stft_frames_for(h, n);
+  if (frames_out) *frames_out = f;
+  if (f > cap) return PFB_ERR_CAPACITY;
+  if (f > 0 && !d_out) return PFB_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(d_iq) % h->bps || reinterpret_cast<uintptr_t>(d_out) % h->out_elem) return PFB_ERR_BAD_ARG;
+  DeviceGuard g(h->device);
+  return stft_enqueue(h, d_iq, n, d_out, f);
+  });
+}
+
+int pfb_stft_sync(pfb_stft_handle* h) {
+  return pfb::abi_guard([&]() -> int {
+  if (!h) return PFB_ERR_BAD_ARG;
+  DeviceGuard g(h->device);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return PFB_OK;
+  });
+}
+
+int pfb_stft_process(pfb_stft_handle* h, const void* iq, uint64_t n, void* out, uint64_t cap, uint64_t* frames_out,
+                     uint32_t mem) {
+  return pfb::abi_guard([&]() -> int {
+  if (!h || (n > 0 && !iq) || mem > PFB_MEM_DEVICE) return PFB_ERR_BAD_ARG;
+  const uint64_t f = stft_frames_for(h, n);
+  if (frames_out) *frames_out = f;
+  if (f > cap) return PFB_ERR_CAPACITY;
+  if (f > 0 && !out) return PFB_ERR_BAD_ARG;
+  DeviceGuard g(h->device);
+  if (mem == PFB_MEM_DEVICE) {
+    if (reinterpret_cast<uintptr_t>(iq) % h->bps || reinterpret_cast<uintptr_t>(out) % h->out_elem) return PFB_ERR_BAD_ARG;
+    const int rc = stft_enqueue(h, iq, n, out, f);
+    if (rc != PFB_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return PFB_OK;
+  }
+  return stft_process_host(h, iq, n, out);
+  });
+}
+
+int pfb_stft_process_iq_file(pfb_stft_handle* h, const char* path, void* out, uint64_t cap, uint64_t* frames_out,
+                             pfb_iq_info* info_out) {
+  return pfb::abi_guard([&]() -> int {
+  if (!h || !path) return PFB_ERR_BAD_ARG;
+  int fd = -1;
+  pfb_iq_info info{};
+  int rc = open_record(nullptr, path, &fd, &info);
+  if (rc == PFB_OK && ((int)info.sample_format != h->fmt || (int)info.packet.bitWidth != h->bit_width)) {
+    ::close(fd);
+    rc = PFB_ERR_BAD_FORMAT;  // the handle's scale / unpack would not match this record
+  }
+  if (info_out) *info_out = info;
+  if (rc != PFB_OK) return rc;
+  const uint64_t n = info.packet.numSamples;
+  const uint64_t need = stft_frames_for(h, n);
+  if (frames_out) *frames_out = need;
+  if (need > cap) { ::close(fd); return PFB_ERR_CAPACITY; }
+  if (need > 0 && !out) { ::close(fd); return PFB_ERR_BAD_ARG; }
+  // the payload in page-locked chunks: the record is never held in memory
+  const uint64_t chunk = (uint64_t)1 << 22;
+  const size_t chunk_bytes = (size_t)std::min<uint64_t>(chunk, n ? n : 1) * h->bps;
+  char* buf = static_cast<char*>(pfb_host_alloc(chunk_bytes));
+  if (!buf) { ::close(fd); return PFB_ERR_NO_MEMORY; }
+  const unsigned hw = std::thread::hardware_concurrency();
+  const int readers = (int)std::max(1u, std::min(4u, hw ? hw / 2 : 1u));
+  uint64_t done = 0, frames_done = 0;
+  while (done < n && rc == PFB_OK) {
+    const uint64_t m = std::min<uint64_t>(chunk, n - done);
+    if (!pread_parallel(fd, buf, (size_t)m * h->bps, (off_t)info.header_bytes + (off_t)(done * h->bps), readers)) {
+      rc = PFB_ERR_BAD_FORMAT;
+      break;
+    }
+    const uint64_t f = stft_frames_for(h, m);
+    DeviceGuard g(h->device);
+    rc = stft_process_host(h, buf, m, static_cast<char*>(out) + frames_done * (uint64_t)h->nfft * h->out_elem);
+    done += m;
+    frames_done += f;
+  }
+  pfb_host_free(buf);
+  ::close(fd);
+  if (frames_out) *frames_out = frames_done;
+  return rc;
+  });
+}
+
+int pfb_stft_axes(uint32_t nfft, uint32_t L, uint32_t H, double fs, uint32_t order, uint64_t first_frame,
+                  uint64_t frames, double* f_out, double* t_out) {
+  if (nfft < 1 || L < 1 || H < 1 || H > L || L > nfft || order > PFB_STFT_TWOSIDED || !std::isfinite(fs) || fs <= 0)
+    return PFB_ERR_BAD_ARG;
+  if (f_out) {
+    // k_r = r - shift' with shift' = nfft/2 - 1 (even, stft 'centered'), (nfft-1)/2 (odd), 0 (twosided)
+    const long long lo = order == PFB_STFT_TWOSIDED ? 0 : (nfft % 2 == 0 ? (long long)nfft / 2 - 1 : ((long long)nfft - 1) / 2);
+    for (uint32_t r = 0; r < nfft; ++r) f_out[r] = (double)((long long)r - lo) * fs / (double)nfft;
+  }
+  if (t_out)
+    for (uint64_t m = 0; m < frames; ++m) t_out[m] = ((double)(first_frame + m) * (double)H + (double)L / 2.0) / fs;
+  return PFB_OK;
+}
+
+const char* pfb_stft_last_kernel(const pfb_stft_handle* h) { return h ? h->last_kernel : ""; }
+
+int pfb_stft_set_experiment(pfb_stft_handle* h, int experiment) {
+  if (!h || experiment < 0 || experiment > 1) return PFB_ERR_BAD_ARG;
+  if (experiment == 1 && !h->kern->launch_loadstore) return PFB_ERR_UNSUPPORTED;
+  h->experiment = experiment;
+  return PFB_OK;
 }
 
 }  // extern "C"

@@ -123,4 +123,34 @@ hipError_t launch_transpose_slab(const void* slab, long long frames, int M, void
 hipError_t launch_stream_copy(const void* in, void* out, long long n_vec16, hipStream_t s);
 hipError_t launch_mix_copy(const void* in, void* out, long long rows, int write_ratio, int spw, hipStream_t s);
 
+
+// Kernel-side view of one pfb_stft_process call.  "Stream sample s" counts from the first carried sample: s < carry_len
+// is carry[carry_cap - carry_len + s], the rest is in[s - carry_len].  Local frame m covers stream samples
+// [m H, m H + L).
+struct StftParams {
+  const void* in;       // this call's samples (device), sample_format
+  const void* carry;    // carry_cap samples; the last carry_len precede in[0]
+  void* out;            // frames * nfft complex64 or float32
+  const float* win;     // L window coefficients times 2^-(bit_width-1)
+  const float2* tw;     // tw[m] = exp(+j 2 pi m / nfft), m = 0..nfft-1 (from float64)
+  long long n_in;       // samples in `in`
+  long long frames;     // frames to produce
+  int carry_len, carry_cap;
+  int L, H, nfft;
+  int fmt;              // pfb_sample_format
+  int output;           // PFB_STFT_COMPLEX / POWER / DB
+  int order;            // PFB_STFT_CENTERED / TWOSIDED
+  float scale, db_floor;
+};
+using StftLaunchFn = hipError_t (*)(const StftParams&, hipStream_t);
+struct StftKernelInfo {
+  StftLaunchFn launch;
+  const char* name;
+  StftLaunchFn launch_loadstore;  // fused kernels: the loads and stores alone (pfb_stft_set_experiment), else nullptr
+  const char* name_loadstore;
+};
+// nullptr if there is no fused kernel for this FFT length and format
+const StftKernelInfo* find_stft_fused(int nfft, int fmt);
+const StftKernelInfo* stft_generic_kernel();
+
 }  // namespace pfb
