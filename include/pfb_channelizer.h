@@ -425,7 +425,9 @@ int pfb_stft_set_stream(pfb_stft_handle* h, void* hip_stream);
 /* Transform num_samples samples; frames = what pfb_stft_frames_for reports, written to *frames_out.
  * `out` must hold out_capacity_frames * nfft values (PFB_ERR_CAPACITY otherwise, with *frames_out = the
  * frames needed and no state change).  mem = PFB_MEM_HOST / PFB_MEM_DEVICE.  Synchronous.  Device pointers must be
- * aligned to one sample (iq) and one output element (out): PFB_ERR_BAD_ARG otherwise. */
+ * aligned to one sample (iq) and one output element (out): PFB_ERR_BAD_ARG otherwise.  Host pointers are staged
+ * as pfb_process stages them (chunks of at most 64 MiB per side, copy-in, transform and copy-out overlapped;
+ * page-locked buffers from pfb_host_alloc overlap the two PCIe directions). */
 int pfb_stft_process(pfb_stft_handle* h, const void* iq, uint64_t num_samples, void* out,
                      uint64_t out_capacity_frames, uint64_t* frames_out, uint32_t mem);
 /* Same, device pointers, enqueued on the handle's stream without a host sync. */
@@ -434,7 +436,8 @@ int pfb_stft_process_async(pfb_stft_handle* h, const void* d_iq, uint64_t num_sa
 int pfb_stft_sync(pfb_stft_handle* h);
 int pfb_stft_frames_for(const pfb_stft_handle* h, uint64_t num_samples, uint64_t* frames_out);
 /* One .iq record from disk (header checked as in pfb_process_iq_file, format and bit width against the
- * handle), streamed in chunks; `out` is host memory. */
+ * handle), streamed as pfb_process_iq_file streams it: chunks of 2^24 samples read into page-locked buffers
+ * while the previous chunk goes through the host staging above; `out` is host memory. */
 int pfb_stft_process_iq_file(pfb_stft_handle* h, const char* path, void* out, uint64_t out_capacity_frames,
                              uint64_t* frames_out, pfb_iq_info* info_out);
 /* Host-only axes: f_out[r] = k_r*fs/nfft (nfft values), t_out[m] = ((first_frame+m)*H + L/2)/fs (frames
@@ -443,6 +446,8 @@ int pfb_stft_axes(uint32_t fft_length, uint32_t window_length, uint32_t hop, dou
                   uint64_t first_frame, uint64_t frames, double* f_out, double* t_out);
 /* Name of the kernel the last process call launched ("" before the first). */
 const char* pfb_stft_last_kernel(const pfb_stft_handle* h);
+/* The device the handle lives on (pfb_stft_config.device_id resolved, as pfb_get_device). */
+int pfb_stft_get_device(const pfb_stft_handle* h, int* device_id);
 
 #ifdef __cplusplus
 }

@@ -103,7 +103,7 @@ EXPORTS = (
     "pfb_center_frequencies_ordered",
     "pfb_stft_create", "pfb_stft_destroy", "pfb_stft_reset", "pfb_stft_set_stream", "pfb_stft_process",
     "pfb_stft_process_async", "pfb_stft_sync", "pfb_stft_frames_for", "pfb_stft_process_iq_file", "pfb_stft_axes",
-    "pfb_stft_last_kernel",
+    "pfb_stft_last_kernel", "pfb_stft_get_device",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment")
@@ -211,6 +211,7 @@ def load() -> C.CDLL:
     lib.pfb_stft_axes.argtypes = [u32, u32, u32, C.c_double, u32, u64, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.pfb_stft_last_kernel.argtypes = [vp]
     lib.pfb_stft_last_kernel.restype = C.c_char_p
+    lib.pfb_stft_get_device.argtypes = [vp, C.POINTER(C.c_int)]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     for name in EXPORTS + DEV_EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -21,9 +21,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._handle import Handle, is_torch
 
 _FMT = {"int8": L.PFB_FMT_INT8_IQ, "int16": L.PFB_FMT_INT16_IQ, "cf32": L.PFB_FMT_CF32}
-_NP_DTYPE = {L.PFB_FMT_INT8_IQ: np.int8, L.PFB_FMT_INT16_IQ: np.int16, L.PFB_FMT_CF32: np.float32}
 
 
 def design_prototype(num_bands: int, taps_per_band: int = 12, stopband_atten: float = 80.0) -> np.ndarray:
@@ -62,13 +62,15 @@ def center_frequencies(num_bands: int, fs: float, order: str = "fft") -> np.ndar
     return out
 
 
-class Channelizer:
+class Channelizer(Handle):
     """``dsp.Channelizer``-shaped front end of the MI355X polyphase filterbank.
 
     Parameters mirror the System object where it has them (NumFrequencyBands,
     NumTapsPerBand, StopbandAttenuation, DecimationFactor) plus what the raw
     I/Q path needs (sample_format / bit_width from the IqPacket header).
     """
+
+    _kind, _destroy, _get_device = "channelizer", "pfb_destroy", "pfb_get_device"
 
     def __init__(self, num_bands: int, *, taps: np.ndarray | None = None, taps_per_band: int = 12,
                  stopband_atten: float = 80.0, decimation: int | None = None, sample_format: str = "int16",
@@ -104,30 +106,7 @@ class Channelizer:
                           L.PFB_LAYOUT_CHANNEL_MAJOR if channel_major else L.PFB_LAYOUT_FRAME_MAJOR, flags,
                           int(input_offset), int(device))
         L.check(lib.pfb_create(C.byref(cfg), C.byref(self._h)), "pfb_create")
-        self._lib = lib
-        dev = C.c_int(-1)  # device=-1: the library took the device current at pfb_create; it says which one that was
-        L.check(lib.pfb_get_device(self._h, C.byref(dev)), "pfb_get_device")
-        self._device_index = int(dev.value)
-
-    # -- lifecycle ---------------------------------------------------------------
-    def release(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.pfb_destroy(self._h)
-            self._h = C.c_void_p()
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
+        self._created(lib)
 
     def reset(self) -> None:
         L.check(self._lib.pfb_reset(self._h), "pfb_reset")
@@ -171,49 +150,9 @@ class Channelizer:
         L.check(self._lib.pfb_set_state(self._h, blob, len(blob)), "pfb_set_state")
 
     # -- samples -----------------------------------------------------------------
-    def _host_samples(self, iq: np.ndarray) -> tuple[np.ndarray, int]:
-        want = _NP_DTYPE[self.fmt]
-        a = np.asarray(iq)
-        if self.fmt == L.PFB_FMT_CF32 and np.iscomplexobj(a):
-            a = np.ascontiguousarray(a, dtype=np.complex64).view(np.float32)
-        if a.dtype != want:
-            raise TypeError(f"expected {np.dtype(want)} I/Q for this channelizer, got {a.dtype}")
-        a = np.ascontiguousarray(a).reshape(-1)
-        if a.size % 2:
-            raise ValueError("interleaved I,Q needs an even element count")
-        return a, a.size // 2
-
-    def _is_torch(self, x) -> bool:
-        return type(x).__module__.startswith("torch")
-
-    def _device_samples(self, iq) -> int:
-        """Validate a CUDA tensor of raw samples against the handle (dtype, device, contiguity) BEFORE its pointer goes
-        to the library -- a wrong dtype would be read at the handle's sample size, past the end of the allocation --
-        and return its length in complex samples."""
-        import torch
-        want = {L.PFB_FMT_INT8_IQ: (torch.int8,), L.PFB_FMT_INT16_IQ: (torch.int16,),
-                L.PFB_FMT_CF32: (torch.float32, torch.complex64)}[self.fmt]
-        if iq.dtype not in want:
-            raise TypeError(f"expected {want[0]} I/Q for this channelizer, got {iq.dtype}")
-        dev = self.device_index
-        if iq.device.index != dev:
-            raise ValueError(f"I/Q tensor is on cuda:{iq.device.index}, the channelizer on cuda:{dev}")
-        if not iq.is_contiguous():
-            raise ValueError("device I/Q must be contiguous")
-        if iq.is_complex():
-            return iq.numel()
-        if iq.numel() % 2 or (iq.dim() >= 2 and iq.shape[-1] != 2):
-            raise ValueError("interleaved I,Q: the last dimension must be 2 (or a flat tensor of even length)")
-        return iq.numel() // 2
-
-    @property
-    def device_index(self) -> int:
-        """The HIP device ordinal the handle lives on (device=-1 at construction = the device current at that moment)."""
-        return self._device_index
-
     def prime(self, iq) -> None:
         """Feed history without producing output (time-shard halo, resume)."""
-        if self._is_torch(iq) and iq.is_cuda:
+        if is_torch(iq) and iq.is_cuda:
             n = self._device_samples(iq)
             L.check(self._lib.pfb_prime(self._h, C.c_void_p(iq.data_ptr()), n, L.PFB_MEM_DEVICE), "pfb_prime")
             return
@@ -224,39 +163,27 @@ class Channelizer:
         """Channelize one buffer.  numpy in -> numpy out (staged through the GPU);
         torch CUDA tensor in -> torch CUDA tensor out (no copies).
         Returns complex64 of shape (frames, M), or (M, frames) when channel_major."""
-        M = self.num_bands
-        if self._is_torch(iq) and iq.is_cuda:
-            import torch
+        if is_torch(iq) and iq.is_cuda:
             n = self._device_samples(iq)
             F = self.frames_for(n)
-            shape = (M, F) if self.channel_major else (F, M)
-            odt = torch.float32 if self.magnitude else torch.complex64
-            if out is None:
-                out = torch.empty(shape, dtype=odt, device=iq.device)
-            elif (not self._is_torch(out) or not out.is_cuda or out.device != iq.device or out.numel() < F * M
-                  or out.dtype != odt or not out.is_contiguous()):
-                raise ValueError(f"out must be a contiguous {odt} tensor on {iq.device} with room for frames*M values")
+            out = self._output(out, self._shape(F), not self.magnitude, iq.device)
             f = C.c_uint64()
             fn = self._lib.pfb_process if sync else self._lib.pfb_process_async
             args = [self._h, C.c_void_p(iq.data_ptr()), n, C.c_void_p(out.data_ptr()), F, C.byref(f)]
             if sync:
                 args.append(L.PFB_MEM_DEVICE)
             L.check(fn(*args), "pfb_process")
-            return out if out.shape == shape else out.reshape(-1)[: F * M].reshape(shape)
+            return out
         a, n = self._host_samples(iq)
         F = self.frames_for(n)
-        shape = (M, F) if self.channel_major else (F, M)
-        odt = np.float32 if self.magnitude else np.complex64
-        if out is None:
-            res = np.empty(shape, dtype=odt)
-        else:  # the library writes F * M elements through this pointer: check before handing it over
-            if not isinstance(out, np.ndarray) or out.dtype != odt or out.size < F * M or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous numpy array of the output dtype with room for frames*M values")
-            res = out if out.shape == shape else out.reshape(-1)[: F * M].reshape(shape)
+        res = self._output(out, self._shape(F), not self.magnitude)
         f = C.c_uint64()
         L.check(self._lib.pfb_process(self._h, C.c_void_p(a.ctypes.data), n, C.c_void_p(res.ctypes.data), F,
                                       C.byref(f), L.PFB_MEM_HOST), "pfb_process")
         return res
+
+    def _shape(self, frames: int) -> tuple[int, int]:
+        return (self.num_bands, frames) if self.channel_major else (frames, self.num_bands)
 
     # -- time sharding (pfb_shard_attach / pfb_process_shard_async) -------------------
     @property
@@ -289,22 +216,15 @@ class Channelizer:
     def process_shard(self, segment, out=None):
         """Channelize this rank's segment (CUDA tensor, whole frames): halo exchange on a side stream, interior frames at
         once, head frames when the halo has landed.  Asynchronous; ``sync()`` waits for kernels and transfers."""
-        import torch
         n = self._device_samples(segment)
         if n % self.decimation:
             raise ValueError("a shard is cut on frame boundaries: its length must be a multiple of the decimation")
-        F, M = n // self.decimation, self.num_bands
-        shape = (M, F) if self.channel_major else (F, M)
-        odt = torch.float32 if self.magnitude else torch.complex64
-        if out is None:
-            out = torch.empty(shape, dtype=odt, device=segment.device)
-        elif (not out.is_cuda or out.device != segment.device or out.numel() < F * M or out.dtype != odt
-              or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous {odt} tensor on {segment.device} with room for frames*M values")
+        F = n // self.decimation
+        out = self._output(out, self._shape(F), not self.magnitude, segment.device)
         f = C.c_uint64()
         L.check(self._lib.pfb_process_shard_async(self._h, C.c_void_p(segment.data_ptr()), n, C.c_void_p(out.data_ptr()),
                                                   F, C.byref(f)), "pfb_process_shard_async")
-        return out if out.shape == shape else out.reshape(-1)[: F * M].reshape(shape)
+        return out
 
     def kernel_times_ms(self) -> list[float]:
         """Durations of the channelizer kernel launches recorded since PFB_OPT_PROFILE was set."""
@@ -324,14 +244,7 @@ class Channelizer:
         if reset:
             self.reset()  # a fresh channelizer per file, create_pdws_channelized.m:33
         F = self.frames_for(int(info.packet.numSamples))
-        dt = np.float32 if self.magnitude else np.complex64
-        shape = (self.num_bands, F) if self.channel_major else (F, self.num_bands)
-        if out is None:
-            res = np.empty(shape, dtype=dt)
-        else:
-            if out.dtype != dt or out.size < F * self.num_bands or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous array of the output dtype with room for frames*M values")
-            res = out.reshape(-1)[: F * self.num_bands].reshape(shape)
+        res = self._output(out, self._shape(F), not self.magnitude)
         f_out = C.c_uint64()
         got = L.PfbIqInfo()
         L.check(self._lib.pfb_process_iq_file(self._h, path.encode(), C.c_void_p(res.ctypes.data), F, C.byref(f_out),

@@ -1,60 +1,30 @@
-// pfb_api.cpp -- host side of the C ABI in include/pfb_channelizer.h.
+// pfb_api.cpp -- host side of the channelizer's C ABI in include/pfb_channelizer.h.
 //
-// Owns: the handle (taps, twiddles, history, counters), kernel selection, the
-// host-pointer staging path and the state blob.  All arithmetic is in
-// pfb_kernels.hip; there is deliberately no CPU implementation here.
+// Owns: the handle (taps, twiddles, history, counters), kernel selection, its
+// host-pointer and .iq paths (over the staged pipeline and the record reader of
+// pfb_host.h) and the state blob.  All arithmetic is in pfb_kernels.hip; there
+// is deliberately no CPU implementation here.  The STFT's ABI is in pfb_stft_api.cpp.
 #include <hip/hip_runtime.h>
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <sys/types.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <stdexcept>
 #include <string>
 #include <utility>
-#include <thread>
 #include <vector>
 
 #include "pfb_common.h"
 #include "pfb_channelizer_dev.h"
+#include "pfb_host.h"
+
+using pfb::DeviceGuard;
+using pfb::g_detail;
+using pfb::hip_fail;
 
 namespace {
-
-thread_local std::string g_detail;
-
-int hip_fail(hipError_t e, const char* what) {
-  char buf[256];
-  std::snprintf(buf, sizeof(buf), "%s: %s (%d)", what, hipGetErrorString(e), (int)e);
-  g_detail = buf;
-  (void)hipGetLastError();  // clear the sticky error
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice || e == hipErrorInsufficientDriver)
-             ? PFB_ERR_NO_DEVICE
-             : (e == hipErrorOutOfMemory ? PFB_ERR_NO_MEMORY : PFB_ERR_HIP);
-}
-
-#define HIP_TRY(expr)                                  \
-  do {                                                 \
-    const hipError_t e__ = (expr);                     \
-    if (e__ != hipSuccess) return hip_fail(e__, #expr); \
-  } while (0)
-
-struct DeviceGuard {  // run on the handle's device, restore the caller's afterwards
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
 
 constexpr uint32_t kStateMagic = 0x50464231u;  // "PFB1"
 
@@ -101,14 +71,7 @@ struct pfb_handle {
   void* d_matrix = nullptr;     // pfb_pdw_from_iq_file: the record's channel matrix (grow-only)
   size_t matrix_bytes = 0;
   const char* last_kernel = "";
-  // host staging: two sets, so chunk i+1 crosses PCIe inbound while chunk i is transformed and chunk i-1 goes out
-  void* d_stage_in = nullptr;   // set 0 (also pfb_prime's scratch)
-  void* d_stage_out = nullptr;
-  void* d_stage_in2 = nullptr;  // set 1
-  void* d_stage_out2 = nullptr;
-  size_t stage_in_bytes = 0, stage_out_bytes = 0;
-  hipStream_t s_in = nullptr, s_out = nullptr;  // copy streams of the host path
-  hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
+  pfb::HostStage stage;  // host-pointer calls (stage.d_in[0] is also pfb_prime's scratch)
   // PFB_OPT_PROFILE: event pairs around each channelizer kernel launch
   int opt_profile = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;  // reusable pairs
@@ -135,24 +98,14 @@ void free_handle(pfb_handle* h) {
   (void)hipFree(h->d_tw_lane);
   (void)hipFree(h->d_hist[0]);
   (void)hipFree(h->d_hist[1]);
-  (void)hipFree(h->d_stage_in);
-  (void)hipFree(h->d_stage_out);
-  (void)hipFree(h->d_stage_in2);
-  (void)hipFree(h->d_stage_out2);
   (void)hipFree(h->d_slab);
   (void)hipFree(h->d_matrix);
   (void)hipFree(h->d_halo);
-  if (h->s_in) (void)hipStreamDestroy(h->s_in);
-  if (h->s_out) (void)hipStreamDestroy(h->s_out);
+  h->stage.release();
   if (h->s_halo) (void)hipStreamDestroy(h->s_halo);
   if (h->ev_seg) (void)hipEventDestroy(h->ev_seg);
   if (h->ev_halo) (void)hipEventDestroy(h->ev_halo);
   if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
-  for (int i = 0; i < 2; ++i) {
-    if (h->ev_in[i]) (void)hipEventDestroy(h->ev_in[i]);
-    if (h->ev_k[i]) (void)hipEventDestroy(h->ev_k[i]);
-    if (h->ev_out[i]) (void)hipEventDestroy(h->ev_out[i]);
-  }
   for (auto& pr : h->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   delete h;
 }
@@ -336,127 +289,25 @@ int enqueue(pfb_handle* h, const void* d_iq, uint64_t n, void* d_out, uint64_t f
   return advance_state(h, d_iq, n, frames);
 }
 
-int ensure_stage(pfb_handle* h, size_t in_bytes, size_t out_bytes, bool both_sets = false) {
-  if (in_bytes > h->stage_in_bytes || (both_sets && in_bytes > 0 && !h->d_stage_in2)) {
-    const size_t nb = std::max(in_bytes, h->stage_in_bytes);
-    (void)hipFree(h->d_stage_in);
-    (void)hipFree(h->d_stage_in2);
-    h->d_stage_in = h->d_stage_in2 = nullptr; h->stage_in_bytes = 0;
-    HIP_TRY(hipMalloc(&h->d_stage_in, nb));
-    if (both_sets) HIP_TRY(hipMalloc(&h->d_stage_in2, nb));
-    h->stage_in_bytes = nb;
-  }
-  if (out_bytes > h->stage_out_bytes || (both_sets && out_bytes > 0 && !h->d_stage_out2)) {
-    const size_t nb = std::max(out_bytes, h->stage_out_bytes);
-    (void)hipFree(h->d_stage_out);
-    (void)hipFree(h->d_stage_out2);
-    h->d_stage_out = h->d_stage_out2 = nullptr; h->stage_out_bytes = 0;
-    HIP_TRY(hipMalloc(&h->d_stage_out, nb));
-    if (both_sets) HIP_TRY(hipMalloc(&h->d_stage_out2, nb));
-    h->stage_out_bytes = nb;
-  }
-  return PFB_OK;
-}
-
-// channel-major: `out` is the whole M x out_ld matrix and this call fills rows [out_row0, out_row0 + frames_total) of
-// every column (pfb_process: out_ld = frames_total, out_row0 = 0; the .iq front end walks out_row0 through a record)
-// device_out: `out` is device memory (frame-major rows follow each other; channel-major as above): nothing is
-// copied back and the call returns once the input has left the host buffer, the kernels still queued on the
-// handle's stream.
-int process_host_pipeline(pfb_handle* h, const void* iq, uint64_t n, void* out, uint64_t frames_total, uint64_t out_ld,
-                          uint64_t out_row0, bool device_out);
-
-int process_host(pfb_handle* h, const void* iq, uint64_t n, void* out, uint64_t frames_total, uint64_t out_ld,
-                 uint64_t out_row0, bool device_out = false) {
-  const int rc = process_host_pipeline(h, iq, n, out, frames_total, out_ld, out_row0, device_out);
-  if (rc != PFB_OK) {
-    // a failed step returned from the middle of the pipeline: copies to and from the CALLER's buffers may still be
-    // in flight on the three streams -- drain them before the caller is told it may free or reuse those buffers
-    if (h->s_in) (void)hipStreamSynchronize(h->s_in);
-    (void)hipStreamSynchronize(h->stream);
-    if (h->s_out) (void)hipStreamSynchronize(h->s_out);
-    (void)hipGetLastError();
-  }
-  return rc;
-}
-
-int process_host_pipeline(pfb_handle* h, const void* iq, uint64_t n, void* out, uint64_t frames_total, uint64_t out_ld,
-                          uint64_t out_row0, bool device_out) {
-  // Stage through device buffers in chunks (multiples of D so chunks never change the carried phase
-  // pattern mid-call beyond what the stream semantics already define).  Three streams and two buffer
-  // sets: chunk i+1 is copied in while chunk i is transformed and chunk i-1 is copied out, so a caller
-  // whose buffers are page-locked (pfb_host_alloc) sees both PCIe directions busy at once; with pageable
-  // memory the runtime's own staging serialises the copies and this degrades to the plain sequence.
-  uint64_t chunk = h->opt_host_chunk > 0 ? (uint64_t)h->opt_host_chunk : (uint64_t)1 << 24;
+// The host path stages through h->stage in chunks of whole frames, so a chunk boundary never falls inside a frame's
+// decimation step: PFB_OPT_HOST_CHUNK_SAMPLES, or 2^24 samples.  `out` as in pfb::stage_host: pfb_process fills rows
+// [0, frames) of a frame-major buffer or of an M x frames matrix; the .iq front end walks row0 through a record.
+int process_host(pfb_handle* h, const void* iq, uint64_t n, const pfb::StageOut& out, uint64_t chunk = 0) {
+  if (chunk == 0) chunk = h->opt_host_chunk > 0 ? (uint64_t)h->opt_host_chunk : (uint64_t)1 << 24;
   chunk = ((chunk + h->D - 1) / h->D) * h->D;
-  const uint64_t max_frames = chunk / h->D + 1;
-  const int rc = ensure_stage(h, (size_t)std::min<uint64_t>(chunk, n ? n : 1) * h->bps,
-                              device_out ? 0
-                                         : (size_t)std::min<uint64_t>(max_frames, frames_total ? frames_total : 1) * h->M *
-                                               sizeof(float2),
-                              true);
-  if (rc != PFB_OK) return rc;
-  if (!h->s_in) {
-    HIP_TRY(hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_in[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_k[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_out[i], hipEventDisableTiming));
-    }
-  }
-  void* const st_in[2] = {h->d_stage_in, h->d_stage_in2};
-  void* const st_out[2] = {h->d_stage_out, h->d_stage_out2};
-  const char* src = static_cast<const char*>(iq);
-  char* dst = static_cast<char*>(out);
-  uint64_t done = 0, frames_done = 0;
-  // whatever the caller queued on the handle's stream comes first
-  HIP_TRY(hipEventRecord(h->ev_k[1], h->stream));
-  HIP_TRY(hipStreamWaitEvent(h->s_in, h->ev_k[1], 0));
-  int rc2 = PFB_OK;
-  for (uint64_t i = 0; done < n; ++i) {
-    const int b = (int)(i & 1);
-    const uint64_t m = std::min<uint64_t>(chunk, n - done);
-    const uint64_t f = frames_for(h, m);
-    if (i >= 2) HIP_TRY(hipStreamWaitEvent(h->s_in, h->ev_k[b], 0));  // the kernel of chunk i-2 has read this input buffer
-    HIP_TRY(hipMemcpyAsync(st_in[b], src + done * h->bps, (size_t)m * h->bps, hipMemcpyHostToDevice, h->s_in));
-    HIP_TRY(hipEventRecord(h->ev_in[b], h->s_in));
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_in[b], 0));
-    if (device_out) {
-      if (h->layout == PFB_LAYOUT_FRAME_MAJOR)
-        rc2 = enqueue(h, st_in[b], m, dst + frames_done * h->M * h->out_elem, f, (int64_t)f, 0);
-      else
-        rc2 = enqueue(h, st_in[b], m, dst, f, (int64_t)out_ld, (int64_t)(out_row0 + frames_done));
-      if (rc2 != PFB_OK) break;
-      HIP_TRY(hipEventRecord(h->ev_k[b], h->stream));
-      done += m;
-      frames_done += f;
-      continue;
-    }
-    if (i >= 2) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_out[b], 0));  // chunk i-2 has left this output buffer
-    rc2 = enqueue(h, st_in[b], m, st_out[b], f, (int64_t)f, 0);
-    if (rc2 != PFB_OK) break;
-    HIP_TRY(hipEventRecord(h->ev_k[b], h->stream));
-    HIP_TRY(hipStreamWaitEvent(h->s_out, h->ev_k[b], 0));
-    if (f > 0) {
-      if (h->layout == PFB_LAYOUT_FRAME_MAJOR) {
-        HIP_TRY(hipMemcpyAsync(dst + frames_done * h->M * h->out_elem, st_out[b], (size_t)f * h->M * h->out_elem,
-                               hipMemcpyDeviceToHost, h->s_out));
-      } else {  // column k of this chunk -> rows [frames_done, frames_done+f) of column k of the call
-        HIP_TRY(hipMemcpy2DAsync(dst + (out_row0 + frames_done) * h->out_elem, (size_t)out_ld * h->out_elem, st_out[b],
-                                 (size_t)f * h->out_elem, (size_t)f * h->out_elem, (size_t)h->M, hipMemcpyDeviceToHost,
-                                 h->s_out));
-      }
-    }
-    HIP_TRY(hipEventRecord(h->ev_out[b], h->s_out));
-    done += m;
-    frames_done += f;
-  }
-  HIP_TRY(hipStreamSynchronize(h->s_in));
-  if (device_out) return rc2;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipStreamSynchronize(h->s_out));
-  return rc2;
+  const pfb::StageSteps steps{
+      chunk, chunk / h->D + 1, (size_t)h->bps, (size_t)h->M * h->out_elem,
+      [h](uint64_t m) { return frames_for(h, m); },
+      [h](const void* d_in, uint64_t m, void* d_out, uint64_t f, int64_t out_ld, int64_t out_row0) {
+        return enqueue(h, d_in, m, d_out, f, out_ld, out_row0);
+      }};
+  return pfb::stage_host(h->stage, h->stream, steps, iq, n, out);
+}
+
+// rows [row0, ...) of the handle's output layout: frame-major rows, or an M x ld channel-major matrix
+pfb::StageOut layout_out(const pfb_handle* h, void* out, bool device, uint64_t ld, uint64_t row0) {
+  return h->layout == PFB_LAYOUT_FRAME_MAJOR ? pfb::StageOut{out, device, 0, row0, 0}
+                                             : pfb::StageOut{out, device, ld, row0, h->M};
 }
 
 }  // namespace
@@ -575,16 +426,9 @@ int pfb_create(const pfb_config* cfg, pfb_handle** out) {
   const int off = cfg->input_offset < 0 ? (int)D - 1 : cfg->input_offset;
   if (off >= (int)D) return PFB_ERR_BAD_ARG;
 
-  int ndev = 0;
-  const hipError_t ce = hipGetDeviceCount(&ndev);
-  if (ce != hipSuccess || ndev <= 0) {
-    g_detail = std::string("hipGetDeviceCount: ") + (ce == hipSuccess ? "0 devices" : hipGetErrorString(ce));
-    (void)hipGetLastError();
-    return PFB_ERR_NO_DEVICE;
-  }
-  int dev = cfg->device_id;
-  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-  if (dev >= ndev) return PFB_ERR_BAD_ARG;
+  int dev = 0;
+  const int drc = pfb::resolve_device(cfg->device_id, &dev);
+  if (drc != PFB_OK) return drc;
 
   pfb_handle* h = new (std::nothrow) pfb_handle();
   if (!h) return PFB_ERR_NO_MEMORY;
@@ -609,19 +453,12 @@ int pfb_create(const pfb_config* cfg, pfb_handle** out) {
   std::vector<float> taps(L, 0.0f);
   const float scale = std::ldexp(1.0f, -(bw - 1));  // power of two: h*scale is exact
   for (size_t i = 0; i < L_given; ++i) taps[i] = cfg->taps[i] * scale;
-  std::vector<float2> tw(M);
-  const double two_pi = 6.283185307179586476925286766559;
-  for (uint32_t m = 0; m < M; ++m) {
-    tw[m].x = (float)std::cos(two_pi * (double)m / (double)M);
-    tw[m].y = (float)std::sin(two_pi * (double)m / (double)M);
-  }
   const size_t hist_bytes = (size_t)h->hist_samples * h->bps;
   hipError_t e = hipMalloc((void**)&h->d_taps, L * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_tw, M * sizeof(float2));
+  if (e == hipSuccess) e = pfb::upload_twiddles(M, &h->d_tw);
   if (e == hipSuccess) e = hipMalloc(&h->d_hist[0], hist_bytes);
   if (e == hipSuccess) e = hipMalloc(&h->d_hist[1], hist_bytes);
   if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps.data(), L * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->d_tw, tw.data(), M * sizeof(float2), hipMemcpyHostToDevice);
   if (e == hipSuccess && h->fast) {
     e = hipMalloc((void**)&h->d_taps_lane, (size_t)h->fast->taps_lane_floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_tw_lane, (size_t)h->fast->tw_lane_elems * sizeof(float2));
@@ -663,15 +500,7 @@ int pfb_reset(pfb_handle* h) {
 int pfb_set_stream(pfb_handle* h, void* hip_stream) {
   return pfb::abi_guard([&]() -> int {
   if (!h) return PFB_ERR_BAD_ARG;
-  hipStream_t next = static_cast<hipStream_t>(hip_stream);
-  if (next != h->stream) {  // what the old stream still has queued for this handle (kernels, the history update) comes first
-    DeviceGuard g(h->device);
-    if (!h->ev_switch) HIP_TRY(hipEventCreateWithFlags(&h->ev_switch, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->ev_switch, h->stream));
-    HIP_TRY(hipStreamWaitEvent(next, h->ev_switch, 0));
-    h->stream = next;
-  }
-  return PFB_OK;
+  return pfb::switch_stream(h->device, &h->stream, &h->ev_switch, static_cast<hipStream_t>(hip_stream));
   });
 }
 
@@ -718,109 +547,29 @@ int pfb_process(pfb_handle* h, const void* iq, uint64_t n, void* out, uint64_t c
     HIP_TRY(hipStreamSynchronize(h->stream));
     return PFB_OK;
   }
-  return process_host(h, iq, n, out, f, f, 0);
+  return process_host(h, iq, n, layout_out(h, out, false, f, 0));
   });
 }
 
 namespace {
 
-// read exactly `bytes` at `offset` of fd into dst with `nthreads` concurrent pread streams (one thread copies out
-// of the page cache at ~7 GB/s, less than PCIe takes; four keep the link busy)
-bool pread_parallel(int fd, char* dst, size_t bytes, off_t offset, int nthreads) {
-  auto read_range = [fd](char* d, size_t len, off_t off) {
-    while (len > 0) {
-      const ssize_t r = ::pread(fd, d, len, off);
-      if (r <= 0) return false;
-      d += r; len -= (size_t)r; off += r;
-    }
-    return true;
-  };
-  if (nthreads <= 1 || bytes < ((size_t)4 << 20)) return read_range(dst, bytes, offset);
-  const size_t part = ((bytes / (size_t)nthreads) + 4095) & ~(size_t)4095;
-  std::vector<std::thread> th;
-  std::vector<char> ok((size_t)nthreads, 1);
-  for (int t = 0; t < nthreads; ++t) {
-    const size_t lo = std::min(bytes, part * (size_t)t), hi = std::min(bytes, part * (size_t)(t + 1));
-    if (hi > lo) th.emplace_back([&, t, lo, hi] { ok[(size_t)t] = read_range(dst + lo, hi - lo, offset + (off_t)lo); });
-  }
-  for (auto& x : th) x.join();
-  for (char c : ok) if (!c) return false;
-  return true;
-}
-
-}  // namespace
-
-namespace {
-
-// open a record, parse and check its header (payload length; format and bit width against the handle, if any)
-int open_record(pfb_handle* h, const char* path, int* fd_out, pfb_iq_info* info) {
-  const int fd = ::open(path, O_RDONLY);
-  if (fd < 0) { g_detail = std::string("cannot open ") + path; return PFB_ERR_BAD_ARG; }
-  unsigned char head[PFB_IQ_HEADER_BYTES];
-  const ssize_t got = ::pread(fd, head, sizeof(head), 0);
-  int rc = pfb_iq_parse_header(head, got > 0 ? (size_t)got : 0, info);
-  if (rc == PFB_OK && h && ((int)info->sample_format != h->fmt || (int)info->packet.bitWidth != h->bit_width))
-    rc = PFB_ERR_BAD_FORMAT;  // the handle's scale / unpack would not match this record
-  if (rc == PFB_OK) {
-    struct stat st;
-    const long long size = ::fstat(fd, &st) == 0 ? (long long)st.st_size : -1;
-    if (size - (long long)info->header_bytes != (long long)info->packet.numSamples * (long long)info->bytes_per_sample)
-      rc = PFB_ERR_BAD_FORMAT;
-  }
-  if (rc != PFB_OK) { ::close(fd); return rc; }
-  *fd_out = fd;
-  return PFB_OK;
-}
-
-// Stream the record's payload through the channelizer.  Two page-locked chunk buffers: reader threads fill one
-// from the file while the other crosses PCIe and is transformed (the staged host path overlaps its own copy-in /
-// transform / copy-out underneath).  device_out: `out` is device memory and nothing comes back.
-int stream_record(pfb_handle* h, int fd, const pfb_iq_info& info, void* out, uint64_t need, bool device_out,
-                  uint64_t* frames_out) {
-  const uint64_t n = info.packet.numSamples;
+// Stream the record's payload through the channelizer: the record reader's two page-locked chunk buffers, one filled
+// from the file while the other crosses PCIe and is transformed by the staged host path, which overlaps its own
+// copy-in / transform / copy-out underneath.  device_out: `out` is device memory and nothing comes back.
+int stream_record(pfb_handle* h, pfb::Record& rec, void* out, uint64_t need, bool device_out, uint64_t* frames_out) {
   const uint64_t chunk = (((uint64_t)1 << 24) / h->D) * h->D;  // whole frames, 64 MB of int16 I/Q
-  const size_t chunk_bytes = (size_t)std::min<uint64_t>(chunk, n ? n : 1) * h->bps;
-  char* bufs[2] = {static_cast<char*>(pfb_host_alloc(chunk_bytes)), static_cast<char*>(pfb_host_alloc(chunk_bytes))};
-  if (!bufs[0] || !bufs[1]) {
-    pfb_host_free(bufs[0]);
-    pfb_host_free(bufs[1]);
-    return PFB_ERR_NO_MEMORY;
-  }
-  const unsigned hw = std::thread::hardware_concurrency();
-  const int readers = (int)std::max(1u, std::min(4u, hw ? hw / 2 : 1u));
-  auto read_chunk = [&](char* dst, uint64_t first, uint64_t m) {
-    return pread_parallel(fd, dst, (size_t)m * h->bps, (off_t)info.header_bytes + (off_t)(first * h->bps), readers);
-  };
   // four staging steps per chunk, so that the copy-in / transform / copy-out pipeline of the host path has stages
   // to overlap inside each call (measured: 3.3 -> 3.7 GS/s; larger file chunks lose more at the ends than they gain)
-  const int64_t user_host_chunk = h->opt_host_chunk;
-  if (user_host_chunk <= 0) h->opt_host_chunk = (int64_t)1 << 22;
-  int rc = PFB_OK;
-  uint64_t done = 0, frames_done = 0;
-  bool have = n > 0 && read_chunk(bufs[0], 0, std::min<uint64_t>(chunk, n));
-  if (n > 0 && !have) rc = PFB_ERR_BAD_FORMAT;
-  for (uint64_t i = 0; done < n && rc == PFB_OK; ++i) {
-    const uint64_t m = std::min<uint64_t>(chunk, n - done);
-    const uint64_t m_next = std::min<uint64_t>(chunk, n - done - m);
-    bool next_ok = true;
-    std::thread reader;
-    if (m_next > 0) reader = std::thread([&, i, m_next] { next_ok = read_chunk(bufs[(i + 1) & 1], done + m, m_next); });
+  const uint64_t steps = h->opt_host_chunk > 0 ? (uint64_t)h->opt_host_chunk : (uint64_t)1 << 22;
+  uint64_t frames_done = 0;
+  const int rc = rec.read(chunk, [&](const char* buf, uint64_t, uint64_t m) {
     const uint64_t fr = frames_for(h, m);
-    {
-      DeviceGuard g(h->device);
-      if (h->layout == PFB_LAYOUT_FRAME_MAJOR)
-        rc = process_host(h, bufs[i & 1], m, static_cast<char*>(out) + frames_done * h->M * h->out_elem, fr, fr, 0, device_out);
-      else  // channel-major: one M x `need` matrix for the whole record, this chunk fills rows frames_done...
-        rc = process_host(h, bufs[i & 1], m, out, fr, need, frames_done, device_out);
-    }
-    if (reader.joinable()) reader.join();
-    if (rc == PFB_OK && !next_ok) rc = PFB_ERR_BAD_FORMAT;
-    done += m;
+    DeviceGuard g(h->device);
+    // channel-major: one M x `need` matrix for the whole record, this chunk fills rows frames_done...
+    const int r = process_host(h, buf, m, layout_out(h, out, device_out, need, frames_done), steps);
     frames_done += fr;
-  }
-  h->opt_host_chunk = user_host_chunk;
-  pfb_host_free(bufs[0]);
-  pfb_host_free(bufs[1]);
+    return r;
+  });
   if (frames_out) *frames_out = frames_done;
   return rc;
 }
@@ -831,18 +580,15 @@ int pfb_process_iq_file(pfb_handle* h, const char* path, void* out, uint64_t cap
                         pfb_iq_info* info_out) {
   return pfb::abi_guard([&]() -> int {
   if (!h || !path) return PFB_ERR_BAD_ARG;
-  int fd = -1;
-  pfb_iq_info info{};  // zeroed: copied out below even when the record could not be opened
-  int rc = open_record(h, path, &fd, &info);
-  if (info_out) *info_out = info;
+  pfb::Record rec;
+  const int rc = rec.open(path, h->fmt, h->bit_width);
+  if (info_out) *info_out = rec.info;
   if (rc != PFB_OK) return rc;
-  const uint64_t need = frames_for(h, info.packet.numSamples);
+  const uint64_t need = frames_for(h, rec.info.packet.numSamples);
   if (frames_out) *frames_out = need;
-  if (need > cap) { ::close(fd); return PFB_ERR_CAPACITY; }
-  if (need > 0 && !out) { ::close(fd); return PFB_ERR_BAD_ARG; }
-  rc = stream_record(h, fd, info, out, need, false, frames_out);
-  ::close(fd);
-  return rc;
+  if (need > cap) return PFB_ERR_CAPACITY;
+  if (need > 0 && !out) return PFB_ERR_BAD_ARG;
+  return stream_record(h, rec, out, need, false, frames_out);
   });
 }
 
@@ -852,26 +598,25 @@ int pfb_pdw_from_iq_file(pfb_handle* h, const char* path, double snr_threshold_d
   if (!h || !path || !count || (capacity > 0 && !out)) return PFB_ERR_BAD_ARG;
   // the PDW stage reads a frame-major complex matrix (mag = abs(iq), phase = angle(iq), :67-68)
   if (h->layout != PFB_LAYOUT_FRAME_MAJOR || (h->flags & PFB_FLAG_MAGNITUDE)) return PFB_ERR_UNSUPPORTED;
-  int fd = -1;
-  pfb_iq_info info{};  // zeroed: copied out below even when the record could not be opened
-  int rc = open_record(h, path, &fd, &info);
-  if (info_out) *info_out = info;
+  pfb::Record rec;
+  int rc = rec.open(path, h->fmt, h->bit_width);
+  if (info_out) *info_out = rec.info;
   if (rc != PFB_OK) return rc;
+  const pfb_iq_info& info = rec.info;
   const uint64_t need = frames_for(h, info.packet.numSamples);
   const size_t bytes = (size_t)std::max<uint64_t>(need, 1) * h->M * sizeof(float2);
   {
     DeviceGuard g(h->device);
     if (bytes > h->matrix_bytes) {
-      if (hipStreamSynchronize(h->stream) != hipSuccess) { ::close(fd); return PFB_ERR_HIP; }
+      if (hipStreamSynchronize(h->stream) != hipSuccess) return PFB_ERR_HIP;
       (void)hipFree(h->d_matrix);
       h->d_matrix = nullptr; h->matrix_bytes = 0;
-      if (hipMalloc(&h->d_matrix, bytes) != hipSuccess) { (void)hipGetLastError(); ::close(fd); return PFB_ERR_NO_MEMORY; }
+      if (hipMalloc(&h->d_matrix, bytes) != hipSuccess) { (void)hipGetLastError(); return PFB_ERR_NO_MEMORY; }
       h->matrix_bytes = bytes;
     }
   }
   uint64_t frames = 0;
-  rc = stream_record(h, fd, info, h->d_matrix, need, true, &frames);
-  ::close(fd);
+  rc = stream_record(h, rec, h->d_matrix, need, true, &frames);
   if (rc != PFB_OK) return rc;
   if (frames == 0) {  // a record shorter than one frame holds no pulse
     *count = 0;
@@ -889,64 +634,39 @@ int pfb_pdw_raw_from_iq_file(const char* path, double snr_threshold_db, double t
                              int32_t device_id) {
   return pfb::abi_guard([&]() -> int {
   if (!path || !count || (capacity > 0 && !out)) return PFB_ERR_BAD_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return PFB_ERR_NO_DEVICE; }
-  int dev = device_id;
-  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-  if (dev >= ndev) return PFB_ERR_BAD_ARG;
-  int fd = -1;
-  pfb_iq_info info{};
-  int rc = open_record(nullptr, path, &fd, &info);
-  if (info_out) *info_out = info;
+  int dev = 0;
+  int rc = pfb::resolve_device(device_id, &dev);
   if (rc != PFB_OK) return rc;
+  pfb::Record rec;
+  rc = rec.open(path);
+  if (info_out) *info_out = rec.info;
+  if (rc != PFB_OK) return rc;
+  const pfb_iq_info& info = rec.info;
   DeviceGuard g(dev);
   const uint64_t n = info.packet.numSamples;
   const size_t bps = info.bytes_per_sample;
-  if (n == 0) { ::close(fd); return PFB_ERR_BAD_ARG; }
-  // the record goes to the device through two page-locked 64 MB buffers: four pread streams fill one while the
-  // other crosses PCIe; the extraction then runs on the device-resident stream
+  if (n == 0) return PFB_ERR_BAD_ARG;
+  // the record goes to the device in 64 MB chunks through the record reader's page-locked buffers; the extraction
+  // then runs on the device-resident stream
   void* d_iq = nullptr;
   hipStream_t st = nullptr;
-  const size_t chunk = (size_t)64 << 20;
-  char* bufs[2] = {static_cast<char*>(pfb_host_alloc(std::min(chunk, n * bps))),
-                   static_cast<char*>(pfb_host_alloc(std::min(chunk, n * bps)))};
-  auto cleanup = [&] {
-    pfb_host_free(bufs[0]);
-    pfb_host_free(bufs[1]);
-    if (st) (void)hipStreamDestroy(st);
-    (void)hipFree(d_iq);
-    ::close(fd);
-  };
-  if (!bufs[0] || !bufs[1] || hipMalloc(&d_iq, n * bps) != hipSuccess || hipStreamCreate(&st) != hipSuccess) {
+  if (hipMalloc(&d_iq, n * bps) != hipSuccess || hipStreamCreate(&st) != hipSuccess) rc = PFB_ERR_NO_MEMORY;
+  if (rc == PFB_OK) {
+    rc = rec.read(((uint64_t)64 << 20) / bps, [&](const char* buf, uint64_t first, uint64_t m) {
+      const hipError_t e = hipMemcpyAsync(static_cast<char*>(d_iq) + first * bps, buf, m * bps, hipMemcpyHostToDevice, st);
+      const hipError_t e2 = hipStreamSynchronize(st);
+      return (e != hipSuccess || e2 != hipSuccess) ? hip_fail(e != hipSuccess ? e : e2, "pfb_pdw_raw_from_iq_file")
+                                                   : (int)PFB_OK;
+    });
+  } else {
     (void)hipGetLastError();
-    cleanup();
-    return PFB_ERR_NO_MEMORY;
   }
-  const unsigned hw = std::thread::hardware_concurrency();
-  const int readers = (int)std::max(1u, std::min(4u, hw ? hw / 2 : 1u));
-  const size_t total = n * bps;
-  auto read_chunk = [&](char* dst, size_t first, size_t len) {
-    return pread_parallel(fd, dst, len, (off_t)info.header_bytes + (off_t)first, readers);
-  };
-  bool ok = read_chunk(bufs[0], 0, std::min(chunk, total));
-  size_t done = 0;
-  for (size_t i = 0; done < total && ok; ++i) {
-    const size_t len = std::min(chunk, total - done), next = std::min(chunk, total - done - len);
-    bool next_ok = true;
-    std::thread reader;
-    if (next > 0) reader = std::thread([&, i, next] { next_ok = read_chunk(bufs[(i + 1) & 1], done + len, next); });
-    const hipError_t e = hipMemcpyAsync(static_cast<char*>(d_iq) + done, bufs[i & 1], len, hipMemcpyHostToDevice, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (reader.joinable()) reader.join();
-    if (e != hipSuccess || e2 != hipSuccess) { cleanup(); return hip_fail(e != hipSuccess ? e : e2, "pfb_pdw_raw_from_iq_file"); }
-    ok = next_ok;
-    done += len;
-  }
-  if (!ok) { cleanup(); return PFB_ERR_BAD_FORMAT; }
-  rc = pfb_pdw_extract_raw(d_iq, n, info.sample_format, info.packet.bitWidth, (double)info.packet.sampleRateSps,
-                           (double)info.packet.frequencyHz, info.packet.sampleStartTime, snr_threshold_db,
-                           trailing_threshold_db, out, capacity, count, noise_floor_out, PFB_MEM_DEVICE, dev, st);
-  cleanup();
+  if (rc == PFB_OK)
+    rc = pfb_pdw_extract_raw(d_iq, n, info.sample_format, info.packet.bitWidth, (double)info.packet.sampleRateSps,
+                             (double)info.packet.frequencyHz, info.packet.sampleStartTime, snr_threshold_db,
+                             trailing_threshold_db, out, capacity, count, noise_floor_out, PFB_MEM_DEVICE, dev, st);
+  if (st) (void)hipStreamDestroy(st);
+  (void)hipFree(d_iq);
   return rc;
   });
 }
@@ -964,10 +684,10 @@ int pfb_prime(pfb_handle* h, const void* iq, uint64_t n, uint32_t mem) {
   const char* tail = static_cast<const char*>(iq) + (n - keep) * h->bps;
   const void* d_tail = tail;
   if (mem == PFB_MEM_HOST) {
-    const int rc = ensure_stage(h, (size_t)keep * h->bps, 0);
+    const int rc = h->stage.ensure((size_t)keep * h->bps, 0);
     if (rc != PFB_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(h->d_stage_in, tail, (size_t)keep * h->bps, hipMemcpyHostToDevice, h->stream));
-    d_tail = h->d_stage_in;
+    HIP_TRY(hipMemcpyAsync(h->stage.d_in[0], tail, (size_t)keep * h->bps, hipMemcpyHostToDevice, h->stream));
+    d_tail = h->stage.d_in[0];
   }
   HIP_TRY(pfb::launch_update_history(h->d_hist[h->cur], d_tail, (long long)keep, h->d_hist[h->cur ^ 1],
                                      h->hist_samples, h->bps, h->stream));
@@ -1239,13 +959,9 @@ void pfb_host_free(void* p) {
 int pfb_measure_stream_copy(int device_id, uint64_t bytes_in, int iters, double* bytes_per_sec) {
   return pfb::abi_guard([&]() -> int {
   if (!bytes_per_sec || iters < 1 || bytes_in < 512) return PFB_ERR_BAD_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return PFB_ERR_NO_DEVICE;
-  }
-  int dev = device_id;
-  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+  int dev = 0;
+  const int drc = pfb::resolve_device(device_id, &dev);
+  if (drc != PFB_OK) return drc;
   DeviceGuard g(dev);
   const long long nvec = (long long)(bytes_in / 512) * 32;  // whole row pairs (512 bytes of input per wave)
   void *in = nullptr, *out = nullptr;
@@ -1278,13 +994,9 @@ int pfb_measure_mix_copy(int device_id, uint64_t bytes_in, uint32_t write_ratio,
   return pfb::abi_guard([&]() -> int {
   if (!bytes_per_sec || iters < 1 || (write_ratio != 2 && write_ratio != 4) || rows_per_wave < 2 || (rows_per_wave & 1))
     return PFB_ERR_BAD_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return PFB_ERR_NO_DEVICE;
-  }
-  int dev = device_id;
-  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+  int dev = 0;
+  const int drc = pfb::resolve_device(device_id, &dev);
+  if (drc != PFB_OK) return drc;
   DeviceGuard g(dev);
   const long long rows = (long long)(bytes_in / 256) / (4ll * rows_per_wave) * (4ll * rows_per_wave);  // whole workgroups
   if (rows <= 0) return PFB_ERR_BAD_ARG;
@@ -1311,366 +1023,6 @@ int pfb_measure_mix_copy(int device_id, uint64_t bytes_in, uint32_t write_ratio,
   (void)hipFree(out);
   return rc;
   });
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------
-// short-time Fourier transform (pfb_stft_*; kernels in pfb_stft.hip)
-
-struct pfb_stft_handle {
-  int L = 0, H = 0, nfft = 0;
-  int fmt = 0, bit_width = 0, output = 0, order = 0, kernel_opt = 0;
-  float scale = 1.f, db_floor = 0.f;
-  int device = 0;
-  int bps = 0;               // bytes per input sample
-  int out_elem = 8;          // complex64, or float32 for power / dB
-  float* d_win = nullptr;    // L: window x 2^-(bit_width-1)
-  float2* d_tw = nullptr;    // nfft: e^{+j 2 pi m / nfft}
-  void* d_carry[2] = {nullptr, nullptr};  // L raw samples each; the last carry_len are the start of the next frame
-  int cur = 0;
-  uint64_t carry_len = 0;    // < L
-  hipStream_t stream = nullptr;
-  const pfb::StftKernelInfo* kern = nullptr;
-  const char* last_kernel = "";
-  int experiment = 0;          // pfb_stft_set_experiment (pfb_channelizer_dev.h): 1 = loads and stores only
-  void* d_stage_in = nullptr;  // host path
-  void* d_stage_out = nullptr;
-  size_t stage_in_bytes = 0, stage_out_bytes = 0;
-  hipEvent_t ev_switch = nullptr;
-};
-
-namespace {
-
-void free_stft(pfb_stft_handle* h) {
-  if (!h) return;
-  DeviceGuard g(h->device);
-  (void)hipFree(h->d_win);
-  (void)hipFree(h->d_tw);
-  (void)hipFree(h->d_carry[0]);
-  (void)hipFree(h->d_carry[1]);
-  (void)hipFree(h->d_stage_in);
-  (void)hipFree(h->d_stage_out);
-  if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
-  delete h;
-}
-
-uint64_t stft_frames_for(const pfb_stft_handle* h, uint64_t n) {
-  const uint64_t total = h->carry_len + n;
-  return total >= (uint64_t)h->L ? (total - (uint64_t)h->L) / (uint64_t)h->H + 1 : 0;
-}
-
-// kernel + carry update for device-resident buffers; no host sync
-int stft_enqueue(pfb_stft_handle* h, const void* d_iq, uint64_t n, void* d_out, uint64_t frames) {
-  if (frames > 0) {
-    pfb::StftParams p{};
-    p.in = d_iq;
-    p.carry = h->d_carry[h->cur];
-    p.out = d_out;
-    p.win = h->d_win;
-    p.tw = h->d_tw;
-    p.n_in = (long long)n;
-    p.frames = (long long)frames;
-    p.carry_len = (int)h->carry_len;
-    p.carry_cap = h->L;
-    p.L = h->L; p.H = h->H; p.nfft = h->nfft;
-    p.fmt = h->fmt; p.output = h->output; p.order = h->order;
-    p.scale = h->scale; p.db_floor = h->db_floor;
-    const bool study = h->experiment == 1;
-    HIP_TRY((study ? h->kern->launch_loadstore : h->kern->launch)(p, h->stream));
-    h->last_kernel = study ? h->kern->name_loadstore : h->kern->name;
-  }
-  if (n > 0) {  // the last L samples of [carry | in]: the next frame starts in them
-    HIP_TRY(pfb::launch_update_history(h->d_carry[h->cur], d_iq, (long long)n, h->d_carry[h->cur ^ 1], h->L, h->bps,
-                                       h->stream));
-    h->cur ^= 1;
-  }
-  h->carry_len = h->carry_len + n - frames * (uint64_t)h->H;
-  return PFB_OK;
-}
-
-int stft_ensure_stage(pfb_stft_handle* h, size_t in_bytes, size_t out_bytes) {
-  if (in_bytes > h->stage_in_bytes) {
-    (void)hipFree(h->d_stage_in);
-    h->d_stage_in = nullptr; h->stage_in_bytes = 0;
-    HIP_TRY(hipMalloc(&h->d_stage_in, in_bytes));
-    h->stage_in_bytes = in_bytes;
-  }
-  if (out_bytes > h->stage_out_bytes) {
-    (void)hipFree(h->d_stage_out);
-    h->d_stage_out = nullptr; h->stage_out_bytes = 0;
-    HIP_TRY(hipMalloc(&h->d_stage_out, out_bytes));
-    h->stage_out_bytes = out_bytes;
-  }
-  return PFB_OK;
-}
-
-// Host buffers (pageable or page-locked): chunks staged through one device buffer pair on the handle's stream, so each
-// chunk's copy-in, transform, carry update and copy-out are ordered behind the previous chunk's.  Chunks are sized
-// so that neither side of the staging exceeds 64 MiB (a hop of 1 makes nfft outputs per input sample).
-int stft_process_host_steps(pfb_stft_handle* h, const void* iq, uint64_t n, void* out) {
-  const uint64_t frame_bytes = (uint64_t)h->nfft * h->out_elem, budget = (uint64_t)64 << 20;
-  uint64_t chunk = std::min<uint64_t>((uint64_t)1 << 24, budget / h->bps);
-  chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, budget / frame_bytes) * (uint64_t)h->H);
-  const uint64_t max_frames = (h->L - 1 + chunk) / (uint64_t)h->H + 1;
-  int rc = stft_ensure_stage(h, (size_t)std::min<uint64_t>(chunk, n ? n : 1) * h->bps,
-                             (size_t)std::min<uint64_t>(max_frames, stft_frames_for(h, n) + 1) * frame_bytes);
-  if (rc != PFB_OK) return rc;
-  const char* src = static_cast<const char*>(iq);
-  char* dst = static_cast<char*>(out);
-  uint64_t done = 0, frames_done = 0;
-  while (done < n) {
-    const uint64_t m = std::min<uint64_t>(chunk, n - done);
-    const uint64_t f = stft_frames_for(h, m);
-    HIP_TRY(hipMemcpyAsync(h->d_stage_in, src + done * h->bps, (size_t)m * h->bps, hipMemcpyHostToDevice, h->stream));
-    rc = stft_enqueue(h, h->d_stage_in, m, h->d_stage_out, f);
-    if (rc != PFB_OK) return rc;
-    if (f > 0)
-      HIP_TRY(hipMemcpyAsync(dst + frames_done * frame_bytes, h->d_stage_out, (size_t)(f * frame_bytes),
-                             hipMemcpyDeviceToHost, h->stream));
-    done += m;
-    frames_done += f;
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return PFB_OK;
-}
-
-int stft_process_host(pfb_stft_handle* h, const void* iq, uint64_t n, void* out) {
-  const int rc = stft_process_host_steps(h, iq, n, out);
-  if (rc != PFB_OK) {  // nothing may still touch the caller's buffers once it has the status
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-  }
-  return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pfb_stft_create(const pfb_stft_config* cfg, pfb_stft_handle** out) {
-  return pfb::abi_guard([&]() -> int {
-  if (!cfg || !out) return PFB_ERR_BAD_ARG;
-  *out = nullptr;
-  if (cfg->struct_size != sizeof(pfb_stft_config) || !cfg->window) return PFB_ERR_BAD_ARG;
-  const uint32_t L = cfg->window_length;
-  const uint32_t H = cfg->hop ? cfg->hop : L;
-  const uint32_t nfft = cfg->fft_length ? cfg->fft_length : L;
-  if (L < 1 || H > L || nfft < L) return PFB_ERR_BAD_ARG;
-  if (cfg->output > PFB_STFT_DB || cfg->freq_order > PFB_STFT_TWOSIDED || cfg->kernel > PFB_STFT_KERNEL_FUSED)
-    return PFB_ERR_BAD_ARG;
-  // both are applied in float32: they must survive the conversion (no overflow to inf, no underflow to 0)
-  const auto in_float = [](double v) { return v == 0 || (v >= (double)FLT_MIN && v <= (double)FLT_MAX); };
-  if (!std::isfinite(cfg->scale) || cfg->scale < 0 || !std::isfinite(cfg->db_floor) || cfg->db_floor < 0 ||
-      !in_float(cfg->scale) || !in_float(cfg->db_floor))
-    return PFB_ERR_BAD_ARG;
-  if (nfft > 4096) return PFB_ERR_UNSUPPORTED;  // as pfb_create for M > 4096
-  if (cfg->sample_format > PFB_FMT_CF32) return PFB_ERR_BAD_FORMAT;
-  int bw = (int)cfg->bit_width;
-  if (cfg->sample_format == PFB_FMT_INT8_IQ && (bw < 1 || bw > 8)) return PFB_ERR_BAD_FORMAT;
-  if (cfg->sample_format == PFB_FMT_INT16_IQ && (bw < 1 || bw > 16)) return PFB_ERR_BAD_FORMAT;
-  if (cfg->sample_format == PFB_FMT_CF32) bw = 1;  // scale 1
-  const pfb::StftKernelInfo* fused = pfb::find_stft_fused((int)nfft, (int)cfg->sample_format);
-  if (cfg->kernel == PFB_STFT_KERNEL_FUSED && !fused) return PFB_ERR_UNSUPPORTED;
-
-  int ndev = 0;
-  const hipError_t ce = hipGetDeviceCount(&ndev);
-  if (ce != hipSuccess || ndev <= 0) {
-    g_detail = std::string("hipGetDeviceCount: ") + (ce == hipSuccess ? "0 devices" : hipGetErrorString(ce));
-    (void)hipGetLastError();
-    return PFB_ERR_NO_DEVICE;
-  }
-  int dev = cfg->device_id;
-  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-  if (dev >= ndev) return PFB_ERR_BAD_ARG;
-
-  pfb_stft_handle* h = new (std::nothrow) pfb_stft_handle();
-  if (!h) return PFB_ERR_NO_MEMORY;
-  h->L = (int)L; h->H = (int)H; h->nfft = (int)nfft;
-  h->fmt = (int)cfg->sample_format; h->bit_width = bw;
-  h->output = (int)cfg->output; h->order = (int)cfg->freq_order; h->kernel_opt = (int)cfg->kernel;
-  h->scale = cfg->scale == 0 ? 1.f : (float)cfg->scale;
-  h->db_floor = (float)cfg->db_floor;
-  h->device = dev;
-  h->bps = pfb::bytes_per_sample(h->fmt);
-  h->out_elem = cfg->output == PFB_STFT_COMPLEX ? 8 : 4;
-  h->kern = (cfg->kernel != PFB_STFT_KERNEL_GENERIC && fused) ? fused : pfb::stft_generic_kernel();
-
-  DeviceGuard g(dev);
-  std::vector<float> win(L);
-  const float scale = std::ldexp(1.0f, -(bw - 1));  // power of two: w*scale is exact
-  for (uint32_t i = 0; i < L; ++i) win[i] = cfg->window[i] * scale;
-  std::vector<float2> tw(nfft);
-  const double two_pi = 6.283185307179586476925286766559;
-  for (uint32_t m = 0; m < nfft; ++m) {
-    tw[m].x = (float)std::cos(two_pi * (double)m / (double)nfft);
-    tw[m].y = (float)std::sin(two_pi * (double)m / (double)nfft);
-  }
-  const size_t carry_bytes = (size_t)L * h->bps;
-  hipError_t e = hipMalloc((void**)&h->d_win, L * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_tw, nfft * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(&h->d_carry[0], carry_bytes);
-  if (e == hipSuccess) e = hipMalloc(&h->d_carry[1], carry_bytes);
-  if (e == hipSuccess) e = hipMemcpy(h->d_win, win.data(), L * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->d_tw, tw.data(), nfft * sizeof(float2), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(h->d_carry[0], 0, carry_bytes);
-  if (e == hipSuccess) e = hipMemset(h->d_carry[1], 0, carry_bytes);
-  if (e != hipSuccess) {
-    const int rc = hip_fail(e, "pfb_stft_create allocation");
-    free_stft(h);
-    return rc;
-  }
-  *out = h;
-  return PFB_OK;
-  });
-}
-
-int pfb_stft_destroy(pfb_stft_handle* h) {
-  return pfb::abi_guard([&]() -> int {
-  if (!h) return PFB_ERR_BAD_ARG;
-  free_stft(h);
-  return PFB_OK;
-  });
-}
-
-int pfb_stft_reset(pfb_stft_handle* h) {
-  return pfb::abi_guard([&]() -> int {
-  if (!h) return PFB_ERR_BAD_ARG;
-  h->carry_len = 0;  // the carried samples are never read again; nothing on the device to clear
-  return PFB_OK;
-  });
-}
-
-int pfb_stft_set_stream(pfb_stft_handle* h, void* hip_stream) {
-  return pfb::abi_guard([&]() -> int {
-  if (!h) return PFB_ERR_BAD_ARG;
-  hipStream_t next = static_cast<hipStream_t>(hip_stream);
-  if (next != h->stream) {  // the carry update the old stream still has queued comes first
-    DeviceGuard g(h->device);
-    if (!h->ev_switch) HIP_TRY(hipEventCreateWithFlags(&h->ev_switch, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->ev_switch, h->stream));
-    HIP_TRY(hipStreamWaitEvent(next, h->ev_switch, 0));
-    h->stream = next;
-  }
-  return PFB_OK;
-  });
-}
-
-int pfb_stft_frames_for(const pfb_stft_handle* h, uint64_t n, uint64_t* frames_out) {
-  if (!h || !frames_out) return PFB_ERR_BAD_ARG;
-  *frames_out = stft_frames_for(h, n);
-  return PFB_OK;
-}
-
-int pfb_stft_process_async(pfb_stft_handle* h, const void* d_iq, uint64_t n, void* d_out, uint64_t cap,
-                           uint64_t* frames_out) {
-  return pfb::abi_guard([&]() -> int {
-  if (!h || (n > 0 && !d_iq)) return PFB_ERR_BAD_ARG;
-  const uint64_t f = stft_frames_for(h, n);
-  if (frames_out) *frames_out = f;
-  if (f > cap) return PFB_ERR_CAPACITY;
-  if (f > 0 && !d_out) return PFB_ERR_BAD_ARG;
-  if (reinterpret_cast<uintptr_t>(d_iq) % h->bps || reinterpret_cast<uintptr_t>(d_out) % h->out_elem) return PFB_ERR_BAD_ARG;
-  DeviceGuard g(h->device);
-  return stft_enqueue(h, d_iq, n, d_out, f);
-  });
-}
-
-int pfb_stft_sync(pfb_stft_handle* h) {
-  return pfb::abi_guard([&]() -> int {
-  if (!h) return PFB_ERR_BAD_ARG;
-  DeviceGuard g(h->device);
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return PFB_OK;
-  });
-}
-
-int pfb_stft_process(pfb_stft_handle* h, const void* iq, uint64_t n, void* out, uint64_t cap, uint64_t* frames_out,
-                     uint32_t mem) {
-  return pfb::abi_guard([&]() -> int {
-  if (!h || (n > 0 && !iq) || mem > PFB_MEM_DEVICE) return PFB_ERR_BAD_ARG;
-  const uint64_t f = stft_frames_for(h, n);
-  if (frames_out) *frames_out = f;
-  if (f > cap) return PFB_ERR_CAPACITY;
-  if (f > 0 && !out) return PFB_ERR_BAD_ARG;
-  DeviceGuard g(h->device);
-  if (mem == PFB_MEM_DEVICE) {
-    if (reinterpret_cast<uintptr_t>(iq) % h->bps || reinterpret_cast<uintptr_t>(out) % h->out_elem) return PFB_ERR_BAD_ARG;
-    const int rc = stft_enqueue(h, iq, n, out, f);
-    if (rc != PFB_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PFB_OK;
-  }
-  return stft_process_host(h, iq, n, out);
-  });
-}
-
-int pfb_stft_process_iq_file(pfb_stft_handle* h, const char* path, void* out, uint64_t cap, uint64_t* frames_out,
-                             pfb_iq_info* info_out) {
-  return pfb::abi_guard([&]() -> int {
-  if (!h || !path) return PFB_ERR_BAD_ARG;
-  int fd = -1;
-  pfb_iq_info info{};
-  int rc = open_record(nullptr, path, &fd, &info);
-  if (rc == PFB_OK && ((int)info.sample_format != h->fmt || (int)info.packet.bitWidth != h->bit_width)) {
-    ::close(fd);
-    rc = PFB_ERR_BAD_FORMAT;  // the handle's scale / unpack would not match this record
-  }
-  if (info_out) *info_out = info;
-  if (rc != PFB_OK) return rc;
-  const uint64_t n = info.packet.numSamples;
-  const uint64_t need = stft_frames_for(h, n);
-  if (frames_out) *frames_out = need;
-  if (need > cap) { ::close(fd); return PFB_ERR_CAPACITY; }
-  if (need > 0 && !out) { ::close(fd); return PFB_ERR_BAD_ARG; }
-  // the payload in page-locked chunks: the record is never held in memory
-  const uint64_t chunk = (uint64_t)1 << 22;
-  const size_t chunk_bytes = (size_t)std::min<uint64_t>(chunk, n ? n : 1) * h->bps;
-  char* buf = static_cast<char*>(pfb_host_alloc(chunk_bytes));
-  if (!buf) { ::close(fd); return PFB_ERR_NO_MEMORY; }
-  const unsigned hw = std::thread::hardware_concurrency();
-  const int readers = (int)std::max(1u, std::min(4u, hw ? hw / 2 : 1u));
-  uint64_t done = 0, frames_done = 0;
-  while (done < n && rc == PFB_OK) {
-    const uint64_t m = std::min<uint64_t>(chunk, n - done);
-    if (!pread_parallel(fd, buf, (size_t)m * h->bps, (off_t)info.header_bytes + (off_t)(done * h->bps), readers)) {
-      rc = PFB_ERR_BAD_FORMAT;
-      break;
-    }
-    const uint64_t f = stft_frames_for(h, m);
-    DeviceGuard g(h->device);
-    rc = stft_process_host(h, buf, m, static_cast<char*>(out) + frames_done * (uint64_t)h->nfft * h->out_elem);
-    done += m;
-    frames_done += f;
-  }
-  pfb_host_free(buf);
-  ::close(fd);
-  if (frames_out) *frames_out = frames_done;
-  return rc;
-  });
-}
-
-int pfb_stft_axes(uint32_t nfft, uint32_t L, uint32_t H, double fs, uint32_t order, uint64_t first_frame,
-                  uint64_t frames, double* f_out, double* t_out) {
-  if (nfft < 1 || L < 1 || H < 1 || H > L || L > nfft || order > PFB_STFT_TWOSIDED || !std::isfinite(fs) || fs <= 0)
-    return PFB_ERR_BAD_ARG;
-  if (f_out) {
-    // k_r = r - shift' with shift' = nfft/2 - 1 (even, stft 'centered'), (nfft-1)/2 (odd), 0 (twosided)
-    const long long lo = order == PFB_STFT_TWOSIDED ? 0 : (nfft % 2 == 0 ? (long long)nfft / 2 - 1 : ((long long)nfft - 1) / 2);
-    for (uint32_t r = 0; r < nfft; ++r) f_out[r] = (double)((long long)r - lo) * fs / (double)nfft;
-  }
-  if (t_out)
-    for (uint64_t m = 0; m < frames; ++m) t_out[m] = ((double)(first_frame + m) * (double)H + (double)L / 2.0) / fs;
-  return PFB_OK;
-}
-
-const char* pfb_stft_last_kernel(const pfb_stft_handle* h) { return h ? h->last_kernel : ""; }
-
-int pfb_stft_set_experiment(pfb_stft_handle* h, int experiment) {
-  if (!h || experiment < 0 || experiment > 1) return PFB_ERR_BAD_ARG;
-  if (experiment == 1 && !h->kern->launch_loadstore) return PFB_ERR_UNSUPPORTED;
-  h->experiment = experiment;
-  return PFB_OK;
 }
 
 }  // extern "C"

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "pfb_common.h"  // abi_guard, launch_transpose_slab (pfb_kernels.hip)
+#include "pfb_host.h"    // resolve_device, DeviceGuard
 
 namespace {
 
@@ -1950,23 +1951,6 @@ int tile_words_for(long long samples, int M) {
   return tw;
 }
 
-// RAII: select the device for the call, restore on exit
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  int enter(int32_t device_id, int ndev) {
-    (void)hipGetDevice(&prev);
-    if (device_id >= 0 && device_id != prev) {
-      if (device_id >= ndev || hipSetDevice(device_id) != hipSuccess) return PFB_ERR_BAD_ARG;
-      switched = true;
-    }
-    return PFB_OK;
-  }
-  ~DeviceScope() {
-    if (switched && prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 }  // namespace
 
 static int pdw_extract_impl(const void* y_in, uint64_t frames, uint32_t M, uint32_t decimation, double fs_in,
@@ -1975,16 +1959,11 @@ static int pdw_extract_impl(const void* y_in, uint64_t frames, uint32_t M, uint3
                             int32_t device_id, void* hip_stream) {
   if (!y_in || !count || M < 1 || decimation < 1 || frames < 1 || mem > PFB_MEM_DEVICE || (capacity && !out))
     return PFB_ERR_BAD_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return PFB_ERR_NO_DEVICE;
-  }
-  DeviceScope scope;
-  if (scope.enter(device_id, ndev) != PFB_OK) return PFB_ERR_BAD_ARG;
   int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= kMaxDevices) return PFB_ERR_BAD_ARG;
+  const int drc = pfb::resolve_device(device_id, &dev);
+  if (drc != PFB_OK) return drc;
+  if (dev >= kMaxDevices) return PFB_ERR_BAD_ARG;
+  pfb::DeviceGuard guard(dev);  // the call runs on that device, the caller's comes back afterwards
   std::lock_guard<std::mutex> lock(g_ws_mutex);  // one extraction per process at a time shares the scratch
   Arena& ws = g_ws[dev][0];
   Arena& ws2 = g_ws[dev][1];
@@ -2349,16 +2328,11 @@ static int pdw_extract_raw_impl(const void* iq, uint64_t num_samples, uint32_t s
     return PFB_ERR_BAD_ARG;
   if (sample_format != PFB_FMT_CF32 && (bit_width < 1 || bit_width > 16)) return PFB_ERR_BAD_ARG;
   if (!(trailing_threshold_db <= snr_threshold_db)) return PFB_ERR_BAD_ARG;  // the masks assume lead >= trail
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return PFB_ERR_NO_DEVICE;
-  }
-  DeviceScope scope;
-  if (scope.enter(device_id, ndev) != PFB_OK) return PFB_ERR_BAD_ARG;
   int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= kMaxDevices) return PFB_ERR_BAD_ARG;
+  const int drc = pfb::resolve_device(device_id, &dev);
+  if (drc != PFB_OK) return drc;
+  if (dev >= kMaxDevices) return PFB_ERR_BAD_ARG;
+  pfb::DeviceGuard guard(dev);  // the call runs on that device, the caller's comes back afterwards
   std::lock_guard<std::mutex> lock(g_ws_mutex);
   Arena& ws = g_ws[dev][0];
   Arena& ws2 = g_ws[dev][1];

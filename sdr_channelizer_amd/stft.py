@@ -18,9 +18,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._handle import Handle, is_torch
 
 _FMT = {"int8": L.PFB_FMT_INT8_IQ, "int16": L.PFB_FMT_INT16_IQ, "cf32": L.PFB_FMT_CF32}
-_NP_DTYPE = {L.PFB_FMT_INT8_IQ: np.int8, L.PFB_FMT_INT16_IQ: np.int16, L.PFB_FMT_CF32: np.float32}
 _OUTPUT = {"complex": L.PFB_STFT_COMPLEX, "power": L.PFB_STFT_POWER, "db": L.PFB_STFT_DB}
 _ORDER = {"centered": L.PFB_STFT_CENTERED, "twosided": L.PFB_STFT_TWOSIDED}
 _KERNEL = {"auto": L.PFB_STFT_KERNEL_AUTO, "generic": L.PFB_STFT_KERNEL_GENERIC, "fused": L.PFB_STFT_KERNEL_FUSED}
@@ -39,17 +39,19 @@ def stft_axes(fft_length: int, window_length: int, hop: int, fs: float, frequenc
 
 
 def _format_of(x) -> str:
-    if type(x).__module__.startswith("torch"):
+    if is_torch(x):
         import torch
         return {torch.int8: "int8", torch.int16: "int16"}.get(x.dtype, "cf32")
     dt = np.asarray(x).dtype
     return {np.dtype(np.int8): "int8", np.dtype(np.int16): "int16"}.get(dt, "cf32")
 
 
-class Stft:
+class Stft(Handle):
     """Stateful STFT of an I/Q stream: frame m covers samples [m H, m H + L) of everything fed since creation or
     ``reset()``; each call returns the frames it completes, frame-major, shape (frames, nfft) -- row r of a frame is
     bin k_r ('centered' or 'twosided' order).  numpy in -> numpy out, CUDA tensor in -> CUDA tensor out."""
+
+    _kind, _destroy, _get_device = "STFT", "pfb_stft_destroy", "pfb_stft_get_device"
 
     def __init__(self, window, *, hop: int | None = None, overlap_length: int | None = None,
                  fft_length: int | None = None, sample_format: str = "cf32", bit_width: int = 12,
@@ -74,28 +76,8 @@ class Stft:
                               self.bit_width, _OUTPUT[output], _ORDER[frequency_range], float(scale), float(db_floor),
                               _KERNEL[kernel], int(device))
         L.check(lib.pfb_stft_create(C.byref(cfg), C.byref(self._h)), "pfb_stft_create")
-        self._lib = lib
+        self._created(lib)
         self.frames_done = 0  # global index of the next frame (the time axis of later calls)
-
-    # -- lifecycle ---------------------------------------------------------------
-    def release(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.pfb_stft_destroy(self._h)
-            self._h = C.c_void_p()
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
 
     def reset(self) -> None:
         L.check(self._lib.pfb_stft_reset(self._h), "pfb_stft_reset")
@@ -120,45 +102,13 @@ class Stft:
         return stft_axes(self.fft_length, self.window_length, self.hop, fs, self.frequency_range, first_frame, frames)
 
     # -- samples -----------------------------------------------------------------
-    def _host_samples(self, iq) -> tuple[np.ndarray, int]:
-        want = _NP_DTYPE[self.fmt]
-        a = np.asarray(iq)
-        if self.fmt == L.PFB_FMT_CF32 and np.iscomplexobj(a):
-            a = np.ascontiguousarray(a, dtype=np.complex64).view(np.float32)
-        if a.dtype != want:
-            raise TypeError(f"expected {np.dtype(want)} I/Q for this STFT, got {a.dtype}")
-        a = np.ascontiguousarray(a).reshape(-1)
-        if a.size % 2:
-            raise ValueError("interleaved I,Q needs an even element count")
-        return a, a.size // 2
-
-    def _device_samples(self, iq) -> int:
-        import torch
-        want = {L.PFB_FMT_INT8_IQ: (torch.int8,), L.PFB_FMT_INT16_IQ: (torch.int16,),
-                L.PFB_FMT_CF32: (torch.float32, torch.complex64)}[self.fmt]
-        if iq.dtype not in want:
-            raise TypeError(f"expected {want[0]} I/Q for this STFT, got {iq.dtype}")
-        if not iq.is_contiguous():
-            raise ValueError("device I/Q must be contiguous")
-        if iq.is_complex():
-            return iq.numel()
-        if iq.numel() % 2:
-            raise ValueError("interleaved I,Q needs an even element count")
-        return iq.numel() // 2
-
     def __call__(self, iq, out=None, sync: bool = True):
         """Transform one buffer; returns the (frames, nfft) frames it completes."""
-        nfft = self.fft_length
-        if type(iq).__module__.startswith("torch") and iq.is_cuda:
-            import torch
+        complex_out = self.output == "complex"
+        if is_torch(iq) and iq.is_cuda:
             n = self._device_samples(iq)
             F = self.frames_for(n)
-            odt = torch.complex64 if self.output == "complex" else torch.float32
-            if out is None:
-                out = torch.empty((F, nfft), dtype=odt, device=iq.device)
-            elif (not out.is_cuda or out.device != iq.device or out.numel() < F * nfft or out.dtype != odt
-                  or not out.is_contiguous()):
-                raise ValueError(f"out must be a contiguous {odt} tensor on {iq.device} with room for frames*nfft values")
+            out = self._output(out, (F, self.fft_length), complex_out, iq.device)
             f = C.c_uint64()
             if sync:
                 L.check(self._lib.pfb_stft_process(self._h, C.c_void_p(iq.data_ptr()), n, C.c_void_p(out.data_ptr()),
@@ -168,16 +118,10 @@ class Stft:
                                                          C.c_void_p(out.data_ptr()), F, C.byref(f)),
                         "pfb_stft_process_async")
             self.frames_done += F
-            return out.reshape(-1)[: F * nfft].reshape(F, nfft)
+            return out
         a, n = self._host_samples(iq)
         F = self.frames_for(n)
-        odt = np.complex64 if self.output == "complex" else np.float32
-        if out is None:
-            res = np.empty((F, nfft), dtype=odt)
-        else:
-            if not isinstance(out, np.ndarray) or out.dtype != odt or out.size < F * nfft or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous numpy array of the output dtype with room for frames*nfft")
-            res = out.reshape(-1)[: F * nfft].reshape(F, nfft)
+        res = self._output(out, (F, self.fft_length), complex_out)
         f = C.c_uint64()
         L.check(self._lib.pfb_stft_process(self._h, C.c_void_p(a.ctypes.data), n, C.c_void_p(res.ctypes.data), F,
                                            C.byref(f), L.PFB_MEM_HOST), "pfb_stft_process")
@@ -193,7 +137,7 @@ class Stft:
         if reset:
             self.reset()
         F = self.frames_for(int(info.packet.numSamples))
-        res = np.empty((F, self.fft_length), dtype=np.complex64 if self.output == "complex" else np.float32)
+        res = self._output(None, (F, self.fft_length), self.output == "complex")
         f = C.c_uint64()
         got = L.PfbIqInfo()
         L.check(self._lib.pfb_stft_process_iq_file(self._h, path.encode(), C.c_void_p(res.ctypes.data), F, C.byref(f),

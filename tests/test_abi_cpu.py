@@ -63,11 +63,15 @@ def test_nothing_thrown_crosses_the_c_abi():
     # and every extern "C" definition in the product sources that builds C++ objects sits under the guard
     csrc = os.path.join(ROOT, "sdr_channelizer_amd", "csrc")
     api = open(os.path.join(csrc, "pfb_api.cpp")).read()
-    for name in ("pfb_create", "pfb_process", "pfb_process_async", "pfb_process_iq_file", "pfb_pdw_from_iq_file",
-                 "pfb_pdw_raw_from_iq_file", "pfb_prime", "pfb_set_option", "pfb_get_kernel_times", "pfb_shard_attach",
-                 "pfb_process_shard_async"):
-        body = api[api.index(f"\nint {name}("):]
-        assert "abi_guard" in body[: body.index("\n}\n")].split("{", 1)[1][:80], name
+    stft_api = open(os.path.join(csrc, "pfb_stft_api.cpp")).read()
+    for src, names in ((api, ("pfb_create", "pfb_process", "pfb_process_async", "pfb_process_iq_file",
+                              "pfb_pdw_from_iq_file", "pfb_pdw_raw_from_iq_file", "pfb_prime", "pfb_set_option",
+                              "pfb_get_kernel_times", "pfb_shard_attach", "pfb_process_shard_async")),
+                       (stft_api, ("pfb_stft_create", "pfb_stft_process", "pfb_stft_process_async",
+                                   "pfb_stft_process_iq_file", "pfb_stft_set_stream"))):
+        for name in names:
+            body = src[src.index(f"\nint {name}("):]
+            assert "abi_guard" in body[: body.index("\n}\n")].split("{", 1)[1][:80], name
     pdw = open(os.path.join(csrc, "pfb_pdw.hip")).read()
     for name in ("pfb_pdw_extract", "pfb_pdw_extract_raw", "pfb_pdw_release_workspace"):
         body = pdw[pdw.index(f'extern "C" int {name}('):]

@@ -870,3 +870,15 @@ def test_non_finite_samples_stay_inside_their_window(M, P):
     assert not np.isfinite(got[hit]).any()
     assert np.array_equal(got[~hit], clean[~hit])
     assert np.array_equal(np.isfinite(gen).all(axis=1), finite)
+
+
+def test_measure_rejects_a_device_past_the_last():
+    """The copy yardsticks resolve device_id as the handles do: an ordinal past the last device is PFB_ERR_BAD_ARG,
+    not a measurement of whichever device is current."""
+    import ctypes as C
+    lib = L.load()
+    r = C.c_double()
+    ndev = lib.pfb_device_count()
+    assert lib.pfb_measure_stream_copy(ndev, 1 << 20, 1, C.byref(r)) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_measure_mix_copy(ndev, 1 << 20, 2, 2, 1, C.byref(r)) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_measure_stream_copy(0, 1 << 20, 1, C.byref(r)) == L.PFB_OK and r.value > 0

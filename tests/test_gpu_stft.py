@@ -248,6 +248,70 @@ def test_spectrogram_my_iq_record(tmp_path):
         assert e.value.status == L.PFB_ERR_BAD_FORMAT
 
 
+def test_record_longer_than_two_reader_chunks(tmp_path):
+    """A record of more than two of the record reader's 2^24-sample chunks (both page-locked buffers reused, the
+    prefetch running across chunk ends) gives the bits of one in-memory host call; a truncated copy is refused."""
+    n = (1 << 25) + 12345
+    iq = np.random.default_rng(29).integers(-128, 128, size=(n, 2), dtype=np.int8)
+    path = str(tmp_path / "long.iq")
+    iqfile.write_iq(path, iq, 56e6, 1e9, 8)
+    with Stft(np.hamming(256), sample_format="int8", bit_width=8, output="power") as st:
+        y, info = st.process_iq_file(path)
+        st.reset()
+        ref = st(iq)
+        assert int(info.packet.numSamples) == n and y.shape == (n // 256, 256)
+        assert np.array_equal(y, ref)
+        short = str(tmp_path / "short.iq")
+        with open(path, "rb") as src, open(short, "wb") as dst:
+            dst.write(src.read(os.path.getsize(path) - 4096))
+        with pytest.raises(L.PfbError) as e:
+            st.process_iq_file(short)
+        assert e.value.status == L.PFB_ERR_BAD_FORMAT
+
+
+def test_page_locked_host_buffers_and_pipelined_staging(torch):
+    """L = 256 at hop 1 fills a 64 MiB output staging buffer every 65536 samples: four staging chunks in flight over
+    three streams give the bits of one device-resident call, from pageable and from page-locked buffers."""
+    from sdr_channelizer_amd import pinned_empty
+    n = 3 * 65536 + 4321
+    raw = raw_input("int16", 12, n, 31)
+    raw_p = pinned_empty(raw.shape, raw.dtype)
+    raw_p[:] = raw
+    with Stft(np.hamming(256), hop=1, sample_format="int16", output="power") as st:
+        ref = run_device(torch, st, raw)
+        assert ref.shape == (n - 255, 256)
+        st.reset()
+        out_p = pinned_empty(ref.shape, ref.dtype)
+        assert np.array_equal(st(raw_p, out=out_p), ref)
+        st.reset()
+        assert np.array_equal(st(raw), ref)
+
+
+def test_handle_reports_its_device(torch):
+    lib = L.load()
+    for device in (0, -1):
+        with Stft(np.hamming(256), device=device) as st:
+            dev = C.c_int(-1)
+            assert lib.pfb_stft_get_device(st._h, C.byref(dev)) == L.PFB_OK
+            assert dev.value == st.device_index == torch.cuda.current_device() == 0
+    assert lib.pfb_stft_get_device(None, C.byref(dev)) == L.PFB_ERR_BAD_ARG
+
+
+def test_device_input_is_checked_before_the_library_sees_it(torch):
+    """The channelizer's rules: a numpy out for a CUDA input, or an interleaved tensor whose last dimension is not 2,
+    is a ValueError"""
+    raw = raw_input("int16", 12, 256 * 4, 5)
+    x = torch.from_numpy(raw).cuda()
+    with Stft(np.hamming(256), sample_format="int16", output="power") as st:
+        with pytest.raises(ValueError):
+            st(x, out=np.empty((4, 256), np.float32))
+        with pytest.raises(ValueError):
+            st(x.reshape(-1, 4))
+        y = st(x.reshape(-1, 2)).cpu().numpy()
+        st.reset()
+        assert np.array_equal(y, st(raw))
+
+
 def test_generate_pulsed_iq_psd_db():
     """generate_pulsed_iq.m:105, spectrogram(iq,1024,0,1024,Fs,'centered','yaxis'): a 1024-point Hamming STFT, PSD
     scale 1/(fs sum w^2), plotted in dB (eps added)."""
