@@ -48,6 +48,18 @@ int pfb_measure_mix_copy(int device_id, uint64_t bytes_in, uint32_t write_ratio,
  * on the generic kernel.  Registered nowhere: pfb_stft_last_kernel names it pfb_stft_loadstore<...>. */
 int pfb_stft_set_experiment(pfb_stft_handle* h, int experiment);
 
+/* The fused-kernel table, row by row in lookup order (host only, no device needed): what the tests walk, so that a
+ * registered plan cannot go untested.  Rows of one (M, P, D, sample_format) are that shape's variants 0, 1, ... */
+typedef struct {
+  int M, P, D, sample_format;
+  int variant;            /* index among the rows of this (M, P, D, format): what PFB_OPT_VARIANT takes */
+  const char* name;       /* what pfb_last_kernel reports (static storage) */
+  int default_schedule, magnitude_schedule, chunk_frames;
+  int channel_major_ok;   /* 0: a channel-major handle on this plan goes by slabs + transpose */
+} pfb_fast_plan_desc;
+int pfb_fast_plan_count(void);
+int pfb_fast_plan_info(int index, pfb_fast_plan_desc* out); /* PFB_ERR_BAD_ARG past the end or for NULL */
+
 /* Diagnostic: throws a C++ exception of the given kind (0 = std::bad_alloc, 1 = std::runtime_error,
  * 2 = a non-std type) INSIDE the guard every entry point runs under and returns what the guard
  * returns (PFB_ERR_NO_MEMORY / PFB_ERR_INTERNAL): proof that nothing thrown crosses the C ABI. */

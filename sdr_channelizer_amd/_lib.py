@@ -71,6 +71,14 @@ class PfbPdw(C.Structure):
                 ("sat", C.c_int32), ("bin", C.c_int32), ("mag", C.c_double)]
 
 
+class PfbFastPlanDesc(C.Structure):
+    _fields_ = [
+        ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
+        ("name", C.c_char_p), ("default_schedule", C.c_int), ("magnitude_schedule", C.c_int),
+        ("chunk_frames", C.c_int), ("channel_major_ok", C.c_int),
+    ]
+
+
 PFB_PDW_MATLAB_QUIRKS = 1        # phase(toa:jj) linear-indexes column 1 (create_pdws_channelized.m:114)
 PFB_PDW_CHANNEL_MAJOR = 2
 PFB_PDW_BINFREQ_UNSHIFTED = 4    # binFreqs(bin) from the FFT-ordered list (:42/:80 if centerFrequencies is unshifted; unpinned)
@@ -106,7 +114,8 @@ EXPORTS = (
     "pfb_stft_last_kernel", "pfb_stft_get_device",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
-DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment")
+DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
+               "pfb_fast_plan_count", "pfb_fast_plan_info")
 
 _lib = None
 
@@ -213,6 +222,8 @@ def load() -> C.CDLL:
     lib.pfb_stft_last_kernel.restype = C.c_char_p
     lib.pfb_stft_get_device.argtypes = [vp, C.POINTER(C.c_int)]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
+    lib.pfb_fast_plan_count.argtypes = []
+    lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
     for name in EXPORTS + DEV_EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     _lib = lib
@@ -222,3 +233,14 @@ def load() -> C.CDLL:
 def check(status: int, where: str) -> None:
     if status != PFB_OK:
         raise PfbError(status, where)
+
+
+def fast_plans() -> list[PfbFastPlanDesc]:
+    """Every row of the fused-kernel table, in lookup order (pfb_fast_plan_info; host only)."""
+    lib = load()
+    rows = []
+    for i in range(lib.pfb_fast_plan_count()):
+        d = PfbFastPlanDesc()
+        check(lib.pfb_fast_plan_info(i, C.byref(d)), "pfb_fast_plan_info")
+        rows.append(d)
+    return rows

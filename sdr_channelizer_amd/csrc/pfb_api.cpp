@@ -169,11 +169,12 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
     ++h->ev_used;  // only a pair whose first event was recorded counts as used
   }
   // Channel-major output of a fused shape is written by the kernel itself (its transposed-tile or plain
-  // channel-major instantiation).  The team plans (M = 1024, 560) have none -- their chunks of 4 frames would be
-  // 32-byte runs -- and go by slabs instead: the frame-major kernel fills a scratch slab, a transpose kernel
-  // moves it into place (M = 1024: 2x the 8-wave plan's fused channel-major stores).  A slab must be long enough
-  // to fill the chip with runs, so it does not fit the memory-side cache; PFB_OPT_SCHEDULE 9 forces the slabs on
-  // any shape, PFB_OPT_SLAB_FRAMES sets their length.
+  // channel-major instantiation) where the plan has one (channel_major_ok, kChannelMajorOk in pfb_fast.hpp).  The
+  // 16-wave plans and the three-pass plans on chunks of 4 or 2 frames -- the defaults of M = 1024, 560, 500 and 250,
+  // whose fused stores would be 32- or 16-byte runs per channel -- have none and go by slabs instead: the frame-major
+  // kernel fills a scratch slab, a transpose kernel moves it into place (1.5-5x faster than the fused stores on those
+  // plans, profiles/r04_channel_major_routes.txt).  A slab must be long enough to fill the chip with runs, so it does
+  // not fit the memory-side cache; PFB_OPT_SCHEDULE 9 forces the slabs on any shape, PFB_OPT_SLAB_FRAMES sets their length.
   const bool cm = h->layout == PFB_LAYOUT_CHANNEL_MAJOR;
   const bool forced_fused = h->opt_schedule == 0 || h->opt_schedule == 2 || h->opt_schedule == 8;
   // (A fused route for the team plans -- the team kernel transposing its own tiles through an L2-resident scratch -- was

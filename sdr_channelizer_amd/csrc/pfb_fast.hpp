@@ -2326,8 +2326,11 @@ constexpr bool kMagStagedOk = K::NT == 64 && K::NP == 2 && !K::PINGPONG && K::M 
 template <class K>
 constexpr int kMagnitudeSchedule = kMagStagedOk<K> ? (K::FMT == PFB_FMT_CF32 ? 7 : 0) : -1;  // (cf32: pairs still win)
 
+// Plans with a fused channel-major instantiation.  The 16-wave plans and the three-pass plans on chunks of 4 or 2 frames
+// (32- / 16-byte runs per channel) have none: a channel-major handle on them goes by frame-major slabs + the transpose
+// kernel, 1.5-5x faster than their fused stores on every such plan measured (profiles/r04_channel_major_routes.txt)
 template <class K>
-constexpr bool kChannelMajorOk = K::NT < 1024 && !(K::NP == 3 && K::C == 4);  // (C = 4 team plans: 32-byte runs)
+constexpr bool kChannelMajorOk = K::NT < 1024 && !(K::NP == 3 && K::C <= 4);
 
 // MAGSEL: -1 = PFB_FLAG_MAGNITUDE is tested inside (channel-major and staged-magnitude instantiations), 0 / 1 = decided
 // at launch (the frame-major kernels: their store count per chunk is then path-independent, see run_impl)

@@ -12,6 +12,7 @@
 //                          (the dsp.Channelizer System-object state,
 //                          channelizer_example.m:50-56)
 //   pfb_stream_copy        1 read : 2 write streaming copy, the measured-HBM yardstick
+#include "pfb_channelizer_dev.h"
 #include "pfb_generic_fft.hpp"
 #include "pfb_table.h"
 
@@ -284,15 +285,49 @@ static const FastEntry kRows[] = {
 
 FastTablePart fast_table_m64() { return FastTablePart{kRows, (int)(sizeof(kRows) / sizeof(kRows[0]))}; }
 
-const FastKernelInfo* find_fast_kernel(int M, int P, int D, int fmt, int variant, bool channel_major) {
+// the four parts in lookup order: row `index` of the whole table, nullptr past its end
+static const FastEntry* fast_row(int index) {
   const FastTablePart parts[] = {fast_table_m64(), fast_table_mid(), fast_table_big(), fast_table_mixed()};
-  for (const FastTablePart& part : parts)
-    for (int i = 0; i < part.count; ++i) {
-      const FastEntry& e = part.rows[i];
-      if (e.M == M && e.P == P && e.D == D && e.fmt == fmt && (!channel_major || e.info.channel_major_ok) && variant-- == 0)
-        return &e.info;
-    }
+  if (index < 0) return nullptr;
+  for (const FastTablePart& part : parts) {
+    if (index < part.count) return &part.rows[index];
+    index -= part.count;
+  }
+  return nullptr;
+}
+
+const FastKernelInfo* find_fast_kernel(int M, int P, int D, int fmt, int variant, bool channel_major) {
+  for (int i = 0; const FastEntry* e = fast_row(i); ++i)
+    if (e->M == M && e->P == P && e->D == D && e->fmt == fmt && (!channel_major || e->info.channel_major_ok) && variant-- == 0)
+      return &e->info;
   return nullptr;
 }
 
 }  // namespace pfb
+
+// ---------------------------------------------------------------------------------
+// the table as the tests see it (pfb_channelizer_dev.h): host only, no device needed
+
+extern "C" int pfb_fast_plan_count(void) {
+  int n = 0;
+  while (pfb::fast_row(n)) ++n;
+  return n;
+}
+
+extern "C" int pfb_fast_plan_info(int index, pfb_fast_plan_desc* out) {
+  const pfb::FastEntry* e = pfb::fast_row(index);
+  if (!e || !out) return PFB_ERR_BAD_ARG;
+  int variant = 0;  // rows of the same shape in front of this one: what PFB_OPT_VARIANT takes to reach it
+  for (int i = 0; i < index; ++i) {
+    const pfb::FastEntry* f = pfb::fast_row(i);
+    variant += f->M == e->M && f->P == e->P && f->D == e->D && f->fmt == e->fmt;
+  }
+  out->M = e->M; out->P = e->P; out->D = e->D; out->sample_format = e->fmt;
+  out->variant = variant;
+  out->name = e->info.name;
+  out->default_schedule = e->info.default_schedule;
+  out->magnitude_schedule = e->info.magnitude_schedule;
+  out->chunk_frames = e->info.chunk_frames;
+  out->channel_major_ok = e->info.channel_major_ok ? 1 : 0;
+  return PFB_OK;
+}

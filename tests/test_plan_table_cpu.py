@@ -1,0 +1,108 @@
+"""The fused-kernel table as the library lists it (pfb_fast_plan_count / pfb_fast_plan_info, host only): every row is
+what its name says, the variants of a shape are numbered the way PFB_OPT_VARIANT counts them, every shape is fuzzed,
+and the channel-major route of every plan is the one DESIGN.md names.  No GPU needed."""
+import os
+import re
+
+import pytest
+
+from sdr_channelizer_amd import _lib as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FMT = {"int8": L.PFB_FMT_INT8_IQ, "int16": L.PFB_FMT_INT16_IQ, "cf32": L.PFB_FMT_CF32}
+NAME_RE = re.compile(r"pfb_fast<M(\d+),P(\d+),D(\d+),(int8|int16|cf32)(?:,(\w+))?>")
+# every value pfb_set_option(PFB_OPT_SCHEDULE) accepts except 9 (channel-major by slabs, a route rather than a schedule)
+SCHEDULES = (-1, 0, 2, 3, 4, 6, 7, 8, 11, 13)
+# the plans a channel-major handle runs by frame-major slabs + the transpose kernel (kChannelMajorOk in pfb_fast.hpp):
+# the 16-wave plans and the three-pass plans on chunks of 4 or 2 frames, whose fused stores would be 32- / 16-byte runs
+SLAB_PLANS = {
+    "pfb_fast<M1024,P16,D1024,int16>", "pfb_fast<M1024,P16,D1024,int16,16w>",
+    "pfb_fast<M1024,P16,D1024,cf32>", "pfb_fast<M1024,P16,D1024,cf32,16w>",
+    "pfb_fast<M560,P12,D560,int16>", "pfb_fast<M560,P12,D560,int16,4f>",
+    "pfb_fast<M560,P12,D560,int8>", "pfb_fast<M560,P12,D560,int8,4f>", "pfb_fast<M560,P12,D560,cf32>",
+    "pfb_fast<M250,P12,D250,int16>", "pfb_fast<M250,P12,D250,int16,lockstep>",
+    "pfb_fast<M500,P12,D500,int16>", "pfb_fast<M500,P12,D500,int16,lockstep>",
+}
+
+
+@pytest.fixture(scope="module")
+def plans():
+    return L.fast_plans()
+
+
+def shape_of(d):
+    return (d.M, d.P, d.D, d.sample_format)
+
+
+def test_table_size(plans):
+    shapes = {shape_of(d) for d in plans}
+    print(f"{len(plans)} rows, {len(shapes)} shapes")
+    assert len(plans) == 58 and len(shapes) == 46
+    with open(os.path.join(ROOT, "README.md")) as f:
+        assert "46 band-count / format combinations" in f.read()   # README's count of fused (M, P, D, format) shapes
+
+
+def test_info_rejects_bad_arguments():
+    lib = L.load()
+    d = L.PfbFastPlanDesc()
+    n = lib.pfb_fast_plan_count()
+    assert lib.pfb_fast_plan_info(n, L.C.byref(d)) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_fast_plan_info(-1, L.C.byref(d)) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_fast_plan_info(0, None) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_fast_plan_info(n - 1, L.C.byref(d)) == L.PFB_OK
+
+
+def test_names_parse_back_to_their_own_shape(plans):
+    names = [d.name.decode() for d in plans]
+    assert len(set(names)) == len(names), "two rows report the same pfb_last_kernel name"
+    for d, name in zip(plans, names):
+        m = NAME_RE.fullmatch(name)
+        assert m, name
+        assert (int(m[1]), int(m[2]), int(m[3]), FMT[m[4]]) == shape_of(d), name
+        # the default plan of a shape carries no suffix, the variants do
+        assert (m[5] is None) == (d.variant == 0), name
+
+
+def test_variants_count_rows_of_a_shape_in_table_order(plans):
+    seen = {}
+    for d in plans:
+        k = shape_of(d)
+        assert d.variant == seen.get(k, 0), d.name
+        seen[k] = d.variant + 1
+
+
+def test_schedules_and_chunks(plans):
+    for d in plans:
+        assert d.default_schedule in SCHEDULES and d.default_schedule >= 0, d.name
+        assert d.magnitude_schedule == -1 or d.magnitude_schedule in SCHEDULES[1:], d.name
+        assert d.chunk_frames >= 1 and d.channel_major_ok in (0, 1), d.name
+
+
+def test_every_shape_is_fuzzed(plans):
+    from test_gpu_fuzz import SHAPES
+    fuzzed = {(M, P, D, FMT[f]) for M, P, D, fmts, _ in SHAPES for f in fmts}
+    missing = sorted({shape_of(d) for d in plans} - fuzzed)
+    assert not missing, f"registered but not in test_gpu_fuzz.SHAPES: {missing}"
+    extra = sorted(fuzzed - {shape_of(d) for d in plans})
+    assert not extra, f"in test_gpu_fuzz.SHAPES without a fused plan: {extra}"
+
+
+def test_channel_major_route_is_pinned(plans):
+    by_slabs = {d.name.decode() for d in plans if not d.channel_major_ok}
+    assert by_slabs == SLAB_PLANS
+    # the 16-byte-run defaults measured slower fused than by slabs (profiles/r04_channel_major_routes.txt) stay on slabs
+    assert {d.name.decode() for d in plans if d.variant == 0 and not d.channel_major_ok} == {
+        "pfb_fast<M1024,P16,D1024,int16>", "pfb_fast<M1024,P16,D1024,cf32>", "pfb_fast<M560,P12,D560,int16>",
+        "pfb_fast<M560,P12,D560,int8>", "pfb_fast<M560,P12,D560,cf32>", "pfb_fast<M250,P12,D250,int16>",
+        "pfb_fast<M500,P12,D500,int16>"}
+
+
+def test_design_names_the_slab_plans():
+    """DESIGN.md section 5.2's paragraph on the slab route lists exactly the plans that take it."""
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        text = f.read()
+    sec = text[text.index("### 5.2 "):text.index("### 5.2b")]
+    start = sec.index("* **Frame-major slabs + a transpose kernel**")
+    end = sec.find("\n* ", start + 1)
+    para = sec[start:end if end > 0 else len(sec)]
+    assert set(NAME_RE.findall(para)) and {m.group(0) for m in NAME_RE.finditer(para)} == SLAB_PLANS
