@@ -56,9 +56,28 @@ typedef struct {
   const char* name;       /* what pfb_last_kernel reports (static storage) */
   int default_schedule, magnitude_schedule, chunk_frames;
   int channel_major_ok;   /* 0: a channel-major handle on this plan goes by slabs + transpose */
+  int default_frames_per_block; /* the tuned run length (before rounding to the chunk), what a long call runs with */
+  int threads;            /* threads of the plan's FIR workgroup (run-length policy for short calls) */
 } pfb_fast_plan_desc;
 int pfb_fast_plan_count(void);
 int pfb_fast_plan_info(int index, pfb_fast_plan_desc* out); /* PFB_ERR_BAD_ARG past the end or for NULL */
+
+/* How the handle's last kernel launch went: what the launch policy actually handed to the kernel, so that a test can
+ * tell which regime a call ran in without repeating the policy's arithmetic.  One call of pfb_process(_async) is one
+ * launch (each staged chunk of a host-pointer call is one; pfb_process_shard_async makes two).  Host only, touches no
+ * device; all zeros before the first launch.  A launch of the generic kernel reports fused = 0, its frames, and zeros. */
+typedef struct {
+  int fused;              /* 1: a fused plan (pfb_last_kernel names it), 0: the generic kernel or no launch yet */
+  int schedule;           /* KernelParams.schedule as passed (-1: a fused channel-major launch, the kernel's own pick) */
+  int frames_per_block;   /* run length passed to the kernel, after every per-call adjustment and rounding */
+  int xcd_remap;          /* as passed: 0 off, 1 consecutive runs on one XCD, G > 1 in groups of G */
+  int by_slabs;           /* 1: channel-major through frame-major slabs + the transpose kernel */
+  int reserved;
+  uint64_t frames;        /* frames of the launch */
+  uint64_t runs;          /* ceil(frames / frames_per_block), summed over the slabs where it went by slabs */
+  uint64_t slab_frames;   /* frames per slab (the last one may be shorter), 0 when not by slabs */
+} pfb_launch_report;
+int pfb_last_launch(const pfb_handle* h, pfb_launch_report* out); /* PFB_ERR_BAD_ARG for NULL */
 
 /* Diagnostic: throws a C++ exception of the given kind (0 = std::bad_alloc, 1 = std::runtime_error,
  * 2 = a non-std type) INSIDE the guard every entry point runs under and returns what the guard

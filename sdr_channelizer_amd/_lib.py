@@ -75,7 +75,16 @@ class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
         ("name", C.c_char_p), ("default_schedule", C.c_int), ("magnitude_schedule", C.c_int),
-        ("chunk_frames", C.c_int), ("channel_major_ok", C.c_int),
+        ("chunk_frames", C.c_int), ("channel_major_ok", C.c_int), ("default_frames_per_block", C.c_int),
+        ("threads", C.c_int),
+    ]
+
+
+class PfbLaunchReport(C.Structure):
+    _fields_ = [
+        ("fused", C.c_int), ("schedule", C.c_int), ("frames_per_block", C.c_int), ("xcd_remap", C.c_int),
+        ("by_slabs", C.c_int), ("reserved", C.c_int), ("frames", C.c_uint64), ("runs", C.c_uint64),
+        ("slab_frames", C.c_uint64),
     ]
 
 
@@ -115,7 +124,7 @@ EXPORTS = (
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
-               "pfb_fast_plan_count", "pfb_fast_plan_info")
+               "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch")
 
 _lib = None
 
@@ -224,6 +233,7 @@ def load() -> C.CDLL:
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
+    lib.pfb_last_launch.argtypes = [vp, C.POINTER(PfbLaunchReport)]
     for name in EXPORTS + DEV_EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     _lib = lib

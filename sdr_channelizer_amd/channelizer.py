@@ -133,6 +133,13 @@ class Channelizer(Handle):
     def last_kernel(self) -> str:
         return self._lib.pfb_last_kernel(self._h).decode()
 
+    @property
+    def last_launch(self) -> L.PfbLaunchReport:
+        """What the launch policy handed to the kernel in the last launch (pfb_last_launch; host only)."""
+        rep = L.PfbLaunchReport()
+        L.check(self._lib.pfb_last_launch(self._h, C.byref(rep)), "pfb_last_launch")
+        return rep
+
     def set_stream(self, hip_stream: int) -> None:
         L.check(self._lib.pfb_set_stream(self._h, C.c_void_p(hip_stream)), "pfb_set_stream")
 

@@ -71,6 +71,7 @@ struct pfb_handle {
   void* d_matrix = nullptr;     // pfb_pdw_from_iq_file: the record's channel matrix (grow-only)
   size_t matrix_bytes = 0;
   const char* last_kernel = "";
+  pfb_launch_report last_launch{};  // what launch_frames handed to the kernel last time (pfb_last_launch)
   pfb::HostStage stage;  // host-pointer calls (stage.d_in[0] is also pfb_prime's scratch)
   // PFB_OPT_PROFILE: event pairs around each channelizer kernel launch
   int opt_profile = 0;
@@ -229,6 +230,14 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
     const int cpt = h->fast->cols_per_thread;
     const int bmod = ((p.base % cpt) + cpt) % cpt;
     p.vec_ok = (bmod == 0) && (reinterpret_cast<uintptr_t>(d_iq) % (uintptr_t)(h->bps * cpt) == 0);
+    pfb_launch_report rep{};
+    rep.fused = 1;
+    rep.schedule = p.schedule;
+    rep.frames_per_block = p.frames_per_block;
+    rep.xcd_remap = p.xcd_remap;
+    rep.by_slabs = by_slabs ? 1 : 0;
+    rep.frames = frames;
+    rep.runs = (frames + (uint64_t)fpb - 1) / (uint64_t)fpb;
     if (by_slabs) {
       long long sf = h->opt_slab_frames > 0 ? h->opt_slab_frames : (long long)h->num_cus * fpb;  // one run per CU
       sf = std::max<long long>(64, (sf + 63) / 64 * 64);
@@ -237,6 +246,8 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
       sf = std::min<long long>(sf, ((long long)frames + 63) / 64 * 64);
       // (tried: two slabs and a side stream, slab k transposed while slab k + 1 is filled -- 6.9 ms instead of 6.4 per 2^30
       // samples at M = 1024: the two kernels slow each other down by more than the overlap buys.  One slab, one stream.)
+      rep.slab_frames = (uint64_t)sf;
+      rep.runs = 0;
       const size_t need = (size_t)sf * h->M * h->out_elem;
       if (need > h->slab_bytes) {
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -256,15 +267,19 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
         if (f0 > 0)  // "history" of a later slab = the input samples in front of it
           q.hist = static_cast<const char*>(q.in) - (size_t)h->hist_samples * h->bps;
         HIP_TRY(h->fast->launch(q, h->stream));
+        rep.runs += ((uint64_t)q.frames + (uint64_t)fpb - 1) / (uint64_t)fpb;
         HIP_TRY(pfb::launch_transpose_slab(h->d_slab, q.frames, h->M, d_out, out_ld, out_frame0 + f0, h->out_elem, h->stream));
       }
     } else {
       HIP_TRY(h->fast->launch(p, h->stream));
     }
     h->last_kernel = h->fast->name;
+    h->last_launch = rep;
   } else {
     HIP_TRY(pfb::launch_generic(p, h->stream));
     h->last_kernel = "pfb_generic";
+    h->last_launch = pfb_launch_report{};
+    h->last_launch.frames = frames;
   }
   if (ev_second) HIP_TRY(hipEventRecord(ev_second, h->stream));
   return PFB_OK;
@@ -923,6 +938,12 @@ int pfb_set_option(pfb_handle* h, int option, int64_t value) {
 }
 
 const char* pfb_last_kernel(const pfb_handle* h) { return h ? h->last_kernel : ""; }
+
+int pfb_last_launch(const pfb_handle* h, pfb_launch_report* out) {
+  if (!h || !out) return PFB_ERR_BAD_ARG;
+  *out = h->last_launch;
+  return PFB_OK;
+}
 
 int pfb_get_device(const pfb_handle* h, int* device_id) {
   if (!h || !device_id) return PFB_ERR_BAD_ARG;

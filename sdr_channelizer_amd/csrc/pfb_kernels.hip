@@ -329,5 +329,7 @@ extern "C" int pfb_fast_plan_info(int index, pfb_fast_plan_desc* out) {
   out->magnitude_schedule = e->info.magnitude_schedule;
   out->chunk_frames = e->info.chunk_frames;
   out->channel_major_ok = e->info.channel_major_ok ? 1 : 0;
+  out->default_frames_per_block = e->info.default_frames_per_block;
+  out->threads = e->info.threads;
   return PFB_OK;
 }

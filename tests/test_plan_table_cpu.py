@@ -78,6 +78,40 @@ def test_schedules_and_chunks(plans):
         assert d.chunk_frames >= 1 and d.channel_major_ok in (0, 1), d.name
 
 
+def test_run_lengths_and_workgroup_sizes(plans):
+    """default_frames_per_block and threads, appended to the descriptor: what the launch policy tunes a long call to.
+    Pinned for the rows the README quotes rates for; sane for every row."""
+    for d in plans:
+        assert d.default_frames_per_block >= 2 * d.chunk_frames, d.name
+        assert d.threads >= 64 and d.threads % 64 == 0 and d.threads <= 1024, d.name
+    by_name = {d.name.decode(): (d.default_schedule, d.chunk_frames, d.default_frames_per_block, d.threads) for d in plans}
+    assert by_name["pfb_fast<M64,P12,D64,int16>"] == (4, 8, 512, 64)
+    assert by_name["pfb_fast<M64,P12,D64,int8>"] == (7, 8, 256, 64)
+    assert by_name["pfb_fast<M128,P12,D64,int16>"] == (11, 8, 32, 64)
+    assert by_name["pfb_fast<M256,P8,D256,int8>"] == (0, 4, 32, 64)
+    assert by_name["pfb_fast<M1024,P16,D1024,int16>"] == (6, 4, 512, 512)
+    assert by_name["pfb_fast<M1024,P16,D1024,int16,16w>"] == (0, 8, 256, 1024)
+    assert by_name["pfb_fast<M1024,P16,D1024,int16,duo>"] == (13, 8, 256, 256)
+    assert by_name["pfb_fast<M560,P12,D560,int8>"] == (6, 2, 512, 320)
+    assert by_name["pfb_fast<M560,P12,D560,int16,9w>"] == (0, 7, 252, 576)
+    assert by_name["pfb_fast<M8,P12,D8,cf32>"] == (0, 64, 1024, 64)
+    # the struct grew at its end only: the fields in front keep their offsets
+    offs = [getattr(L.PfbFastPlanDesc, f).offset for f, _ in L.PfbFastPlanDesc._fields_]
+    assert offs == sorted(offs) and [f for f, _ in L.PfbFastPlanDesc._fields_][-2:] == ["default_frames_per_block", "threads"]
+    assert L.PfbFastPlanDesc.channel_major_ok.offset == 44 and L.C.sizeof(L.PfbFastPlanDesc) == 56
+
+
+def test_launch_report_needs_a_handle():
+    """pfb_last_launch is host only: no handle (there is none without a device) or no destination is an argument error,
+    and the mirror of the struct has the header's layout.  (That a new handle reports all zeros, and what it reports
+    after a launch, is checked on the GPU: tests/test_gpu_async.py, tests/test_gpu_plan_at_size.py.)"""
+    lib = L.load()
+    rep = L.PfbLaunchReport()
+    assert lib.pfb_last_launch(None, L.C.byref(rep)) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_last_launch(None, None) == L.PFB_ERR_BAD_ARG
+    assert L.C.sizeof(L.PfbLaunchReport) == 48 and L.PfbLaunchReport.frames.offset == 24
+
+
 def test_every_shape_is_fuzzed(plans):
     from test_gpu_fuzz import SHAPES
     fuzzed = {(M, P, D, FMT[f]) for M, P, D, fmts, _ in SHAPES for f in fmts}
