@@ -226,6 +226,10 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
     }
     // short sliding runs in dispatch order already sweep the stream as one window: leave them round-robin over the XCDs
     if ((p.schedule == 0 || p.schedule == 11) && fpb <= 64 && h->opt_xcd_remap < 0) p.xcd_remap = 0;
+    // The fixed lengths of schedules 3 and 4 (24, 64) are whole chunks of the plans that have those schedules (c = 8).  A
+    // plan without them runs its sliding runs at that length, and an interior run stores whole chunks unconditionally:
+    // a run that is no whole number of chunks would write past its end, and past the call's last frame.
+    fpb = ((fpb + c - 1) / c) * c;
     p.frames_per_block = fpb;
     const int cpt = h->fast->cols_per_thread;
     const int bmod = ((p.base % cpt) + cpt) % cpt;

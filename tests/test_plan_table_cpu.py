@@ -121,6 +121,44 @@ def test_every_shape_is_fuzzed(plans):
     assert not extra, f"in test_gpu_fuzz.SHAPES without a fused plan: {extra}"
 
 
+def simulate_calls(lens, D):
+    """(frames, carried phase at its start) of every call and the phases left behind: the stream arithmetic of
+    pfb_frames_for, frames = (phase + n) // D, phase = (phase + n) % D."""
+    phase, calls, left = 0, [], set()
+    for n in lens:
+        assert n >= 0
+        calls.append(((phase + n) // D, phase))
+        phase = (phase + n) % D
+        left.add(phase)
+    return calls, left
+
+
+def test_short_call_walk_has_no_hole(plans):
+    """The call lengths tests/test_gpu_plan_short_calls.py plays on every row: every frame count 0 ... K = 4 c + 3,
+    every count up to 2 c + 1 both from a frame boundary and from a carried phase, a call that leaves phase D - 1, and
+    the calls of 1, D - 1, history - 1 and history samples -- for every registered row, so that a plan registered
+    tomorrow is not walked with a hole.  The schedule sweep's shorter walk: 0 ... 2 c + 1 in both classes, and K."""
+    from test_gpu_plan_short_calls import sweep_lengths, top_frames, walk_lengths
+    for d in plans:
+        D, c = d.D, d.chunk_frames
+        K, hist = top_frames(c), d.M * d.P + D   # pfb_history_samples: the GPU tests read it from the handle
+        assert K == 4 * c + 3
+        lens = walk_lengths(D, K, hist)
+        calls, left = simulate_calls(lens, D)
+        assert {f for f, _ in calls} >= set(range(K + 1)), d.name
+        assert {f for f, ph in calls if ph == 0} >= set(range(1, 2 * c + 2)), d.name
+        assert {f for f, ph in calls if ph != 0} >= set(range(1, 2 * c + 2)), d.name
+        assert D - 1 in left, d.name
+        assert {1, D - 1, hist - 1, hist} <= set(lens), d.name
+        assert K * (K + 1) // 2 <= sum(lens) // D <= K * (K + 1), d.name   # "about K (K + 1) / 2 frames"
+        sweep = sweep_lengths(D, c, hist)
+        calls, _ = simulate_calls(sweep, D)
+        assert {f for f, ph in calls if ph == 0} >= set(range(1, 2 * c + 2)), d.name
+        assert {f for f, ph in calls if ph != 0} >= set(range(1, 2 * c + 2)), d.name
+        assert 0 in {f for f, _ in calls} and calls[-1] == (K, 0), d.name
+        assert sum(sweep) <= sum(lens), d.name   # it is played on a prefix of the same stream
+
+
 def test_channel_major_route_is_pinned(plans):
     by_slabs = {d.name.decode() for d in plans if not d.channel_major_ok}
     assert by_slabs == SLAB_PLANS
