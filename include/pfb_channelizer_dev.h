@@ -79,6 +79,22 @@ typedef struct {
 } pfb_launch_report;
 int pfb_last_launch(const pfb_handle* h, pfb_launch_report* out); /* PFB_ERR_BAD_ARG for NULL */
 
+/* The launch policy on its own (host only, no device needed): the report a handle on row plan_index of the table above
+ * would store for a fused launch of `frames` frames with these options, layout, output type and compute-unit count --
+ * the function launch_frames calls (pfb_launch_policy.h).  PFB_ERR_BAD_ARG for NULL, an index past the end or a
+ * struct_size that is not sizeof(pfb_launch_request). */
+typedef struct {
+  uint32_t struct_size;
+  int schedule;           /* PFB_OPT_SCHEDULE, -1 = default */
+  int frames_per_block;   /* PFB_OPT_FRAMES_PER_BLOCK, 0 = default */
+  int xcd_remap;          /* PFB_OPT_XCD_REMAP, -1 = per schedule */
+  int channel_major;      /* the handle's layout */
+  int magnitude;          /* PFB_FLAG_MAGNITUDE */
+  int num_cus;            /* compute units of the device */
+  int64_t slab_frames;    /* PFB_OPT_SLAB_FRAMES, 0 = default */
+} pfb_launch_request;
+int pfb_plan_launch(int plan_index, const pfb_launch_request* rq, uint64_t frames, pfb_launch_report* out);
+
 /* Diagnostic: throws a C++ exception of the given kind (0 = std::bad_alloc, 1 = std::runtime_error,
  * 2 = a non-std type) INSIDE the guard every entry point runs under and returns what the guard
  * returns (PFB_ERR_NO_MEMORY / PFB_ERR_INTERNAL): proof that nothing thrown crosses the C ABI. */

@@ -88,6 +88,13 @@ class PfbLaunchReport(C.Structure):
     ]
 
 
+class PfbLaunchRequest(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("schedule", C.c_int), ("frames_per_block", C.c_int), ("xcd_remap", C.c_int),
+        ("channel_major", C.c_int), ("magnitude", C.c_int), ("num_cus", C.c_int), ("slab_frames", C.c_int64),
+    ]
+
+
 PFB_PDW_MATLAB_QUIRKS = 1        # phase(toa:jj) linear-indexes column 1 (create_pdws_channelized.m:114)
 PFB_PDW_CHANNEL_MAJOR = 2
 PFB_PDW_BINFREQ_UNSHIFTED = 4    # binFreqs(bin) from the FFT-ordered list (:42/:80 if centerFrequencies is unshifted; unpinned)
@@ -124,7 +131,7 @@ EXPORTS = (
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
-               "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch")
+               "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch")
 
 _lib = None
 
@@ -234,6 +241,7 @@ def load() -> C.CDLL:
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
     lib.pfb_last_launch.argtypes = [vp, C.POINTER(PfbLaunchReport)]
+    lib.pfb_plan_launch.argtypes = [C.c_int, C.POINTER(PfbLaunchRequest), u64, C.POINTER(PfbLaunchReport)]
     for name in EXPORTS + DEV_EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     _lib = lib
@@ -254,3 +262,14 @@ def fast_plans() -> list[PfbFastPlanDesc]:
         check(lib.pfb_fast_plan_info(i, C.byref(d)), "pfb_fast_plan_info")
         rows.append(d)
     return rows
+
+
+def plan_launch(row: int, frames: int, num_cus: int, schedule: int = -1, frames_per_block: int = 0, xcd_remap: int = -1,
+                slab_frames: int = 0, channel_major: bool = False, magnitude: bool = False) -> PfbLaunchReport:
+    """What the launch policy decides for row ``row`` of the table, these options and ``frames`` frames
+    (pfb_plan_launch; host only): the report a handle stores for that launch."""
+    rq = PfbLaunchRequest(C.sizeof(PfbLaunchRequest), schedule, frames_per_block, xcd_remap, int(channel_major),
+                          int(magnitude), num_cus, slab_frames)
+    rep = PfbLaunchReport()
+    check(load().pfb_plan_launch(row, C.byref(rq), frames, C.byref(rep)), "pfb_plan_launch")
+    return rep

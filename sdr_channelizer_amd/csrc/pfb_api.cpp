@@ -1,9 +1,11 @@
 // pfb_api.cpp -- host side of the channelizer's C ABI in include/pfb_channelizer.h.
 //
-// Owns: the handle (taps, twiddles, history, counters), kernel selection, its
-// host-pointer and .iq paths (over the staged pipeline and the record reader of
-// pfb_host.h) and the state blob.  All arithmetic is in pfb_kernels.hip; there
-// is deliberately no CPU implementation here.  The STFT's ABI is in pfb_stft_api.cpp.
+// Owns: the handle (taps, twiddles, history, counters, options), the choice between the shape's fused plan and the
+// generic kernel, the launch itself (launch_frames: one kernel, or slabs + transpose; how a fused plan is launched is
+// decided in pfb_launch_policy.h), the host-pointer and .iq paths (over the staged pipeline and the record reader of
+// pfb_host.h), time sharding, the state blob and the copy yardsticks of pfb_channelizer_dev.h.  All arithmetic is in
+// the kernels (pfb_kernels*.hip); there is deliberately no CPU implementation here.  The STFT's ABI is in
+// pfb_stft_api.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +21,7 @@
 #include "pfb_common.h"
 #include "pfb_channelizer_dev.h"
 #include "pfb_host.h"
+#include "pfb_launch_policy.h"
 
 using pfb::DeviceGuard;
 using pfb::g_detail;
@@ -54,6 +57,7 @@ struct pfb_handle {
   uint64_t frame_index = 0;  // global index of the next frame
   hipStream_t stream = nullptr;
   const pfb::FastKernelInfo* fast = nullptr;
+  pfb_fast_plan_desc plan{};  // fast's row of the table as pfb_fast_plan_info gives it: what the launch policy reads
   // options
   int opt_kernel = 0;
   int opt_frames_per_block = 0;
@@ -113,6 +117,50 @@ void free_handle(pfb_handle* h) {
 
 uint64_t frames_for(const pfb_handle* h, uint64_t n) { return (h->phase + n) / (uint64_t)h->D; }
 
+// PFB_OPT_PROFILE: take the next event pair of the pool (a new one when all are in use) and record its first event on
+// the stream.  *second is the event to record behind the launch, null when not profiling or 4096 pairs are taken.
+int begin_profile(pfb_handle* h, hipEvent_t* second) {
+  *second = nullptr;
+  if (!h->opt_profile || h->ev_used >= 4096) return PFB_OK;
+  if (h->ev_used == h->ev_pool.size()) {
+    hipEvent_t a = nullptr, b = nullptr;
+    HIP_TRY(hipEventCreate(&a));
+    if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return hip_fail(hipGetLastError(), "hipEventCreate"); }
+    h->ev_pool.emplace_back(a, b);
+  }
+  HIP_TRY(hipEventRecord(h->ev_pool[h->ev_used].first, h->stream));
+  *second = h->ev_pool[h->ev_used].second;
+  ++h->ev_used;  // only a pair whose first event was recorded counts as used
+  return PFB_OK;
+}
+
+// Channel-major by slabs of sf frames: the frame-major kernel fills the handle's scratch slab (grown here), the
+// transpose kernel moves it into place.  p is the whole call's launch; its output fields say where the matrix is.
+int launch_by_slabs(pfb_handle* h, const pfb::KernelParams& p, long long sf) {
+  const size_t need = (size_t)sf * h->M * h->out_elem;
+  if (need > h->slab_bytes) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    (void)hipFree(h->d_slab);
+    h->d_slab = nullptr; h->slab_bytes = 0;
+    HIP_TRY(hipMalloc(&h->d_slab, need));
+    h->slab_bytes = need;
+  }
+  for (long long f0 = 0; f0 < p.frames; f0 += sf) {
+    pfb::KernelParams q = p;
+    q.layout = PFB_LAYOUT_FRAME_MAJOR;
+    q.out = static_cast<float2*>(h->d_slab);
+    q.frames = std::min<long long>(sf, p.frames - f0);
+    q.frame0 = p.frame0 + f0;
+    q.in = static_cast<const char*>(p.in) + (size_t)f0 * h->D * h->bps;
+    q.n_in = p.n_in - f0 * h->D;
+    if (f0 > 0)  // "history" of a later slab = the input samples in front of it
+      q.hist = static_cast<const char*>(q.in) - (size_t)h->hist_samples * h->bps;
+    HIP_TRY(h->fast->launch(q, h->stream));
+    HIP_TRY(pfb::launch_transpose_slab(h->d_slab, q.frames, h->M, p.out, p.out_ld, p.out_frame0 + f0, h->out_elem, h->stream));
+  }
+  return PFB_OK;
+}
+
 // Launch the channelizer kernel(s) for local frames [f_begin, f_end) of a device buffer of n samples.  `hist` holds
 // the hist_samples raw samples in front of d_iq[0]; it is only read when f_begin == 0 (a later range starts at
 // least hist_samples into the buffer, so its "history" is the buffer itself).  Output row f lands where a call
@@ -156,124 +204,22 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
   p.tile_waves = h->opt_tile_waves;
   const bool want_fast = h->fast && h->opt_kernel != 1;
   if (h->opt_kernel == 2 && !want_fast) return PFB_ERR_UNSUPPORTED;
-  hipEvent_t ev_first = nullptr, ev_second = nullptr;
-  if (h->opt_profile && h->ev_used < 4096) {
-    if (h->ev_used == h->ev_pool.size()) {
-      hipEvent_t a = nullptr, b = nullptr;
-      HIP_TRY(hipEventCreate(&a));
-      if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return hip_fail(hipGetLastError(), "hipEventCreate"); }
-      h->ev_pool.emplace_back(a, b);
-    }
-    ev_first = h->ev_pool[h->ev_used].first;
-    ev_second = h->ev_pool[h->ev_used].second;
-    HIP_TRY(hipEventRecord(ev_first, h->stream));
-    ++h->ev_used;  // only a pair whose first event was recorded counts as used
-  }
-  // Channel-major output of a fused shape is written by the kernel itself (its transposed-tile or plain
-  // channel-major instantiation) where the plan has one (channel_major_ok, kChannelMajorOk in pfb_fast.hpp).  The
-  // 16-wave plans and the three-pass plans on chunks of 4 or 2 frames -- the defaults of M = 1024, 560, 500 and 250,
-  // whose fused stores would be 32- or 16-byte runs per channel -- have none and go by slabs instead: the frame-major
-  // kernel fills a scratch slab, a transpose kernel moves it into place (1.5-5x faster than the fused stores on those
-  // plans, profiles/r04_channel_major_routes.txt).  A slab must be long enough to fill the chip with runs, so it does
-  // not fit the memory-side cache; PFB_OPT_SCHEDULE 9 forces the slabs on any shape, PFB_OPT_SLAB_FRAMES sets their length.
-  const bool cm = h->layout == PFB_LAYOUT_CHANNEL_MAJOR;
-  const bool forced_fused = h->opt_schedule == 0 || h->opt_schedule == 2 || h->opt_schedule == 8;
-  // (A fused route for the team plans -- the team kernel transposing its own tiles through an L2-resident scratch -- was
-  // bit-identical but slower than the slabs, 7.4 against 6.4 ms per 2^30 samples at M = 1024, and was removed.)
-  const bool by_slabs = cm && want_fast && (!h->fast->channel_major_ok || h->opt_schedule == 9);
+  hipEvent_t ev_second = nullptr;
+  const int prc = begin_profile(h, &ev_second);
+  if (prc != PFB_OK) return prc;
   if (want_fast) {
-    const int c = h->fast->chunk_frames;
-    int fpb = h->opt_frames_per_block > 0 ? h->opt_frames_per_block : h->fast->default_frames_per_block;
-    fpb = ((fpb + c - 1) / c) * c;
-    p.schedule = (h->opt_schedule >= 0 && h->opt_schedule != 9) ? h->opt_schedule : h->fast->default_schedule;
-    if (h->opt_schedule < 0 && (h->flags & PFB_FLAG_MAGNITUDE) && h->fast->magnitude_schedule >= 0 && !cm) {
-      p.schedule = h->fast->magnitude_schedule;  // fused abs(): magnitudes staged in LDS, sliding runs
-    }
-    if (cm && !by_slabs)  // fused channel-major: 0 = sliding runs, 2 = tiles, 8 = short runs transposed in LDS, else the kernel's pick
-      p.schedule = forced_fused ? h->opt_schedule : -1;
-    if (p.schedule == 3 && h->opt_frames_per_block <= 0) fpb = 24;
-    // Team kernels run one workgroup per CU, so their runs are dealt in rounds of num_cus, and a last round that is not
-    // full costs a whole round: 683 593 frames of M = 1024 in the tuned 512-frame runs are 5.2 rounds = 6 (0.549 of the
-    // roofline), in 672-frame runs 3.97 rounds (0.600).  Unless the caller fixed it, the run length is the call's frames
-    // split evenly over k full rounds, k chosen for runs near twice the tuned length (full rounds of 1024-frame runs
-    // measured +1.3 % over 512: half the pipeline fills and drains) -- short calls thereby spread over every CU instead
-    // of filling a few.  (The slab route sizes its slabs as one 512-frame run per CU: already whole rounds.)
-    if (p.schedule == 6 && h->opt_frames_per_block <= 0 && !by_slabs && frames > 0) {
-      // (plans of <= 8 waves are built for several workgroups per CU, 16 waves in all: their rounds are that much wider)
-      const long long slots = (long long)h->num_cus * std::max(1, 16 / ((h->fast->threads + 64 * c) / 64)), target = 2ll * fpb;
-      const long long k = std::max<long long>(1, ((long long)frames + slots * target / 2) / (slots * target));
-      const long long even = ((long long)frames + k * slots - 1) / (k * slots);
-      fpb = (int)std::min<long long>(std::max<long long>(even, 2 * c), 4 * target);
-    }
-    // The other kernels with long runs (a wave pair, a lockstep workgroup or a single wave per run of 128-512 frames): a
-    // short call must not leave most of the chip idle -- 2 * 10^7 samples of M = 1024 in 512-frame runs kept 39 of 256 CUs
-    // busy (0.105 of the roofline; 0.456 spread over all of them).  When the tuned run length gives fewer runs than the
-    // chip holds at once, the runs shrink until it is full (at least one chunk pair each).
-    if ((p.schedule == 0 || p.schedule == 7 || p.schedule == 11 || p.schedule == 13) && h->opt_frames_per_block <= 0 && !by_slabs &&
-        !cm && frames > 0) {
-      const int waves = std::max(1, h->fast->threads / 64);
-      const long long per_cu = p.schedule == 7 ? 6 : p.schedule == 13 ? 2 : std::max(1, 8 / waves);  // runs resident per CU
-      const long long slots = h->num_cus * per_cu;
-      if (((long long)frames + fpb - 1) / fpb < slots) {
-        const long long even = ((long long)frames + slots - 1) / slots;
-        fpb = (int)std::min<long long>(fpb, std::max<long long>(2 * c, (even + c - 1) / c * c));
-      }
-    }
-    if (p.schedule == 6 || p.schedule == 7) fpb = ((fpb + 2 * c - 1) / (2 * c)) * (2 * c);  // these kernels walk chunks in pairs
-    if (p.schedule == 4) {
-      if (h->opt_frames_per_block <= 0) fpb = 64;
-      if (h->opt_xcd_remap < 0) p.xcd_remap = 0;  // 512-frame workgroups: one dense sweep beats L2 halo hits
-    }
-    // short sliding runs in dispatch order already sweep the stream as one window: leave them round-robin over the XCDs
-    if ((p.schedule == 0 || p.schedule == 11) && fpb <= 64 && h->opt_xcd_remap < 0) p.xcd_remap = 0;
-    // The fixed lengths of schedules 3 and 4 (24, 64) are whole chunks of the plans that have those schedules (c = 8).  A
-    // plan without them runs its sliding runs at that length, and an interior run stores whole chunks unconditionally:
-    // a run that is no whole number of chunks would write past its end, and past the call's last frame.
-    fpb = ((fpb + c - 1) / c) * c;
-    p.frames_per_block = fpb;
+    const pfb::LaunchRequest rq{h->opt_schedule, h->opt_frames_per_block, h->opt_xcd_remap, h->opt_slab_frames,
+                                h->layout == PFB_LAYOUT_CHANNEL_MAJOR, (h->flags & PFB_FLAG_MAGNITUDE) != 0, h->num_cus};
+    const pfb_launch_report rep = pfb::plan_launch(h->plan, rq, frames);
+    p.schedule = rep.schedule;
+    p.frames_per_block = rep.frames_per_block;
+    p.xcd_remap = rep.xcd_remap;
     const int cpt = h->fast->cols_per_thread;
     const int bmod = ((p.base % cpt) + cpt) % cpt;
     p.vec_ok = (bmod == 0) && (reinterpret_cast<uintptr_t>(d_iq) % (uintptr_t)(h->bps * cpt) == 0);
-    pfb_launch_report rep{};
-    rep.fused = 1;
-    rep.schedule = p.schedule;
-    rep.frames_per_block = p.frames_per_block;
-    rep.xcd_remap = p.xcd_remap;
-    rep.by_slabs = by_slabs ? 1 : 0;
-    rep.frames = frames;
-    rep.runs = (frames + (uint64_t)fpb - 1) / (uint64_t)fpb;
-    if (by_slabs) {
-      long long sf = h->opt_slab_frames > 0 ? h->opt_slab_frames : (long long)h->num_cus * fpb;  // one run per CU
-      sf = std::max<long long>(64, (sf + 63) / 64 * 64);
-      sf = std::max<long long>(sf, (h->hist_samples + h->D - 1) / h->D + 1);  // a later slab's window reaches back into the input, never into the history
-      sf = std::min<long long>(sf, 65535ll * 64);  // the transpose kernel's grid: one row of 64 x 64 tiles per 64 frames
-      sf = std::min<long long>(sf, ((long long)frames + 63) / 64 * 64);
-      // (tried: two slabs and a side stream, slab k transposed while slab k + 1 is filled -- 6.9 ms instead of 6.4 per 2^30
-      // samples at M = 1024: the two kernels slow each other down by more than the overlap buys.  One slab, one stream.)
-      rep.slab_frames = (uint64_t)sf;
-      rep.runs = 0;
-      const size_t need = (size_t)sf * h->M * h->out_elem;
-      if (need > h->slab_bytes) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_slab);
-        h->d_slab = nullptr; h->slab_bytes = 0;
-        HIP_TRY(hipMalloc(&h->d_slab, need));
-        h->slab_bytes = need;
-      }
-      for (long long f0 = 0; f0 < (long long)frames; f0 += sf) {
-        pfb::KernelParams q = p;
-        q.layout = PFB_LAYOUT_FRAME_MAJOR;
-        q.out = static_cast<float2*>(h->d_slab);
-        q.frames = std::min<long long>(sf, (long long)frames - f0);
-        q.frame0 = p.frame0 + f0;
-        q.in = static_cast<const char*>(d_iq) + (size_t)f0 * h->D * h->bps;
-        q.n_in = (long long)n - f0 * h->D;
-        if (f0 > 0)  // "history" of a later slab = the input samples in front of it
-          q.hist = static_cast<const char*>(q.in) - (size_t)h->hist_samples * h->bps;
-        HIP_TRY(h->fast->launch(q, h->stream));
-        rep.runs += ((uint64_t)q.frames + (uint64_t)fpb - 1) / (uint64_t)fpb;
-        HIP_TRY(pfb::launch_transpose_slab(h->d_slab, q.frames, h->M, d_out, out_ld, out_frame0 + f0, h->out_elem, h->stream));
-      }
+    if (rep.by_slabs) {
+      const int rc = launch_by_slabs(h, p, (long long)rep.slab_frames);
+      if (rc != PFB_OK) return rc;
     } else {
       HIP_TRY(h->fast->launch(p, h->stream));
     }
@@ -324,10 +270,58 @@ int process_host(pfb_handle* h, const void* iq, uint64_t n, const pfb::StageOut&
   return pfb::stage_host(h->stage, h->stream, steps, iq, n, out);
 }
 
+// Allocate the per-lane tables of fused plan f and fill them from the handle's taps and twiddles (the null stream is
+// drained when this returns).  On an error nothing stays allocated and both pointers are null.
+hipError_t make_lane_tables(const pfb_handle* h, const pfb::FastKernelInfo* f, float** taps_lane, float2** tw_lane) {
+  *taps_lane = nullptr;
+  *tw_lane = nullptr;
+  hipError_t e = hipMalloc((void**)taps_lane, (size_t)f->taps_lane_floats * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)tw_lane, (size_t)f->tw_lane_elems * sizeof(float2));
+  if (e == hipSuccess) e = f->init_tables(h->d_taps, h->d_tw, *taps_lane, *tw_lane, nullptr);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) {
+    (void)hipFree(*taps_lane);
+    (void)hipFree(*tw_lane);
+    *taps_lane = nullptr;
+    *tw_lane = nullptr;
+  }
+  return e;
+}
+
 // rows [row0, ...) of the handle's output layout: frame-major rows, or an M x ld channel-major matrix
 pfb::StageOut layout_out(const pfb_handle* h, void* out, bool device, uint64_t ld, uint64_t row0) {
   return h->layout == PFB_LAYOUT_FRAME_MAJOR ? pfb::StageOut{out, device, 0, row0, 0}
                                              : pfb::StageOut{out, device, ld, row0, h->M};
+}
+
+// The timing loop of the two copy yardsticks: scratch of in_bytes (set to 1s) and out_bytes on the current device, one
+// warm-up launch, then `iters` launches of launch(in, out) between an event pair.  *bytes_per_sec = the bytes one
+// launch moves, times iters, over the elapsed time.
+template <class Launch>
+int time_copy(const char* what, size_t in_bytes, size_t out_bytes, double bytes_per_launch, int iters, Launch launch,
+              double* bytes_per_sec) {
+  void *in = nullptr, *out = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = PFB_OK;
+  float ms = 0.f;
+  hipError_t e = hipMalloc(&in, in_bytes);
+  if (e == hipSuccess) e = hipMalloc(&out, out_bytes);
+  if (e == hipSuccess) e = hipMemset(in, 1, in_bytes);
+  if (e == hipSuccess) e = hipEventCreate(&e0);
+  if (e == hipSuccess) e = hipEventCreate(&e1);
+  if (e == hipSuccess) e = launch(in, out);  // warm-up
+  if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
+  for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch(in, out);
+  if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
+  if (e == hipSuccess) e = hipEventSynchronize(e1);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+  if (e != hipSuccess) rc = hip_fail(e, what);
+  else *bytes_per_sec = bytes_per_launch * iters / ((double)ms * 1e-3);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  (void)hipFree(in);
+  (void)hipFree(out);
+  return rc;
 }
 
 }  // namespace
@@ -460,8 +454,10 @@ int pfb_create(const pfb_config* cfg, pfb_handle** out) {
   h->bps = pfb::bytes_per_sample(h->fmt);
   h->hist_samples = (int)(M * P + D);
   // (a channel-major handle takes the shape's default plan too: plans without a channel-major instantiation of
-  // their own go through frame-major slabs, see enqueue)
-  h->fast = pfb::find_fast_kernel(h->M, h->P, h->D, h->fmt, 0);
+  // their own go through frame-major slabs, see pfb_launch_policy.h)
+  int row = -1;
+  h->fast = pfb::find_fast_kernel(h->M, h->P, h->D, h->fmt, 0, false, &row);
+  if (h->fast) (void)pfb_fast_plan_info(row, &h->plan);
 
   DeviceGuard g(dev);
   {
@@ -479,12 +475,7 @@ int pfb_create(const pfb_config* cfg, pfb_handle** out) {
   if (e == hipSuccess) e = hipMalloc(&h->d_hist[0], hist_bytes);
   if (e == hipSuccess) e = hipMalloc(&h->d_hist[1], hist_bytes);
   if (e == hipSuccess) e = hipMemcpy(h->d_taps, taps.data(), L * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && h->fast) {
-    e = hipMalloc((void**)&h->d_taps_lane, (size_t)h->fast->taps_lane_floats * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tw_lane, (size_t)h->fast->tw_lane_elems * sizeof(float2));
-    if (e == hipSuccess) e = h->fast->init_tables(h->d_taps, h->d_tw, h->d_taps_lane, h->d_tw_lane, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  }
+  if (e == hipSuccess && h->fast) e = make_lane_tables(h, h->fast, &h->d_taps_lane, &h->d_tw_lane);
   if (e == hipSuccess) e = hipMemset(h->d_hist[0], 0, hist_bytes);
   if (e == hipSuccess) e = hipMemset(h->d_hist[1], 0, hist_bytes);
   if (e != hipSuccess) {
@@ -907,27 +898,21 @@ int pfb_set_option(pfb_handle* h, int option, int64_t value) {
     case PFB_OPT_VARIANT: {
       if (value < 0 || value > 16) return PFB_ERR_BAD_ARG;
       if ((int)value == h->opt_variant) return PFB_OK;
-      const pfb::FastKernelInfo* f =
-          pfb::find_fast_kernel(h->M, h->P, h->D, h->fmt, (int)value);
+      int row = -1;
+      const pfb::FastKernelInfo* f = pfb::find_fast_kernel(h->M, h->P, h->D, h->fmt, (int)value, false, &row);
       if (!f) return PFB_ERR_UNSUPPORTED;
       DeviceGuard g(h->device);
       HIP_TRY(hipStreamSynchronize(h->stream));  // the old tables may still be in use
       float* tl = nullptr;
       float2* tw = nullptr;
-      hipError_t e = hipMalloc((void**)&tl, (size_t)f->taps_lane_floats * sizeof(float));
-      if (e == hipSuccess) e = hipMalloc((void**)&tw, (size_t)f->tw_lane_elems * sizeof(float2));
-      if (e == hipSuccess) e = f->init_tables(h->d_taps, h->d_tw, tl, tw, nullptr);
-      if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-      if (e != hipSuccess) {
-        (void)hipFree(tl);
-        (void)hipFree(tw);
-        return hip_fail(e, "pfb_set_option(PFB_OPT_VARIANT)");
-      }
+      const hipError_t e = make_lane_tables(h, f, &tl, &tw);
+      if (e != hipSuccess) return hip_fail(e, "pfb_set_option(PFB_OPT_VARIANT)");
       (void)hipFree(h->d_taps_lane);
       (void)hipFree(h->d_tw_lane);
       h->d_taps_lane = tl;
       h->d_tw_lane = tw;
       h->fast = f;
+      (void)pfb_fast_plan_info(row, &h->plan);
       h->opt_variant = (int)value;
       return PFB_OK;
     }
@@ -946,6 +931,15 @@ const char* pfb_last_kernel(const pfb_handle* h) { return h ? h->last_kernel : "
 int pfb_last_launch(const pfb_handle* h, pfb_launch_report* out) {
   if (!h || !out) return PFB_ERR_BAD_ARG;
   *out = h->last_launch;
+  return PFB_OK;
+}
+
+int pfb_plan_launch(int plan_index, const pfb_launch_request* rq, uint64_t frames, pfb_launch_report* out) {
+  pfb_fast_plan_desc plan;
+  if (!rq || !out || rq->struct_size != sizeof(pfb_launch_request) || pfb_fast_plan_info(plan_index, &plan) != PFB_OK)
+    return PFB_ERR_BAD_ARG;
+  *out = pfb::plan_launch(plan, pfb::LaunchRequest{rq->schedule, rq->frames_per_block, rq->xcd_remap, rq->slab_frames,
+                                                   rq->channel_major, rq->magnitude, rq->num_cus}, frames);
   return PFB_OK;
 }
 
@@ -990,28 +984,8 @@ int pfb_measure_stream_copy(int device_id, uint64_t bytes_in, int iters, double*
   if (drc != PFB_OK) return drc;
   DeviceGuard g(dev);
   const long long nvec = (long long)(bytes_in / 512) * 32;  // whole row pairs (512 bytes of input per wave)
-  void *in = nullptr, *out = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = PFB_OK;
-  float ms = 0.f;
-  hipError_t e = hipMalloc(&in, (size_t)nvec * 16);
-  if (e == hipSuccess) e = hipMalloc(&out, (size_t)nvec * 32);
-  if (e == hipSuccess) e = hipMemset(in, 1, (size_t)nvec * 16);
-  if (e == hipSuccess) e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
-  if (e == hipSuccess) e = pfb::launch_stream_copy(in, out, nvec, nullptr);  // warm-up
-  if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
-  for (int i = 0; i < iters && e == hipSuccess; ++i) e = pfb::launch_stream_copy(in, out, nvec, nullptr);
-  if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
-  if (e == hipSuccess) e = hipEventSynchronize(e1);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  if (e != hipSuccess) rc = hip_fail(e, "pfb_measure_stream_copy");
-  else *bytes_per_sec = (double)nvec * 48.0 * iters / ((double)ms * 1e-3);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(in);
-  (void)hipFree(out);
-  return rc;
+  return time_copy("pfb_measure_stream_copy", (size_t)nvec * 16, (size_t)nvec * 32, (double)nvec * 48.0, iters,
+                   [&](void* in, void* out) { return pfb::launch_stream_copy(in, out, nvec, nullptr); }, bytes_per_sec);
   });
 }
 
@@ -1026,28 +1000,10 @@ int pfb_measure_mix_copy(int device_id, uint64_t bytes_in, uint32_t write_ratio,
   DeviceGuard g(dev);
   const long long rows = (long long)(bytes_in / 256) / (4ll * rows_per_wave) * (4ll * rows_per_wave);  // whole workgroups
   if (rows <= 0) return PFB_ERR_BAD_ARG;
-  void *in = nullptr, *out = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = PFB_OK;
-  float ms = 0.f;
-  hipError_t e = hipMalloc(&in, (size_t)rows * 256);
-  if (e == hipSuccess) e = hipMalloc(&out, (size_t)rows * 256 * write_ratio);
-  if (e == hipSuccess) e = hipMemset(in, 1, (size_t)rows * 256);
-  if (e == hipSuccess) e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
-  if (e == hipSuccess) e = pfb::launch_mix_copy(in, out, rows, (int)write_ratio, (int)rows_per_wave, nullptr);  // warm-up
-  if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
-  for (int i = 0; i < iters && e == hipSuccess; ++i) e = pfb::launch_mix_copy(in, out, rows, (int)write_ratio, (int)rows_per_wave, nullptr);
-  if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
-  if (e == hipSuccess) e = hipEventSynchronize(e1);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  if (e != hipSuccess) rc = hip_fail(e, "pfb_measure_mix_copy");
-  else *bytes_per_sec = (double)rows * 256.0 * (1.0 + write_ratio) * iters / ((double)ms * 1e-3);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(in);
-  (void)hipFree(out);
-  return rc;
+  return time_copy("pfb_measure_mix_copy", (size_t)rows * 256, (size_t)rows * 256 * write_ratio,
+                   (double)rows * 256.0 * (1.0 + write_ratio), iters, [&](void* in, void* out) {
+                     return pfb::launch_mix_copy(in, out, rows, (int)write_ratio, (int)rows_per_wave, nullptr);
+                   }, bytes_per_sec);
   });
 }
 

@@ -113,7 +113,9 @@ struct FastKernelInfo {
   int magnitude_schedule;  // measured best schedule with PFB_FLAG_MAGNITUDE, -1 = default_schedule
   int threads;             // threads of the plan's FIR workgroup (run-length policy for short calls)
 };
-const FastKernelInfo* find_fast_kernel(int M, int P, int D, int fmt, int variant = 0, bool channel_major = false);
+// (*row, when asked for: the plan's index in the table, what pfb_fast_plan_info takes)
+const FastKernelInfo* find_fast_kernel(int M, int P, int D, int fmt, int variant = 0, bool channel_major = false,
+                                       int* row = nullptr);
 
 hipError_t launch_generic(const KernelParams& p, hipStream_t s);
 hipError_t launch_update_history(const void* old_hist, const void* in, long long n_in, void* new_hist,

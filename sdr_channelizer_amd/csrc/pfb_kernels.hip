@@ -296,10 +296,12 @@ static const FastEntry* fast_row(int index) {
   return nullptr;
 }
 
-const FastKernelInfo* find_fast_kernel(int M, int P, int D, int fmt, int variant, bool channel_major) {
+const FastKernelInfo* find_fast_kernel(int M, int P, int D, int fmt, int variant, bool channel_major, int* row) {
   for (int i = 0; const FastEntry* e = fast_row(i); ++i)
-    if (e->M == M && e->P == P && e->D == D && e->fmt == fmt && (!channel_major || e->info.channel_major_ok) && variant-- == 0)
+    if (e->M == M && e->P == P && e->D == D && e->fmt == fmt && (!channel_major || e->info.channel_major_ok) && variant-- == 0) {
+      if (row) *row = i;
       return &e->info;
+    }
   return nullptr;
 }
 

@@ -1,6 +1,7 @@
 """The fused-kernel table as the library lists it (pfb_fast_plan_count / pfb_fast_plan_info, host only): every row is
 what its name says, the variants of a shape are numbered the way PFB_OPT_VARIANT counts them, every shape is fuzzed,
 and the channel-major route of every plan is the one DESIGN.md names.  No GPU needed."""
+import json
 import os
 import re
 
@@ -110,6 +111,64 @@ def test_launch_report_needs_a_handle():
     assert lib.pfb_last_launch(None, L.C.byref(rep)) == L.PFB_ERR_BAD_ARG
     assert lib.pfb_last_launch(None, None) == L.PFB_ERR_BAD_ARG
     assert L.C.sizeof(L.PfbLaunchReport) == 48 and L.PfbLaunchReport.frames.offset == 24
+
+
+def test_launch_policy_gives_the_recorded_launches(plans):
+    """tests/golden/launch_policy.json: what pfb_last_launch reported on an MI355X (its CU count is in the file) for
+    every row of the table, at the commit named in the file -- the last one whose launch_frames decided the launch in
+    its own body -- over default and forced options at call lengths from one frame to past eight tuned runs per CU.
+    pfb_plan_launch, the function launch_frames now calls, gives every one of those reports field by field; and the
+    recording leaves out no row, none of a row's schedules and neither channel-major route."""
+    with open(os.path.join(ROOT, "tests", "golden", "launch_policy.json")) as f:
+        gold = json.load(f)
+    req_fields, rep_fields = gold["request"], gold["report"]
+    assert req_fields == ["schedule", "frames_per_block", "xcd_remap", "slab_frames", "channel_major", "magnitude"]
+    assert rep_fields == ["fused", "schedule", "frames_per_block", "xcd_remap", "by_slabs", "frames", "runs", "slab_frames"]
+    assert len(gold["parent"]) == 40 and gold["num_cus"] > 0
+    index = {d.name.decode(): i for i, d in enumerate(plans)}
+    assert set(gold["rows"]) == set(index)
+    nreq, played, entries = len(req_fields), set(), 0
+    for name, rows in gold["rows"].items():
+        d, seen, slabs = plans[index[name]], set(), set()
+        for e in rows:
+            assert len(e) == nreq + 1 + len(rep_fields), name
+            req, frames, want = dict(zip(req_fields, e[:nreq])), e[nreq], dict(zip(rep_fields, e[nreq + 1:]))
+            rep = L.plan_launch(index[name], frames, gold["num_cus"], **req)
+            assert {f: getattr(rep, f) for f in rep_fields} == want and rep.reserved == 0, (name, req, frames)
+            assert want["fused"] == 1 and want["frames"] == frames, (name, req, frames)
+            seen.add(want["schedule"])
+            slabs.add(want["by_slabs"])
+            played.add(req["schedule"])
+        entries += len(rows)
+        # the row's own schedules, every schedule a frame-major handle can be forced to, and both routes
+        own = {d.default_schedule} | ({d.magnitude_schedule} if d.magnitude_schedule >= 0 else set())
+        assert seen >= own | {0, 2, 3, 4, 6, 7, 11, 13}, (name, seen)
+        assert seen >= ({-1, 8} if d.channel_major_ok else set()), (name, seen)   # the fused channel-major launches
+        assert slabs == {0, 1}, name
+    assert played == set(SCHEDULES) | {9}
+    print(f"{entries} recorded launches on {gold['num_cus']} CUs at {gold['parent'][:7]}")
+
+
+def test_plan_launch_rejects_bad_arguments():
+    lib = L.load()
+    rq = L.PfbLaunchRequest(L.C.sizeof(L.PfbLaunchRequest), -1, 0, -1, 0, 0, 256, 0)
+    rep = L.PfbLaunchReport()
+    n = lib.pfb_fast_plan_count()
+    assert lib.pfb_plan_launch(0, None, 100, L.C.byref(rep)) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_plan_launch(0, L.C.byref(rq), 100, None) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_plan_launch(n, L.C.byref(rq), 100, L.C.byref(rep)) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_plan_launch(-1, L.C.byref(rq), 100, L.C.byref(rep)) == L.PFB_ERR_BAD_ARG
+    for size in (0, L.C.sizeof(L.PfbLaunchRequest) - 8, L.C.sizeof(L.PfbLaunchRequest) + 8):
+        rq.struct_size = size
+        assert lib.pfb_plan_launch(0, L.C.byref(rq), 100, L.C.byref(rep)) == L.PFB_ERR_BAD_ARG
+    rq.struct_size = L.C.sizeof(L.PfbLaunchRequest)
+    assert lib.pfb_plan_launch(n - 1, L.C.byref(rq), 100, L.C.byref(rep)) == L.PFB_OK
+    assert rep.fused == 1 and rep.frames == 100 and rep.runs == -(-100 // rep.frames_per_block)
+    assert lib.pfb_plan_launch(0, L.C.byref(rq), 0, L.C.byref(rep)) == L.PFB_OK and rep.runs == 0   # no frames, no runs
+    rq.channel_major, rq.schedule = 1, 9
+    assert lib.pfb_plan_launch(0, L.C.byref(rq), 0, L.C.byref(rep)) == L.PFB_OK and rep.runs == 0 and rep.by_slabs == 1
+    # the mirror has the header's layout: a uint32 and six ints, then the int64 on its own 8 bytes
+    assert L.C.sizeof(L.PfbLaunchRequest) == 40 and L.PfbLaunchRequest.slab_frames.offset == 32
 
 
 def test_every_shape_is_fuzzed(plans):
