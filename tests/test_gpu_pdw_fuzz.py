@@ -26,6 +26,9 @@ def pulses_into(rng, x, amp_lo, amp_hi):
 
 @pytest.mark.parametrize("case", range(CASES))
 def test_channelized_pdws_random(oracle, case):
+    """Pulses are drawn up to F / 8 frames, under 375: they stay below kPulseCache (512) and so, unless several overlap, never
+    leave the counting median.  The routes above it (the select over memory, its tie branches, the lengths on the thresholds themselves) are
+    walked on designed data by test_gpu_pdw_branches.py."""
     rng = np.random.default_rng(7000 + case)
     F, M = int(rng.integers(2, 3000)), int(rng.integers(1, 70))
     y = 0.01 * (rng.standard_normal((F, M)) + 1j * rng.standard_normal((F, M)))
