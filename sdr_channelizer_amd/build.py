@@ -16,7 +16,8 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libpfb_channelizer.so")
 SOURCES = ["pfb_api.cpp", "pfb_stft_api.cpp", "pfb_host.cpp", "pfb_kernels.hip", "pfb_kernels_mid.hip", "pfb_kernels_big.hip", "pfb_kernels_mixed.hip", "pfb_pdw.hip", "pfb_stft.hip", "iq_packet.c"]
-HEADERS = ["pfb_common.h", "pfb_host.h", "pfb_launch_policy.h", "pfb_fast.hpp", "pfb_generic_fft.hpp", "pfb_table.h"]
+# every header under csrc/: one that a hand-kept list misses would let a stale library pass for current
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hpp")))
 ARCH = "gfx950"
 PUBLIC_HEADERS = ["pfb_channelizer.h", "pfb_channelizer_dev.h", "pfb_iq_packet.h"]
 

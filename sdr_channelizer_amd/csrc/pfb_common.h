@@ -36,7 +36,7 @@ struct KernelParams {
   const float* taps;       // M*P taps, pre-scaled by 2^-(bit_width-1) (exact)
   const float2* tw;        // tw[m] = exp(+j 2 pi m / M), m = 0..M-1 (from float64)
   const float* taps_lane;  // fast kernels: taps_lane[c][j] = taps[(D-1-c) + D*j], rows padded to float4s
-  const float2* tw_lane;   // fast kernels: inter-pass twiddle rows, see pfb_fast.hpp
+  const float2* tw_lane;   // fast kernels: inter-pass twiddle rows, see pfb_fast_cfg.hpp
   long long n_in;          // samples in `in`
   long long frames;        // frames to produce
   long long frame0;        // global index of local frame 0 (PFB_FLAG_DEROTATE)

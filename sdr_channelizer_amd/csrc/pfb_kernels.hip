@@ -1,6 +1,6 @@
 // pfb_kernels.hip -- gfx950 kernels of the channelizer library and their launchers.
 //
-//   pfb_fast_kernel<...>   the hot path (pfb_fast.hpp), one instantiation per
+//   pfb_fast_kernel<...>   the hot path (pfb_fast.hpp and the pfb_fast_*.hpp it lists), one instantiation per
 //                          (M, P, D, sample format) in kFastTable below
 //   pfb_generic_kernel     any M (2^k by radix-2 in LDS, 2^a 3^b 5^c 7^d by a run-time mixed-radix
 //                          Stockham FFT, otherwise a plain DFT),

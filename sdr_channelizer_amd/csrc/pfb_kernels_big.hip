@@ -25,7 +25,7 @@ using Cfg560x12i8 =
 // cfg4, team plan (the default): 512 FIR threads x 2 columns filter chunks of 4 frames and run the last pass
 // + stores of the chunk before the previous one; 4 FFT waves take one frame each for the first two passes
 // (16 x 16 x 4, wave-local, twiddles in registers); 12 waves per workgroup, three LDS chunk buffers, one
-// workgroup barrier per chunk (pfb_fast.hpp, schedule T)
+// workgroup barrier per chunk (pfb_fast_teams.hpp, schedule T)
 using Cfg1024x16i16t =
     FastCfg<1024, 16, 1024, 2, PFB_FMT_INT16_IQ, 4, 3, 16, 16, 4, 64, 68, 260, 1088, false, 3, false>;
 // M = 560, team plan (the default): 280 FIR threads x 2 columns (5 waves) + 4 FFT waves, chunks of 4 frames,
@@ -49,7 +49,7 @@ using Cfg560x12i8t2 =
 using Cfg560x12f32 = FastCfg<560, 12, 560, 1, PFB_FMT_CF32, 7, 3, 10, 8, 7, 56, 71, 82, 600, false, 3, true>;
 using Cfg1024x16f32b = FastCfg<1024, 16, 1024, 1, PFB_FMT_CF32, 8, 3, 8, 8, 16, 128, 128, 65, 1040, false, 1, true>;
 
-// cfg4, schedule W (pfb_fast.hpp): independent workgroups whose waves filter their columns and then transform whole
+// cfg4, schedule W (pfb_fast_twin.hpp): independent workgroups whose waves filter their columns and then transform whole
 // frames by themselves; the window stays packed (raw int16 pairs).  Three shapes of it:
 //   twin    512 threads x 2 columns, chunks of 8 frames (one per wave), 128 registers, 78 KB of LDS: 2 workgroups per CU
 //   triple  256 threads x 4 columns (16-byte loads), chunks of 4 frames, 168 registers, 44 KB: 3 workgroups per CU

@@ -58,7 +58,7 @@ static const FastEntry kRows[] = {
     // schedule 11 (sliding runs, the next chunk's FIR scheduled into this chunk's FFT, rows two chunks ahead) over short
     // runs: cfg5 1.125 -> 1.048 ms per 2^28 samples (59.6 -> 64.0 % of roofline), cfg3 2.104 -> 2.073 ms (63.8 -> 64.8 %)
     entry<Cfg128x12os2i16>("pfb_fast<M128,P12,D64,int16>", 32, 11),
-    // cfg3: schedule 0 again -- once its loop kept the compiler's wait counts exact (FastKernel::run_impl) it read 0.68
+    // cfg3: schedule 0 again -- once its loop kept the compiler's wait counts exact (SlidingRun::run_impl, pfb_fast_sliding.hpp) it read 0.68
     // against 0.64 for schedule 11, whose 4-column register budget spills inside the chunk loop
     entry<Cfg256x8i8>("pfb_fast<M256,P8,D256,int8>", 32, 0),
     entry<Cfg256x8i16>("pfb_fast<M256,P8,D256,int16>", 32, 0),

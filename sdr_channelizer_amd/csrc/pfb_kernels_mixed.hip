@@ -5,10 +5,10 @@
 // /root/reference/matlab/channelizer_example.m:29, create_pdws_channelized.m:31) or in units of 0.1 MHz
 // (generate_channelized_training_iq.m:95-96): 12, 24, 25, 30, 48, 50, 80, 96, 100, 112, 120, 160, 200, 250, 280, 320,
 // 400, 500, 512 besides the shapes of the other tables.  All of them are instantiations of the same templates as the
-// tuned shapes (pfb_fast.hpp), with radices from {2 .. 16 \ 9, 11, 13, 15} and the LDS paddings
+// tuned shapes (pfb_fast_core.hpp), with radices from {2 .. 16 \ 9, 11, 13, 15} and the LDS paddings
 // tools/fft_plan_search.py picks (modelled bank conflicts minimal, last radix small so that the final pass stores long
 // runs of adjacent channels):
-//   M < 64           SegKernel: 64 / M segments of the run per wave, two passes
+//   M < 64           SegKernel (pfb_fast_seg.hpp): 64 / M segments of the run per wave, two passes
 //   64 < M <= 160    one wave (two in lockstep at M = 160), 2 adjacent columns per lane, two passes
 //   M >= 200         4-5 waves in lockstep, 1-2 columns per lane, three passes in place, twiddles from the table
 // 12 taps per band (dsp.Channelizer's default, the only value the reference uses); shorter prototypes are zero-padded

@@ -10,14 +10,14 @@
 //          buffer, converted to float and kept in LDS -- overlapping frames read their shared samples from LDS, not
 //          from HBM.
 //   FFT    Stockham passes of compile-time radix (R0 x R1 [x R2]), each butterfly an in-register Dft<R> of
-//          pfb_fast.hpp with one LDS exchange between passes.  The first pass reads the span, multiplies by the window
+//          pfb_cplx.hpp with one LDS exchange between passes.  The first pass reads the span, multiplies by the window
 //          table (window x 2^-(bw-1), one float per point) and supplies the zero padding n >= L.  Dft<R> is the
 //          e^{+j} kernel: the span is stored with re and im swapped and every result is read back swapped,
 //          DFT-(x) = swap(DFT+(swap(x))), so the e^{-j} transform costs nothing.
 //   STORE  the row rotation ('centered' or FFT order) is applied while reading the last pass's buffer, so every frame
 //          leaves as consecutive 16-byte-per-lane stores (the tile's T * nfft outputs are one contiguous run).
 // LDS: two T x nfft complex buffers (the span, at most T L <= T nfft samples, lives in the first), 32-36 KiB.
-#include "pfb_fast.hpp"
+#include "pfb_cplx.hpp"
 #include "pfb_generic_fft.hpp"
 
 namespace pfb {

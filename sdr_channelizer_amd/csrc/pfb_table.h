@@ -1,4 +1,5 @@
-// pfb_table.h -- one row of the fused-kernel table; the table is split over four translation units
+// pfb_table.h -- one row of the fused-kernel table (launch_fast: pfb_fast.hpp, launch_seg: pfb_fast_seg.hpp, init_tables:
+// pfb_fast_cfg.hpp); the table is split over four translation units
 // (pfb_kernels.hip: M = 64; pfb_kernels_mid.hip: the other tuned single-wave shapes; pfb_kernels_big.hip: M = 1024 and
 // 560; pfb_kernels_mixed.hip: the other plausible radio rates, M = 2^a 3^b 5^c 7^d) so that they compile in parallel.
 #pragma once
@@ -15,7 +16,7 @@ constexpr FastEntry entry(const char* name, int default_fpb, int default_schedul
                                   default_fpb, K::CPT, default_schedule, kChannelMajorOk<K>, kMagnitudeSchedule<K>, K::NT}};
 }
 
-// small banks: SegKernel, 64 / M segments of the run per wave; frames_per_block is a multiple of C * SEG
+// small banks: SegKernel (pfb_fast_seg.hpp), 64 / M segments of the run per wave; frames_per_block is a multiple of C * SEG
 template <class K>
 constexpr FastEntry seg_entry(const char* name, int default_fpb) {
   return FastEntry{K::M, K::P, K::D, K::FMT,

@@ -14,7 +14,7 @@ FMT = {"int8": L.PFB_FMT_INT8_IQ, "int16": L.PFB_FMT_INT16_IQ, "cf32": L.PFB_FMT
 NAME_RE = re.compile(r"pfb_fast<M(\d+),P(\d+),D(\d+),(int8|int16|cf32)(?:,(\w+))?>")
 # every value pfb_set_option(PFB_OPT_SCHEDULE) accepts except 9 (channel-major by slabs, a route rather than a schedule)
 SCHEDULES = (-1, 0, 2, 3, 4, 6, 7, 8, 11, 13)
-# the plans a channel-major handle runs by frame-major slabs + the transpose kernel (kChannelMajorOk in pfb_fast.hpp):
+# the plans a channel-major handle runs by frame-major slabs + the transpose kernel (kChannelMajorOk next to launch_fast in pfb_fast.hpp):
 # the 16-wave plans and the three-pass plans on chunks of 4 or 2 frames, whose fused stores would be 32- / 16-byte runs
 SLAB_PLANS = {
     "pfb_fast<M1024,P16,D1024,int16>", "pfb_fast<M1024,P16,D1024,int16,16w>",
