@@ -370,6 +370,83 @@ int pfb_pdw_last_noise_floor_path(void);
  * serialised on it).  This frees it: device_id >= 0 for one device, < 0 for all. */
 int pfb_pdw_release_workspace(int32_t device_id);
 
+/* ---- dwell analysis and event prediction -------------------------------------------------------
+ * The last layer of the reference: capture a dwell, find its pulses, fit the SNR-vs-TOA parabola, schedule
+ * the next capture (matlab/predict_event.m:53-138, cpp/usrp_predict_event.cpp:285-375), plus the gain finders'
+ * saturation scan (cpp/usrp_find_max_unsaturated_gain.cpp:146, cpp/blade_find_max_unsaturated_gain.cpp:268).
+ * x = (I + jQ) / 2^(bit_width-1) (predict_event.m:48-51; cf32 as is).  With i0 and j the 0-based leading and
+ * trailing sample of a pulse, both statistics share:
+ *   noise floor NF, threshold NF*10^(snr_threshold_db/10) (m:64-66, cpp:289-291); leading edge |x| >= thr,
+ *   trailing edge |x| <= thr (m:76,82, cpp:306,316); snr = 10*log10(amp/NF) (m:93, cpp:329); pw = (j - i0)/fs
+ *   (m:98); sat from the samples strictly inside the pulse with |I| or |Q| >= 0.9999 (m:118, cpp:336); bin = 0;
+ *   a pulse still active at the end of the buffer gives no PDW; *count is the number found, even beyond
+ *   `capacity` (only `capacity` are written).
+ * PFB_DWELL_STAT_MEDIAN (predict_event.m:64-121): NF = median |x| (:64), amp = median of |x| over i0..j
+ *   inclusive (:89), toa = (i0+1)/fs + sample_start_time (:86, 1-based), freq as create_pdws.m (:102-110).
+ *   Bit-identical to pfb_pdw_extract_raw with trailing_threshold_db == snr_threshold_db: it is that code.
+ * PFB_DWELL_STAT_MEAN (usrp_predict_event.cpp:287-343): NF = mean |x| (:288-289), amp = (sum of |x_i| over
+ *   i0 <= i < j)/(j - i0) (:311,334,325: the trailing sample is not in the sum), toa = i0/fs + sample_start_time
+ *   (:321, 0-based), freq = fc + fs/(360/median wrapped phase step of i0..j) as the other extractors compute it
+ *   (the C++ loop has none), or NaN with PFB_DWELL_SKIP_FREQ.  Arithmetic is float64: the reference's float32
+ *   cwiseAbs()/mean() (:288-289) is NOT reproduced.  The sums are taken in a fixed order, so the same buffer
+ *   gives the same bits on every call.
+ * pfb_dwell_stats comes from one pass over the buffer; with full = 2^(bit_width-1):
+ *   saturated_components  the I and Q components c (raw integers, compared in double) with
+ *                         c <= sat_fraction*(-full) or c >= sat_fraction*(full-1): the gain finders' test; for
+ *                         cf32 the limits are -sat_fraction and +sat_fraction
+ *   mean_mag, peak_mag    mean and max of |x|; peak_mag is what predict_event.m:53 gates on (> 0.9)
+ *   peak_component        max of |I|/full, |Q|/full
+ *   noise_floor, threshold the ones the edges used; pulses = *count
+ *   any_pulse_saturated   OR of sat over the PDWs written (the first min(*count, capacity))
+ * `iq` is host or device memory per cfg->mem; `out` and `stats` are host memory.  Every argument is validated
+ * before the device is touched: PFB_ERR_BAD_ARG for a null cfg / iq / count / stats (or out with capacity > 0),
+ * a wrong struct_size, num_samples < 2, bit_width outside 1..16 for the integer formats, an unknown
+ * sample_format, statistic, flag or mem, sat_fraction outside [0, 1], a non-finite fs or threshold; then
+ * PFB_ERR_NO_DEVICE without a HIP device.  Shares the PDW extractors' device scratch
+ * (pfb_pdw_release_workspace) and error text (pfb_pdw_last_error_detail). */
+enum { PFB_DWELL_STAT_MEAN = 0, PFB_DWELL_STAT_MEDIAN = 1 };
+enum { PFB_DWELL_SKIP_FREQ = 1u << 0 };   /* freq = NaN, no phase work: the live loop reads toa and snr only */
+
+typedef struct pfb_dwell_config {
+  uint32_t struct_size;    /* = sizeof(pfb_dwell_config)                                        */
+  uint32_t sample_format;  /* pfb_sample_format                                                 */
+  uint32_t bit_width;      /* 1..16: scale 2^-(bit_width-1); ignored for CF32                   */
+  uint32_t statistic;      /* PFB_DWELL_STAT_*                                                  */
+  uint32_t flags;          /* PFB_DWELL_SKIP_FREQ (MEAN only; MEDIAN ignores it)                */
+  uint32_t mem;            /* PFB_MEM_HOST / PFB_MEM_DEVICE for `iq`                            */
+  int32_t device_id;       /* HIP device ordinal, -1 = current device                           */
+  double fs, fc, sample_start_time;
+  double snr_threshold_db; /* both sources: 20 (m:65, cpp:290)                                  */
+  double sat_fraction;     /* gain finders: 0.98; 0 = 0.98                                      */
+} pfb_dwell_config;
+
+typedef struct pfb_dwell_stats {
+  uint64_t num_samples, saturated_components, pulses;
+  double mean_mag, peak_mag, peak_component;
+  double noise_floor, threshold;
+  int32_t any_pulse_saturated, reserved;
+} pfb_dwell_stats;
+
+int pfb_dwell_analyze(const pfb_dwell_config* cfg, const void* iq, uint64_t num_samples, pfb_pdw* out,
+                      uint64_t capacity, uint64_t* count, pfb_dwell_stats* stats, void* hip_stream);
+/* One record from disk: its header supplies sample format, bit width, fs, fc and start time (overriding cfg's);
+ * the payload is loaded as pfb_pdw_raw_from_iq_file loads it; cfg->mem is ignored. */
+int pfb_dwell_from_iq_file(const char* path, const pfb_dwell_config* cfg, pfb_pdw* out, uint64_t capacity,
+                           uint64_t* count, pfb_dwell_stats* stats, pfb_iq_info* info_out);
+/* Host only.  Least-squares quadratic of snr against toa (predict_event.m:125-130 polyfit,
+ * usrp_predict_event.cpp:28-52 householderQr), solved by Householder QR in double on tau = toa - toa[0]: raw
+ * UTC seconds squared are not representable well enough, and the peak is translation-invariant.
+ * coef = [p0, p1, p2] of p0 + p1*tau + p2*tau^2; *t_peak = toa[0] - p1/(2*p2) (m:129, cpp:51), *snr_peak the
+ * parabola there (m:130).  n < 3 or a null pointer: PFB_ERR_BAD_ARG.  A fit that is not concave or not finite
+ * (p2 >= 0, rank-deficient abscissae): PFB_ERR_UNSUPPORTED with coef filled.  The reference's own gate,
+ * toaList.size() > 10 (cpp:348), is the caller's. */
+int pfb_event_fit(const pfb_pdw* pdws, uint64_t n, double* t_peak, double* snr_peak, double coef[3]);
+/* Host only.  Next event from the event times so far.  convention 0 (predict_event.m:134-138): next = last +
+ * median(diff) with MATLAB's median (mean of the middle two for an even count), *have_next = 0 when n < 2 (the
+ * script's hard-coded first period is the caller's business).  convention 1 (usrp_predict_event.cpp:354-372): only
+ * when n > 5, the median is sorted_diff[size/2].  Other conventions: PFB_ERR_BAD_ARG. */
+int pfb_event_next(const double* event_times, uint64_t n, uint32_t convention, double* next, int32_t* have_next);
+
 
 /* ---- short-time Fourier transform of an I/Q stream --------------------------------------------
  * Replaces the spectrogram lines of the reference scripts:

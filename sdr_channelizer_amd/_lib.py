@@ -36,6 +36,8 @@ PFB_OPT_SLAB_FRAMES = 11
 PFB_STFT_COMPLEX, PFB_STFT_POWER, PFB_STFT_DB = 0, 1, 2
 PFB_STFT_CENTERED, PFB_STFT_TWOSIDED = 0, 1
 PFB_STFT_KERNEL_AUTO, PFB_STFT_KERNEL_GENERIC, PFB_STFT_KERNEL_FUSED = 0, 1, 2
+PFB_DWELL_STAT_MEAN, PFB_DWELL_STAT_MEDIAN = 0, 1
+PFB_DWELL_SKIP_FREQ = 1
 
 
 class PfbConfig(C.Structure):
@@ -69,6 +71,23 @@ class PfbIqPacket(C.Structure):
 class PfbPdw(C.Structure):
     _fields_ = [("toa", C.c_double), ("freq", C.c_double), ("pw", C.c_double), ("snr", C.c_double),
                 ("sat", C.c_int32), ("bin", C.c_int32), ("mag", C.c_double)]
+
+
+class PfbDwellConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("sample_format", C.c_uint32), ("bit_width", C.c_uint32), ("statistic", C.c_uint32),
+        ("flags", C.c_uint32), ("mem", C.c_uint32), ("device_id", C.c_int32), ("fs", C.c_double), ("fc", C.c_double),
+        ("sample_start_time", C.c_double), ("snr_threshold_db", C.c_double), ("sat_fraction", C.c_double),
+    ]
+
+
+class PfbDwellStats(C.Structure):
+    _fields_ = [
+        ("num_samples", C.c_uint64), ("saturated_components", C.c_uint64), ("pulses", C.c_uint64),
+        ("mean_mag", C.c_double), ("peak_mag", C.c_double), ("peak_component", C.c_double),
+        ("noise_floor", C.c_double), ("threshold", C.c_double), ("any_pulse_saturated", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
 
 
 class PfbFastPlanDesc(C.Structure):
@@ -128,6 +147,7 @@ EXPORTS = (
     "pfb_stft_create", "pfb_stft_destroy", "pfb_stft_reset", "pfb_stft_set_stream", "pfb_stft_process",
     "pfb_stft_process_async", "pfb_stft_sync", "pfb_stft_frames_for", "pfb_stft_process_iq_file", "pfb_stft_axes",
     "pfb_stft_last_kernel", "pfb_stft_get_device",
+    "pfb_dwell_analyze", "pfb_dwell_from_iq_file", "pfb_event_fit", "pfb_event_next",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -237,6 +257,13 @@ def load() -> C.CDLL:
     lib.pfb_stft_last_kernel.argtypes = [vp]
     lib.pfb_stft_last_kernel.restype = C.c_char_p
     lib.pfb_stft_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_dwell_analyze.argtypes = [C.POINTER(PfbDwellConfig), vp, u64, C.POINTER(PfbPdw), u64, C.POINTER(u64),
+                                      C.POINTER(PfbDwellStats), vp]
+    lib.pfb_dwell_from_iq_file.argtypes = [C.c_char_p, C.POINTER(PfbDwellConfig), C.POINTER(PfbPdw), u64, C.POINTER(u64),
+                                           C.POINTER(PfbDwellStats), C.POINTER(PfbIqInfo)]
+    lib.pfb_event_fit.argtypes = [C.POINTER(PfbPdw), u64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double)]
+    lib.pfb_event_next.argtypes = [C.POINTER(C.c_double), u64, u32, C.POINTER(C.c_double), C.POINTER(i32)]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]

@@ -640,6 +640,26 @@ int pfb_pdw_from_iq_file(pfb_handle* h, const char* path, double snr_threshold_d
   });
 }
 
+namespace {
+
+// The payload of an open record into a new device buffer, on a new stream: 64 MB chunks through the record reader's
+// page-locked buffers.  The caller destroys *st and frees *d_iq whatever comes back.
+int record_to_device(pfb::Record& rec, void** d_iq, hipStream_t* st, const char* what) {
+  const uint64_t n = rec.info.packet.numSamples;
+  const size_t bps = rec.info.bytes_per_sample;
+  if (hipMalloc(d_iq, n * bps) != hipSuccess || hipStreamCreate(st) != hipSuccess) {
+    (void)hipGetLastError();
+    return PFB_ERR_NO_MEMORY;
+  }
+  return rec.read(((uint64_t)64 << 20) / bps, [&](const char* buf, uint64_t first, uint64_t m) {
+    const hipError_t e = hipMemcpyAsync(static_cast<char*>(*d_iq) + first * bps, buf, m * bps, hipMemcpyHostToDevice, *st);
+    const hipError_t e2 = hipStreamSynchronize(*st);
+    return (e != hipSuccess || e2 != hipSuccess) ? hip_fail(e != hipSuccess ? e : e2, what) : (int)PFB_OK;
+  });
+}
+
+}  // namespace
+
 int pfb_pdw_raw_from_iq_file(const char* path, double snr_threshold_db, double trailing_threshold_db, pfb_pdw* out,
                              uint64_t capacity, uint64_t* count, double* noise_floor_out, pfb_iq_info* info_out,
                              int32_t device_id) {
@@ -655,27 +675,51 @@ int pfb_pdw_raw_from_iq_file(const char* path, double snr_threshold_db, double t
   const pfb_iq_info& info = rec.info;
   DeviceGuard g(dev);
   const uint64_t n = info.packet.numSamples;
-  const size_t bps = info.bytes_per_sample;
   if (n == 0) return PFB_ERR_BAD_ARG;
-  // the record goes to the device in 64 MB chunks through the record reader's page-locked buffers; the extraction
-  // then runs on the device-resident stream
+  // the record goes to the device; the extraction then runs on the device-resident stream
   void* d_iq = nullptr;
   hipStream_t st = nullptr;
-  if (hipMalloc(&d_iq, n * bps) != hipSuccess || hipStreamCreate(&st) != hipSuccess) rc = PFB_ERR_NO_MEMORY;
-  if (rc == PFB_OK) {
-    rc = rec.read(((uint64_t)64 << 20) / bps, [&](const char* buf, uint64_t first, uint64_t m) {
-      const hipError_t e = hipMemcpyAsync(static_cast<char*>(d_iq) + first * bps, buf, m * bps, hipMemcpyHostToDevice, st);
-      const hipError_t e2 = hipStreamSynchronize(st);
-      return (e != hipSuccess || e2 != hipSuccess) ? hip_fail(e != hipSuccess ? e : e2, "pfb_pdw_raw_from_iq_file")
-                                                   : (int)PFB_OK;
-    });
-  } else {
-    (void)hipGetLastError();
-  }
+  rc = record_to_device(rec, &d_iq, &st, "pfb_pdw_raw_from_iq_file");
   if (rc == PFB_OK)
     rc = pfb_pdw_extract_raw(d_iq, n, info.sample_format, info.packet.bitWidth, (double)info.packet.sampleRateSps,
                              (double)info.packet.frequencyHz, info.packet.sampleStartTime, snr_threshold_db,
                              trailing_threshold_db, out, capacity, count, noise_floor_out, PFB_MEM_DEVICE, dev, st);
+  if (st) (void)hipStreamDestroy(st);
+  (void)hipFree(d_iq);
+  return rc;
+  });
+}
+
+int pfb_dwell_from_iq_file(const char* path, const pfb_dwell_config* cfg, pfb_pdw* out, uint64_t capacity, uint64_t* count,
+                           pfb_dwell_stats* stats, pfb_iq_info* info_out) {
+  return pfb::abi_guard([&]() -> int {
+  if (!path || !count || !stats || (capacity > 0 && !out)) return PFB_ERR_BAD_ARG;
+  int rc = pfb::dwell_check_config(cfg, true);
+  if (rc != PFB_OK) return rc;
+  int dev = 0;
+  rc = pfb::resolve_device(cfg->device_id, &dev);
+  if (rc != PFB_OK) return rc;
+  pfb::Record rec;
+  rc = rec.open(path);
+  if (info_out) *info_out = rec.info;
+  if (rc != PFB_OK) return rc;
+  const pfb_iq_info& info = rec.info;
+  DeviceGuard g(dev);
+  const uint64_t n = info.packet.numSamples;
+  if (n < 2) return PFB_ERR_BAD_ARG;
+  // the payload goes to the device as in pfb_pdw_raw_from_iq_file; the record's header overrides the config
+  pfb_dwell_config c = *cfg;
+  c.sample_format = info.sample_format;
+  c.bit_width = info.packet.bitWidth;
+  c.fs = (double)info.packet.sampleRateSps;
+  c.fc = (double)info.packet.frequencyHz;
+  c.sample_start_time = info.packet.sampleStartTime;
+  c.mem = PFB_MEM_DEVICE;
+  c.device_id = dev;
+  void* d_iq = nullptr;
+  hipStream_t st = nullptr;
+  rc = record_to_device(rec, &d_iq, &st, "pfb_dwell_from_iq_file");
+  if (rc == PFB_OK) rc = pfb_dwell_analyze(&c, d_iq, n, out, capacity, count, stats, st);
   if (st) (void)hipStreamDestroy(st);
   (void)hipFree(d_iq);
   return rc;

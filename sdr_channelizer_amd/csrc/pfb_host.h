@@ -38,6 +38,10 @@ struct DeviceGuard {  // run on the handle's device, restore the caller's afterw
 // PFB_ERR_BAD_ARG for an ordinal past the last device.
 int resolve_device(int requested, int* dev);
 
+// What pfb_dwell_analyze and pfb_dwell_from_iq_file check of their config before the device is touched (pfb_event.cpp);
+// from_file: sample format, bit width, fs and mem come from the record, not from the config.
+int dwell_check_config(const pfb_dwell_config* cfg, bool from_file);
+
 // pfb_*_set_stream: what the old stream still has queued for the handle comes first on the new one
 int switch_stream(int device, hipStream_t* stream, hipEvent_t* ev_switch, hipStream_t next);
 

@@ -22,7 +22,8 @@
 //
 // The raw-stream script (matlab/create_pdws.m:30-105, pfb_pdw_extract_raw) shares the edge and pulse stages; its
 // one column makes the noise floor a time-parallel radix select whose leading digits are predicted from a small
-// sample and proven by the first counting pass, and its masks a comparison of integer keys.
+// sample and proven by the first counting pass, and its masks a comparison of integer keys.  The dwell analysis of the
+// event predictor (pfb_dwell_analyze, pfb_dwell.hpp, included at the end) runs on the same sources, masks and edge stage.
 //
 // Arithmetic is float64 like the MATLAB scripts: everything that decides an outcome is computed on the exact float64
 // |y|^2 (float32 only screens what cannot matter).
@@ -34,6 +35,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pfb_common.h"  // abi_guard, launch_transpose_slab (pfb_kernels.hip)
@@ -1369,6 +1371,7 @@ struct ChanSrc {  // F x M channelizer output, frame-major complex64
 template <int FMT>
 struct RawSrc {
   static constexpr int kCache = kPulseCacheRaw;
+  static constexpr int kFmt = FMT;
   static constexpr int kThreads = 512;  // 256: 0.84 ms for 4794 pulses of 5600 samples, 512: 0.66, 1024: 1.09 (one workgroup per CU)
   const void* p;
   double inv_scale;  // 2^-(bit_width-1); 1 for cf32
@@ -1853,8 +1856,12 @@ EdgeStage take_edge_stage(Arena& ws, long long words, long long ntiles, uint32_t
 // d_check / h_check / h_nf (optional): flags of an optimistic noise-floor pass and its medians, fetched with the edge
 // totals in the one sync; if the flags say the medians are not valid (bits 1 | 2) the function stops there and
 // returns kRedo so that the caller can take the slow path and call again.
+// Pulse: what runs per pulse.  MedianPulse is the scripts' pdw_pulse_kernel; any other tag launches its own kernel
+// through Pulse::launch (pfb_dwell.hpp: the live loop's mean amplitude).  `flags` goes to that stage as it is:
+// PFB_PDW_* for MedianPulse, PFB_DWELL_* for the dwell analysis.
 constexpr int kRedo = 1;
-template <class Src>
+struct MedianPulse {};
+template <class Src, class Pulse = MedianPulse>
 int edges_and_pulses(Src src, int Mi, long long ntiles, int tile_words, const EdgeStage& e, Arena& ws2, double fs, double fc, double t0,
                      unsigned flags, pfb_pdw* out, uint64_t capacity, uint64_t* count, hipStream_t st,
                      const unsigned* d_check = nullptr, unsigned* h_check = nullptr, double* h_nf = nullptr) {
@@ -1927,9 +1934,14 @@ int edges_and_pulses(Src src, int Mi, long long ntiles, int tile_words, const Ed
                          (const unsigned long long*)e.off_s, (const unsigned long long*)e.off_e, d_starts, d_ends);
     }
     if (n_out > 0) {
-      hipLaunchKernelGGL((pdw_pulse_kernel<Src, Src::kCache, Src::kThreads>), dim3((unsigned)n_out), dim3(Src::kThreads), 0, st, src, Mi, (const long long*)d_starts,
-                         (const long long*)d_ends, (const unsigned long long*)e.base, (const unsigned long long*)(e.base + M),
-                         (const double*)e.nf, (const double*)e.binf, fs, fc, t0, flags, d_out, n_out);
+      if constexpr (std::is_same_v<Pulse, MedianPulse>) {
+        hipLaunchKernelGGL((pdw_pulse_kernel<Src, Src::kCache, Src::kThreads>), dim3((unsigned)n_out), dim3(Src::kThreads), 0, st, src, Mi, (const long long*)d_starts,
+                           (const long long*)d_ends, (const unsigned long long*)e.base, (const unsigned long long*)(e.base + M),
+                           (const double*)e.nf, (const double*)e.binf, fs, fc, t0, flags, d_out, n_out);
+      } else {  // one column: pulse k runs from d_starts[k] to d_ends[k]
+        Pulse::launch(src, (const long long*)d_starts, (const long long*)d_ends, (const double*)e.nf, fs, fc, t0, flags, d_out,
+                      n_out, st);
+      }
       PDW_TRY(hipGetLastError());
       PDW_TRY(hipMemcpyAsync(out, d_out, (size_t)n_out * sizeof(pfb_pdw), hipMemcpyDeviceToHost, st));
     }
@@ -2160,6 +2172,36 @@ extern "C" int pfb_pdw_extract(const void* y_in, uint64_t frames, uint32_t M, ui
 
 namespace {
 
+// comparison masks of the raw stream at the magnitudes `lead` and `trail`.  The thresholds as keys: the first key whose
+// magnitude is >= lead / > trail, found with the float64 operations the device's key_mag uses
+template <int FMT>
+void launch_raw_masks(const RawSrc<FMT>& src, long long n, double inv_scale, double lead, double trail, bool vec,
+                      const EdgeStage& e, long long words, hipStream_t st) {
+  auto key_mag = [&](unsigned long long k) {
+    return (FMT == PFB_FMT_CF32) ? std::sqrt(dkey_inv_host(k)) : std::sqrt((double)k) * inv_scale;
+  };
+  const unsigned long long k_lo = (FMT == PFB_FMT_CF32) ? 0x8000000000000000ull : 0ull;               // |x|^2 = 0
+  const unsigned long long k_hi = (FMT == PFB_FMT_CF32) ? 0xFFF0000000000000ull : (1ull << 33);       // +inf / above any sample
+  auto first_key = [&](auto pred) {  // smallest key in [k_lo, k_hi] that passes, k_hi + 1 if none (pred is monotone)
+    if (!pred(k_hi)) return k_hi + 1;
+    unsigned long long lo = k_lo, hi = k_hi;  // invariant: pred(hi)
+    while (lo < hi) {
+      const unsigned long long mid = lo + (hi - lo) / 2;
+      if (pred(mid)) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+  };
+  const unsigned long long key_ge = first_key([&](unsigned long long k) { return key_mag(k) >= lead; });
+  const unsigned long long key_gt = first_key([&](unsigned long long k) { return key_mag(k) > trail; });
+  if (vec) {
+    hipLaunchKernelGGL((pdw_raw_mask_kernel<RawSrc<FMT>, true>), dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, src, n,
+                       key_ge, key_gt, k_hi, e.f0, e.f1, words);
+  } else {
+    hipLaunchKernelGGL((pdw_raw_mask_kernel<RawSrc<FMT>, false>), dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, src, n,
+                       key_ge, key_gt, k_hi, e.f0, e.f1, words);
+  }
+}
+
 template <int FMT>
 int extract_raw(const void* d_iq, long long n, double inv_scale, double fs, double fc, double t0, double lead_db,
                 double trail_db, pfb_pdw* out, uint64_t capacity, uint64_t* count, double* noise_floor_out, Arena& ws,
@@ -2286,32 +2328,8 @@ int extract_raw(const void* d_iq, long long n, double inv_scale, double fs, doub
   }
   PDW_TRY(hipMemcpyAsync(e.nf, &nf, sizeof(double), hipMemcpyHostToDevice, st));
   PDW_TRY(hipStreamSynchronize(st));  // nf lives on this stack frame
-  // ---- edges (:54-105) and pulses.  The thresholds as keys: the first key whose magnitude is >= lead / > trail
-  {
-    auto key_mag = [&](unsigned long long k) {
-      return (FMT == PFB_FMT_CF32) ? std::sqrt(dkey_inv_host(k)) : std::sqrt((double)k) * inv_scale;
-    };
-    const unsigned long long k_lo = (FMT == PFB_FMT_CF32) ? 0x8000000000000000ull : 0ull;               // |x|^2 = 0
-    const unsigned long long k_hi = (FMT == PFB_FMT_CF32) ? 0xFFF0000000000000ull : (1ull << 33);       // +inf / above any sample
-    auto first_key = [&](auto pred) {  // smallest key in [k_lo, k_hi] that passes, k_hi + 1 if none (pred is monotone)
-      if (!pred(k_hi)) return k_hi + 1;
-      unsigned long long lo = k_lo, hi = k_hi;  // invariant: pred(hi)
-      while (lo < hi) {
-        const unsigned long long mid = lo + (hi - lo) / 2;
-        if (pred(mid)) hi = mid; else lo = mid + 1;
-      }
-      return lo;
-    };
-    const unsigned long long key_ge = first_key([&](unsigned long long k) { return key_mag(k) >= lead; });
-    const unsigned long long key_gt = first_key([&](unsigned long long k) { return key_mag(k) > trail; });
-    if (vec) {
-      hipLaunchKernelGGL((pdw_raw_mask_kernel<RawSrc<FMT>, true>), dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, src, n,
-                         key_ge, key_gt, k_hi, e.f0, e.f1, words);
-    } else {
-      hipLaunchKernelGGL((pdw_raw_mask_kernel<RawSrc<FMT>, false>), dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, src, n,
-                         key_ge, key_gt, k_hi, e.f0, e.f1, words);
-    }
-  }
+  // ---- edges (:54-105) and pulses
+  launch_raw_masks<FMT>(src, n, inv_scale, lead, trail, vec, e, words, st);
   PDW_TRY(hipGetLastError());
   rc = edges_and_pulses(src, 1, ntiles, tile_words, e, ws2, fs, fc, t0, 0u, out, capacity, count, st);
 done:
@@ -2387,3 +2405,6 @@ extern "C" int pfb_pdw_extract_raw(const void* iq, uint64_t num_samples, uint32_
                                 trailing_threshold_db, out, capacity, count, noise_floor_out, mem, device_id, hip_stream);
   });
 }
+
+// ---- dwell analysis (matlab/predict_event.m:53-121, cpp/usrp_predict_event.cpp:285-343): pfb_dwell_analyze ----
+#include "pfb_dwell.hpp"
