@@ -1,5 +1,5 @@
-// pfb_dwell.hpp -- dwell analysis (include/pfb_channelizer.h, pfb_dwell_analyze), included at the end of pfb_pdw.hip,
-// whose sample sources, edge stage and scratch arenas it uses.
+// pfb_dwell.hpp -- dwell analysis (include/pfb_channelizer.h, pfb_dwell_analyze; the entry point is in pfb_pdw.hip) on
+// the raw extractor's sample source, stage and edge stage (pfb_pdw_raw.hpp).
 //
 // Restates the per-dwell part of the reference's event predictor on the raw recorder stream:
 //   matlab/predict_event.m:53-121       MEDIAN: the raw extractor with one threshold for both edges -- extract_raw itself
@@ -18,8 +18,9 @@
 // The MEAN route reads the stream twice (stats, masks) plus the pulses' own samples; it has no radix select.
 #pragma once
 
-namespace {
+#include "pfb_pdw_raw.hpp"
 
+namespace {
 struct DwellPartial {  // what one workgroup of the stats pass saw
   double sum;    // of sqrt(I^2 + Q^2), raw units (integers: the 2^-(bit_width-1) scale is applied once, to the total)
   double m2max;  // largest I^2 + Q^2 (exact in double for every format)
@@ -255,34 +256,26 @@ struct MeanPulse {  // edges_and_pulses' per-pulse stage of the MEAN statistic
   template <class Src>
   static void launch(Src src, const long long* starts, const long long* ends, const double* nf, double fs, double fc, double t0,
                      unsigned flags, pfb_pdw* out, unsigned long long n_out, hipStream_t st) {
-    if (flags & PFB_DWELL_SKIP_FREQ) {
-      hipLaunchKernelGGL((dwell_pulse_mean_kernel<Src, false>), dim3((unsigned)n_out), dim3(Src::kThreads), 0, st, src, starts, ends,
-                         nf, fs, fc, t0, out);
-    } else {
-      hipLaunchKernelGGL((dwell_pulse_mean_kernel<Src, true>), dim3((unsigned)n_out), dim3(Src::kThreads), 0, st, src, starts, ends,
-                         nf, fs, fc, t0, out);
-    }
+    with_bool(!(flags & PFB_DWELL_SKIP_FREQ), [&](auto freq) {
+      hipLaunchKernelGGL((dwell_pulse_mean_kernel<Src, decltype(freq)::value>), dim3((unsigned)n_out), dim3(Src::kThreads), 0, st, src,
+                         starts, ends, nf, fs, fc, t0, out);
+    });
   }
 };
 
-struct DwellStage {  // device buffers of one call, all inside arena 0
-  unsigned* hist;
-  unsigned long long* pair;
-  DwellPartial* part;
-  EdgeStage e;
-  long long words, ntiles;
-  int tile_words;
+struct DwellStage : RawStage {  // device buffers of one call, all inside arena 0
+  DwellPartial* part;  // [kDwellMaxBlocks]
 };
 
 template <int FMT>
-int dwell_run(const pfb_dwell_config& c, const void* d_iq, long long n, pfb_pdw* out, uint64_t capacity, uint64_t* count,
-              pfb_dwell_stats* stats, Arena& ws, Arena& ws2, const DwellStage& d, hipStream_t st) {
-  int rc = PFB_OK;
+int dwell_run(PdwCall& call, const pfb_dwell_config& c, const DwellStage& d, pfb_pdw* out, uint64_t capacity, uint64_t* count,
+              pfb_dwell_stats* stats) {
+  const hipStream_t st = call.st;
+  const long long n = d.n;
   const int full_bits = (int)c.bit_width - 1;
-  const double inv_scale = FMT == PFB_FMT_CF32 ? 1.0 : std::ldexp(1.0, -full_bits);
+  const double inv_scale = d.inv_scale;
   const double gain = std::pow(10.0, c.snr_threshold_db / 10.0);
-  const RawSrc<FMT> src{d_iq, inv_scale};
-  const bool vec = (reinterpret_cast<uintptr_t>(d_iq) % 16) == 0;
+  const RawSrc<FMT> src{d.d_iq, inv_scale};
   const unsigned grid = dwell_stats_grid(n);
   const double sf = c.sat_fraction == 0.0 ? 0.98 : c.sat_fraction;
   // the gain finders' limits; for the integer formats rounded outwards to the integers the kernel compares with
@@ -292,18 +285,17 @@ int dwell_run(const pfb_dwell_config& c, const void* d_iq, long long n, pfb_pdw*
     sat_lo = std::floor(sf * -full);
     sat_hi = std::ceil(sf * (full - 1.0));
   }
-  std::vector<DwellPartial> part(grid);
-  double sum = 0.0, m2max = 0.0, cmax = 0.0, nf = 0.0;
-  unsigned long long nsat = 0ull;
   *count = 0;
-  if (vec) {
-    hipLaunchKernelGGL((dwell_stats_kernel<RawSrc<FMT>, true>), dim3(grid), dim3(256), 0, st, src, n, sat_lo, sat_hi, d.part);
-  } else {
-    hipLaunchKernelGGL((dwell_stats_kernel<RawSrc<FMT>, false>), dim3(grid), dim3(256), 0, st, src, n, sat_lo, sat_hi, d.part);
-  }
+  with_bool(d.vec, [&](auto vec) {
+    hipLaunchKernelGGL((dwell_stats_kernel<RawSrc<FMT>, decltype(vec)::value>), dim3(grid), dim3(256), 0, st, src, n, sat_lo, sat_hi,
+                       d.part);
+  });
   PDW_TRY(hipGetLastError());
+  std::vector<DwellPartial> part(grid);
   PDW_TRY(hipMemcpyAsync(part.data(), d.part, grid * sizeof(DwellPartial), hipMemcpyDeviceToHost, st));
   PDW_TRY(hipStreamSynchronize(st));
+  double sum = 0.0, m2max = 0.0, cmax = 0.0;
+  unsigned long long nsat = 0ull;
   for (const DwellPartial& p : part) {  // index order
     sum += p.sum;
     m2max = std::max(m2max, p.m2max);
@@ -315,17 +307,19 @@ int dwell_run(const pfb_dwell_config& c, const void* d_iq, long long n, pfb_pdw*
   stats->mean_mag = sum * inv_scale / (double)n;
   stats->peak_mag = std::sqrt(m2max) * inv_scale;
   stats->peak_component = cmax * inv_scale;
+  double nf = 0.0;
+  int rc;
   if (c.statistic == PFB_DWELL_STAT_MEDIAN) {  // predict_event.m:64-121 is create_pdws.m with one threshold
-    rc = extract_raw<FMT>(d_iq, n, inv_scale, c.fs, c.fc, c.sample_start_time, c.snr_threshold_db, c.snr_threshold_db, out,
-                          capacity, count, &nf, ws, ws2, d.e, d.hist, d.pair, d.words, d.ntiles, d.tile_words, st);
+    rc = extract_raw<FMT>(call, d, RawParams{c.fs, c.fc, c.sample_start_time, c.snr_threshold_db, c.snr_threshold_db, out, capacity,
+                                             count, &nf});
   } else {
     nf = stats->mean_mag;  // usrp_predict_event.cpp:288-289
     PDW_TRY(hipMemcpyAsync(d.e.nf, &nf, sizeof(double), hipMemcpyHostToDevice, st));
     PDW_TRY(hipStreamSynchronize(st));  // nf lives on this stack frame
-    launch_raw_masks<FMT>(src, n, inv_scale, nf * gain, nf * gain, vec, d.e, d.words, st);  // :291, :306, :316
+    launch_raw_masks<FMT>(src, d, nf * gain, nf * gain, st);  // :291, :306, :316
     PDW_TRY(hipGetLastError());
-    rc = edges_and_pulses<RawSrc<FMT>, MeanPulse>(src, 1, d.ntiles, d.tile_words, d.e, ws2, c.fs, c.fc, c.sample_start_time,
-                                                  c.flags, out, capacity, count, st);
+    rc = edges_and_pulses<RawSrc<FMT>, MeanPulse>(src, 1, d.ntiles, d.tile_words, d.e, call, c.fs, c.fc, c.sample_start_time, c.flags,
+                                                  out, capacity, count);
   }
   stats->noise_floor = nf;
   stats->threshold = nf * gain;
@@ -334,7 +328,6 @@ int dwell_run(const pfb_dwell_config& c, const void* d_iq, long long n, pfb_pdw*
   stats->reserved = 0;
   if (rc == PFB_OK)
     for (uint64_t i = 0; i < std::min<uint64_t>(*count, capacity); ++i) stats->any_pulse_saturated |= out[i].sat != 0;
-done:
   return rc;
 }
 
@@ -343,49 +336,14 @@ int dwell_analyze_impl(const pfb_dwell_config* cfg, const void* iq, uint64_t num
   if (!iq || !count || !stats || num_samples < 2 || (capacity && !out)) return PFB_ERR_BAD_ARG;
   int rc = pfb::dwell_check_config(cfg, false);
   if (rc != PFB_OK) return rc;
-  int dev = 0;
-  rc = pfb::resolve_device(cfg->device_id, &dev);
-  if (rc != PFB_OK) return rc;
-  if (dev >= kMaxDevices) return PFB_ERR_BAD_ARG;
-  pfb::DeviceGuard guard(dev);
-  std::lock_guard<std::mutex> lock(g_ws_mutex);
-  Arena& ws = g_ws[dev][0];
-  Arena& ws2 = g_ws[dev][1];
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const long long n = (long long)num_samples;
-  const uint32_t fmt = cfg->sample_format;
-  const size_t bps = fmt == PFB_FMT_INT8_IQ ? 2 : fmt == PFB_FMT_INT16_IQ ? 4 : 8;
-  const void* d_iq = iq;
+  PdwCall call(cfg->device_id, hip_stream);
+  if (call.rc != PFB_OK) return call.rc;
   DwellStage d{};
-  d.tile_words = tile_words_for(n, 1);
-  d.ntiles = (n + 64ll * d.tile_words - 1) / (64ll * d.tile_words);
-  d.words = d.ntiles * d.tile_words;
-  constexpr size_t kHistBytes = kRawBins * sizeof(unsigned) + 4096 * sizeof(unsigned long long);  // as pdw_extract_raw_impl
-  PDW_TRY(arena_reserve(ws, (cfg->mem == PFB_MEM_HOST ? padded((size_t)n * bps) : 0) + padded(kHistBytes) +
-                                padded(2 * sizeof(unsigned long long)) + padded(kDwellMaxBlocks * sizeof(DwellPartial)) +
-                                edge_stage_bytes(d.words, d.ntiles, 1)));
-  if (cfg->mem == PFB_MEM_HOST) {
-    char* own = take<char>(ws, (size_t)n * bps);
-    PDW_TRY(hipMemcpyAsync(own, iq, (size_t)n * bps, hipMemcpyHostToDevice, st));
-    d_iq = own;
-  }
-  d.hist = take<unsigned>(ws, kHistBytes / sizeof(unsigned));
-  d.pair = take<unsigned long long>(ws, 2);
-  d.part = take<DwellPartial>(ws, kDwellMaxBlocks);
-  d.e = take_edge_stage(ws, d.words, d.ntiles, 1, false);
-  switch (fmt) {
-    case PFB_FMT_INT8_IQ: rc = dwell_run<PFB_FMT_INT8_IQ>(*cfg, d_iq, n, out, capacity, count, stats, ws, ws2, d, st); break;
-    case PFB_FMT_INT16_IQ: rc = dwell_run<PFB_FMT_INT16_IQ>(*cfg, d_iq, n, out, capacity, count, stats, ws, ws2, d, st); break;
-    default: rc = dwell_run<PFB_FMT_CF32>(*cfg, d_iq, n, out, capacity, count, stats, ws, ws2, d, st); break;
-  }
-done:
-  (void)hipStreamSynchronize(st);
-  return rc;
+  rc = raw_stage(call, iq, num_samples, cfg->sample_format, cfg->bit_width, cfg->mem, d,
+                 [&](Arena& a) { d.part = take<DwellPartial>(a, kDwellMaxBlocks); });
+  if (rc != PFB_OK) return rc;
+  return with_format(cfg->sample_format, [&](auto fmt) {
+    return dwell_run<decltype(fmt)::value>(call, *cfg, d, out, capacity, count, stats);
+  });
 }
-
 }  // namespace
-
-extern "C" int pfb_dwell_analyze(const pfb_dwell_config* cfg, const void* iq, uint64_t num_samples, pfb_pdw* out,
-                                 uint64_t capacity, uint64_t* count, pfb_dwell_stats* stats, void* hip_stream) {
-  return pfb::abi_guard([&] { return dwell_analyze_impl(cfg, iq, num_samples, out, capacity, count, stats, hip_stream); });
-}

@@ -1,7 +1,7 @@
 """Designed inputs for the PDW extractors (plain numpy, no GPU): data built to land on the data-dependent branches of
-sdr_channelizer_amd/csrc/pfb_pdw.hip -- the per-pulse median routes (pdw_pulse_kernel, cached_median, block_median and
-its two tie branches), the saturation scan, the identity elements and the word / tile / thread-segment / wave boundaries
-of the edge scan, and the overflow of the undecided list (noise-floor path 4).
+sdr_channelizer_amd/csrc/pfb_pdw.hip and its stage headers -- the per-pulse median routes (pfb_pdw_pulse.hpp:
+pdw_pulse_kernel; pfb_pdw_select.hpp: cached_median, block_median and its two tie branches), the saturation scan, the
+identity elements and the word / tile / thread-segment / wave boundaries of the edge scan, and the overflow of the undecided list (noise-floor path 4).
 
 Every builder returns a Case: the input, the extraction arguments, and the designed facts -- the pulses as
 (column, toa0, n) with toa0 the 0-based index of the first sample at or above the leading threshold and
@@ -26,7 +26,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-# constants of sdr_channelizer_amd/csrc/pfb_pdw.hip (tests/test_pdw_cases_cpu.py reads them out of the source and fails
+# constants of sdr_channelizer_amd/csrc/pfb_pdw_select.hpp (tests/test_pdw_cases_cpu.py reads them out of the source and fails
 # if they move: the lengths below sit on them)
 kTile = 512
 kPulseCache = 512
@@ -111,7 +111,7 @@ def median_route(kind: str, n: int):
 
 
 def tile_words_for(samples: int, M: int) -> int:
-    """restates pfb_pdw.hip's tile_words_for: the tile length of the edge scan, in 64-sample words"""
+    """restates pfb_pdw_stage.hpp's tile_words_for: the tile length of the edge scan, in 64-sample words"""
     w = (samples + 63) // 64
     max_tiles = min(16384, max(2048, (1 << 18) // max(1, M)))
     tw = kTile // 64

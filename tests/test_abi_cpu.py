@@ -72,10 +72,21 @@ def test_nothing_thrown_crosses_the_c_abi():
         for name in names:
             body = src[src.index(f"\nint {name}("):]
             assert "abi_guard" in body[: body.index("\n}\n")].split("{", 1)[1][:80], name
+    # pfb_pdw.hip holds every entry point of its unit: each extern "C" int definition found there is guarded, and the
+    # stage headers it includes define none
     pdw = open(os.path.join(csrc, "pfb_pdw.hip")).read()
-    for name in ("pfb_pdw_extract", "pfb_pdw_extract_raw", "pfb_pdw_release_workspace"):
-        body = pdw[pdw.index(f'extern "C" int {name}('):]
-        assert "abi_guard" in body[: body.index("\n}\n")], name
+    found = {}
+    for m in re.finditer(r'^extern "C" int (\w+)\(', pdw, re.M):
+        rest = pdw[m.start():]
+        line = rest[: rest.index("\n")]
+        found[m.group(1)] = line if line.endswith("}") else rest[: rest.index("\n}\n")]   # one line, or up to its "}" line
+    assert {"pfb_pdw_extract", "pfb_pdw_extract_raw", "pfb_pdw_release_workspace", "pfb_dwell_analyze"} <= set(found)
+    for name, body in found.items():
+        assert "abi_guard" in body, name
+    headers = [f for f in os.listdir(csrc) if re.fullmatch(r"pfb_pdw_\w+\.hpp|pfb_dwell\.hpp", f)]
+    assert "pfb_dwell.hpp" in headers and len(headers) > 1
+    for f in headers:
+        assert 'extern "C"' not in open(os.path.join(csrc, f)).read(), f
 
 
 def test_shard_entry_points_validate_arguments():

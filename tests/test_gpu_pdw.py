@@ -323,7 +323,7 @@ def test_raw_stream_long_tiles(oracle):
 
 
 def _sample_row(q, stride):
-    """the library's hashed sample position (pfb_pdw.hip: sample_row)"""
+    """the library's hashed sample position (pfb_pdw_floor.hpp: sample_row)"""
     h = (q * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
     h ^= h >> 29
     return q * stride + (((h >> 40) * stride) >> 24)

@@ -1,5 +1,5 @@
-"""The data-dependent branches of the PDW extractors (sdr_channelizer_amd/csrc/pfb_pdw.hip) on data designed to land on
-them -- tests/pdw_cases.py, whose designs tests/test_pdw_cases_cpu.py proves with the oracle alone:
+"""The data-dependent branches of the PDW extractors (sdr_channelizer_amd/csrc/pfb_pdw.hip, pfb_pdw_*.hpp) on data
+designed to land on them -- tests/pdw_cases.py, whose designs tests/test_pdw_cases_cpu.py proves with the oracle alone:
 
   A  per-pulse medians: pulse lengths on either side of kCountingMedian, kPulseCache and kPulseCacheRaw, with distinct,
      constant, two-level (both tie branches of block_median) and narrowly packed values, every source format

@@ -1,7 +1,8 @@
 """The designs of tests/pdw_cases.py, proven with the oracle alone (no GPU): the oracle's restatement of
 create_pdws.m / create_pdws_channelized.m finds exactly the designed pulses on every designed input, the tie structures
 are what they claim to be, no phase step sits on the +-180 degree wrap, and the kernel constants the lengths were chosen
-around are still the ones in pfb_pdw.hip.  tests/test_gpu_pdw_branches.py then holds the library to the same answers."""
+around are still the ones in pfb_pdw.hip and its headers.  tests/test_gpu_pdw_branches.py then holds the library to the same
+answers."""
 import os
 import re
 
@@ -49,7 +50,9 @@ def check_two_level(case, want):
 
 
 def test_kernel_constants_are_the_ones_designed_around():
-    src = open(os.path.join(os.path.dirname(__file__), "..", "sdr_channelizer_amd", "csrc", "pfb_pdw.hip")).read()
+    csrc = os.path.join(os.path.dirname(__file__), "..", "sdr_channelizer_amd", "csrc")
+    src = open(os.path.join(csrc, "pfb_pdw.hip")).read()   # the umbrella, then the stage headers it includes
+    src += "".join(open(os.path.join(csrc, h)).read() for h in re.findall(r'^#include "(pfb_(?:pdw_\w+|dwell)\.hpp)"', src, re.M))
     for name in ("kTile", "kPulseCache", "kPulseCacheRaw", "kCountingMedian", "kUndecided"):
         m = re.search(r"constexpr\s+int\s+" + name + r"\s*=\s*([^;]+);", src)
         assert m, name

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """isa_identical.py OLD_TREE NEW_TREE -- is the device code of two checkouts the same?
 
-Compiles the five kernel translation units of both trees to gfx950 assembly with the flags of
+Compiles the six kernel translation units of both trees to gfx950 assembly with the flags of
 sdr_channelizer_amd/build.py and compares them per kernel symbol: the instruction text with its
-.amdhsa_kernel block, and the kernel's entry in the code object's metadata.  Comments, .ident, .file and the
-per-compilation __hip_cuid_<hash> symbol are dropped; local labels lose the function's ordinal, so that the order
+.amdhsa_kernel block, and the kernel's entry in the code object's metadata.  Comments, .ident, .file, the
+per-compilation __hip_cuid_<hash> symbol and the file's .AMDGPU.* trailer sections (which follow whichever kernel was
+emitted last) are dropped; local labels lose the function's ordinal, so that the order
 in which kernels are emitted does not matter.  Exit status 0 = every kernel of every file exists in both trees and
 is identical.  A refactor that only moves device code between structs and headers must pass with no difference.
 """
@@ -16,7 +17,8 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-FILES = ["pfb_kernels.hip", "pfb_kernels_mid.hip", "pfb_kernels_big.hip", "pfb_kernels_mixed.hip", "pfb_stft.hip"]
+FILES = ["pfb_kernels.hip", "pfb_kernels_mid.hip", "pfb_kernels_big.hip", "pfb_kernels_mixed.hip", "pfb_stft.hip",
+         "pfb_pdw.hip"]
 CSRC = os.path.join("sdr_channelizer_amd", "csrc")
 FIELDS = [".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
           ".group_segment_fixed_size"]
@@ -44,7 +46,7 @@ def kernels(path):
             word = line.split()[0] if line.strip() else ""
             if not word or word in (".ident", ".file"):
                 continue
-            if "__hip_cuid_" in line:
+            if "__hip_cuid_" in line or (word == ".section" and ".AMDGPU." in line):  # the file's trailer, no kernel's
                 cur, pending = None, []
             elif word == ".amdgpu_metadata":
                 in_meta = True
