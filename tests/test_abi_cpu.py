@@ -8,18 +8,10 @@ import numpy as np
 import pytest
 
 import sdr_channelizer_amd as pkg
+from abi_symbols import declared_symbols
 from sdr_channelizer_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols(headers=("pfb_channelizer.h", "pfb_iq_packet.h")):
-    names = set()
-    for hdr in headers:
-        text = open(os.path.join(ROOT, "include", hdr)).read()
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        names |= set(re.findall(r"\b(pfb_[a-z0-9_]+)\s*\(", text))
-    return names
 
 
 def test_library_exports_every_declared_symbol():

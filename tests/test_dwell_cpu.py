@@ -11,9 +11,9 @@ import pytest
 
 import dwell_ref
 import sdr_channelizer_amd as pkg
+from abi_symbols import declared_symbols
 from sdr_channelizer_amd import _lib as L
 from sdr_channelizer_amd.pdw import PDW_DTYPE
-from test_abi_cpu import declared_symbols
 
 NEW = ("pfb_dwell_analyze", "pfb_dwell_from_iq_file", "pfb_event_fit", "pfb_event_next")
 

@@ -10,6 +10,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from gpu_support import Busy, cuda_torch  # noqa: E402
+from pdw_checks import synthetic_matrix  # noqa: E402
+from plan_support import device_input  # noqa: E402
 from sdr_channelizer_amd import Channelizer, Stft, synth  # noqa: E402
 from sdr_channelizer_amd import _lib as L  # noqa: E402
 from sdr_channelizer_amd.pdw import extract_pdws, extract_pdws_raw  # noqa: E402
@@ -25,18 +28,7 @@ IDS = [f"M{c[0]}-D{c[2]}-{c[3]}{'-cm' if c[5] else ''}" for c in CASES]
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch
-
-
-def make_input(torch, n, fmt, bw, seed):
-    if fmt == "cf32":
-        g = torch.Generator(device="cuda")
-        g.manual_seed(seed)
-        return torch.randn((n, 2), dtype=torch.float32, device="cuda", generator=g)
-    return synth.pulsed_iq_torch(n, bw, torch.int8 if fmt == "int8" else torch.int16, seed=seed, device="cuda")
+    return cuda_torch()
 
 
 def make_handle(case, seed=3, **extra):
@@ -61,23 +53,6 @@ def size_slab_scratch(ch, bufs):
     if ch.channel_major:
         ch(max(bufs, key=lambda x: x.shape[0]))
         ch.reset()
-
-
-class Busy:
-    """A few tens of milliseconds of unrelated work queued on a stream (large device copies), so that everything
-    enqueued behind it is issued with the host ahead of the device."""
-
-    def __init__(self, torch):
-        self.torch = torch
-        self.src = torch.empty(1 << 30, dtype=torch.float32, device="cuda")   # 4 GiB
-        self.dst = torch.empty_like(self.src)
-        self.src.zero_()
-        torch.cuda.synchronize()
-
-    def queue(self, stream, copies=8):
-        with self.torch.cuda.stream(stream):
-            for _ in range(copies):
-                self.dst.copy_(self.src, non_blocking=True)
 
 
 @pytest.fixture(scope="module")
@@ -108,7 +83,7 @@ def test_back_to_back_async_calls(torch, busy, case, switch):
         rep = ch.last_launch
         assert all(getattr(rep, f) == 0 for f, _ in L.PfbLaunchReport._fields_)   # nothing launched yet
         lens = ragged_lengths(rng, D, ch.history_samples)
-        iq = make_input(torch, sum(lens), fmt, bw, 77)
+        iq = device_input(sum(lens), fmt, bw, 77)
         want = ref(iq)
         assert ref.last_kernel.startswith(kernel), ref.last_kernel
         cuts = np.concatenate([[0], np.cumsum(lens)])
@@ -143,7 +118,7 @@ def test_state_calls_behind_queued_work(torch, busy, case):
     rng = np.random.default_rng(2 * M + D)
     with make_handle(case) as ref, make_handle(case) as ch, make_handle(case) as resumed:
         lens = ragged_lengths(rng, D, ch.history_samples, count=24)
-        iq = make_input(torch, sum(lens), fmt, bw, 78)
+        iq = device_input(sum(lens), fmt, bw, 78)
         want = ref(iq)
         cuts = np.concatenate([[0], np.cumsum(lens)])
         bufs = [iq[a:b].clone() for a, b in zip(cuts[:-1], cuts[1:])]
@@ -200,7 +175,7 @@ def test_set_frame_index_behind_queued_work(torch, busy):
     case = CASES[1]
     M, P, D = case[:3]
     n1, n2 = 5000 * D + 17, 3000 * D + 5
-    iq = make_input(torch, n1 + n2, "int16", 12, 79)
+    iq = device_input(n1 + n2, "int16", 12, 79)
     a, b = iq[:n1].clone(), iq[n1:].clone()
     with make_handle(case, derotate=True) as ref, make_handle(case, derotate=True) as ch:
         one = ref(iq)
@@ -229,7 +204,7 @@ def test_slab_scratch_regrown_behind_queued_calls(torch, busy):
     frames = [70, 300, 1500, 9000, 40000, 150000, 100]
     lens = [f * D + 3 for f in frames]
     with make_handle(case) as ref, make_handle(case) as ch:
-        iq = make_input(torch, sum(lens), fmt, bw, 80)
+        iq = device_input(sum(lens), fmt, bw, 80)
         want = ref(iq)
         assert ref.last_kernel.startswith(kernel) and ref.last_launch.by_slabs == 1
         cuts = np.concatenate([[0], np.cumsum(lens)])
@@ -257,7 +232,7 @@ def test_profiled_async_launches(torch, busy, case):
     frames = [100, 300, 1 << 20, 200, 0, 300]
     lens = [f * D for f in frames]
     with make_handle(case) as ref, make_handle(case) as ch:
-        iq = make_input(torch, sum(lens), fmt, bw, 81)
+        iq = device_input(sum(lens), fmt, bw, 81)
         want = ref(iq)
         cuts = np.concatenate([[0], np.cumsum(lens)])
         bufs = [iq[a:b].clone() for a, b in zip(cuts[:-1], cuts[1:])]
@@ -329,7 +304,6 @@ def test_stft_back_to_back_async_calls(torch, busy, nfft, Lw, H, fmt, kernel, sw
 def test_pdw_extraction_on_a_busy_stream(torch, busy):
     """extract_pdws / extract_pdws_raw on a device tensor while a non-default stream is current and still busy with the
     kernel that wrote the tensor: the PDWs of the same data extracted after a full synchronise."""
-    from test_gpu_pdw import synthetic_matrix
     y_src = torch.from_numpy(synthetic_matrix(F=40000, M=64, seed=11)).cuda()
     iq_src = synth.pulsed_iq_torch(1 << 22, 12, device="cuda")
     s = torch.cuda.Stream()

@@ -6,7 +6,7 @@ compared with tests/dwell_ref.py (float64, math.fsum) on the same samples:
   sums       noise_floor, mean_mag: relative (n + 4) * 2^-52, the worst case of any summation order of n non-negative
              doubles plus one rounding of |x|; a pulse's mag the same with its own length
   snr        (20 / ln 10) * (n + 4) * 2^-52 dB: the same bound through the logarithm, twice (a ratio of two sums)
-  freq       as tests/test_gpu_pdw.py compares it (rtol 1e-9, atol 1e-6, the antipodal-step slack)
+  freq       as compare of tests/pdw_checks.py holds it (rtol 1e-9, atol 1e-6, the antipodal-step slack)
 
 Every design keeps each |x| at least 1e-9 (relative) away from the threshold, asserted on the reference side, so that
 no rounding of the noise floor can move an edge.  The thresholds are chosen from the data (threshold_db: the level
@@ -22,77 +22,19 @@ pytestmark = pytest.mark.gpu
 
 import dwell_ref  # noqa: E402
 import pdw_cases as pc  # noqa: E402
+from gpu_support import Busy, cuda_torch  # noqa: E402
+from pdw_checks import FC, FS, check_mean, threshold_db  # noqa: E402
 from sdr_channelizer_amd import EventPredictor, analyze_dwell, dwell_from_iq_file, iqfile  # noqa: E402
 from sdr_channelizer_amd.pdw import extract_pdws_raw  # noqa: E402
-from test_gpu_pdw import antipodal_slack  # noqa: E402
-
-EPS = 2.0 ** -52
-FS, FC = pc.FS_RAW, pc.FC
 
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch
+    return cuda_torch()
 
 
 def to_device(torch, data):
     return torch.from_numpy(np.ascontiguousarray(data)).cuda()
-
-
-def threshold_db(data, bit_width, level=0.15):
-    """the snr_threshold_db that puts the MEAN threshold near `level`, to a tenth of a dB"""
-    return round(10.0 * math.log10(level / dwell_ref.stats(data, bit_width)["mean_mag"]), 1)
-
-
-def check_mean(got, stats, data, bit_width, snr_db, fs=FS, fc=FC, t0=0.0, skip_freq=False, min_pulses=0, sat_fraction=0.98):
-    """(pdws, stats) of a MEAN call against the reference on the same samples; returns the reference"""
-    want = dwell_ref.analyze(data, fs, fc, t0, statistic="mean", bit_width=bit_width, snr_threshold_db=snr_db,
-                             skip_freq=skip_freq)
-    ws = dwell_ref.stats(data, bit_width, sat_fraction)
-    n = want["n"]
-    assert want["clearance"] >= 1e-9, want["clearance"]       # a condition on the input
-    assert len(want["i0"]) >= min_pulses
-    rel = (n + 4) * EPS
-    print(f"n={n} pulses={stats.pulses} nf={stats.noise_floor!r} want={want['noise_floor']!r} "
-          f"rel={abs(stats.noise_floor / want['noise_floor'] - 1) if want['noise_floor'] else 0:.3g} bound={rel:.3g}")
-    assert stats.num_samples == n and stats.pulses == len(want["i0"])
-    assert stats.peak_mag == ws["peak_mag"] and stats.peak_component == ws["peak_component"]
-    assert stats.saturated_components == ws["saturated_components"]
-    assert abs(stats.noise_floor - want["noise_floor"]) <= rel * want["noise_floor"]
-    assert abs(stats.mean_mag - ws["mean_mag"]) <= rel * ws["mean_mag"] and stats.noise_floor == stats.mean_mag
-    assert abs(stats.threshold - want["threshold"]) <= 2 * rel * want["threshold"]
-    k = len(got)
-    assert k == min(stats.pulses, k)
-    i0 = np.rint((got["toa"] - t0) * fs).astype(np.int64)
-    j = i0 + np.rint(got["pw"] * fs).astype(np.int64)
-    assert np.array_equal(i0, want["i0"][:k]) and np.array_equal(j, want["j"][:k])
-    assert np.array_equal(got["sat"], want["sat"][:k]) and (got["bin"] == 0).all()
-    assert stats.any_pulse_saturated == bool(want["sat"][:k].any())
-    assert np.allclose(got["toa"], want["toa"][:k], rtol=0, atol=1e-9 / fs + 1e-12 * abs(t0))
-    assert np.allclose(got["pw"], want["pw"][:k], rtol=1e-12, atol=0)
-    m = (want["j"] - want["i0"])[:k]
-    mag_err = np.abs(got["mag"] - want["mag"][:k])
-    assert (mag_err <= (m + 4) * EPS * want["mag"][:k]).all(), (mag_err / want["mag"][:k]).max()
-    snr_err = np.abs(got["snr"] - want["snr"][:k])
-    snr_bound = (20.0 / math.log(10.0)) * rel
-    finite = np.isfinite(want["snr"][:k])
-    print(f"snr err max={snr_err[finite].max(initial=0.0):.3g} bound={snr_bound:.3g}  "
-          f"mag rel err max={(mag_err / np.maximum(want['mag'][:k], 1e-300)).max(initial=0.0):.3g}")
-    assert (snr_err[finite] <= snr_bound).all(), snr_err[finite].max()
-    assert np.array_equal(np.isnan(got["snr"]), np.isnan(want["snr"][:k]))
-    if skip_freq:
-        assert np.isnan(got["freq"]).all()
-    else:
-        bad = ~np.isclose(got["freq"], want["freq"][:k], rtol=1e-9, atol=1e-6, equal_nan=True)
-        re, im = dwell_ref.components(data, bit_width)
-        for i in np.flatnonzero(bad):
-            col = re[i0[i]:j[i] + 1] + 1j * im[i0[i]:j[i] + 1]
-            bad[i] = not antipodal_slack(col, float(got["freq"][i]), float(want["freq"][i]), fs)
-        assert not bad.any(), (np.flatnonzero(bad), got["freq"][bad], want["freq"][:k][bad])
-    return want
 
 
 def run_mean(data, bit_width, *, min_pulses=1, **kw):
@@ -314,7 +256,6 @@ def test_same_buffer_same_bits(torch, source):
 def test_dwell_on_a_busy_stream(torch):
     """analyze_dwell on a device tensor while a non-default stream is current and still busy with the kernel that wrote
     the tensor (the pattern of tests/test_gpu_async.py::test_pdw_extraction_on_a_busy_stream)"""
-    from test_gpu_async import Busy
     busy = Busy(torch)
     case = short_stream((1 << 20) + 5, "int16_12", seed=6)
     src = to_device(torch, case.data)

@@ -8,36 +8,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from plan_support import FMT, SHAPES  # noqa: E402
 from sdr_channelizer_amd import Channelizer, synth  # noqa: E402
 from sdr_channelizer_amd import _lib as L  # noqa: E402
 
-# (M, P, D, formats, schedules worth forcing besides the default)
-SHAPES = [
-    (64, 12, 64, ("int16", "int8", "cf32"), (0, 2, 3, 4, 7, 8, 11)),
-    (64, 16, 64, ("int16",), (0, 4, 7, 8)),
-    (128, 12, 64, ("int16", "cf32"), (0, 2, 3, 7, 8, 11)),
-    (256, 8, 256, ("int8", "int16", "cf32"), (0, 2, 8, 11)),
-    (1024, 16, 1024, ("int16", "cf32"), (0, 6)),
-    (56, 12, 56, ("int16", "int8", "cf32"), (0, 2, 3, 7, 8)),
-    (560, 12, 560, ("int16", "int8", "cf32"), (0, 6)),
-    (32, 12, 32, ("int16", "int8"), (0, 2, 7, 8)),
-    (16, 12, 16, ("int16", "int8"), (0,)),
-    (8, 12, 8, ("int16", "int8", "cf32"), (0,)),
-    (10, 12, 10, ("int16",), (0,)),
-    (20, 12, 20, ("int16",), (0,)),
-    (40, 12, 40, ("int16",), (0,)),
-    # csrc/pfb_kernels_mixed.hip: SegKernel shapes, single-wave two-pass shapes, multi-wave three-pass shapes (lockstep / teams)
-    (12, 12, 12, ("int16",), (0,)), (24, 12, 24, ("int16",), (0,)), (25, 12, 25, ("int16",), (0,)), (30, 12, 30, ("int16",), (0,)),
-    (48, 12, 48, ("int16",), (0, 7, 11, 8)), (50, 12, 50, ("int16",), (0, 7, 11)),
-    (80, 12, 80, ("int16",), (0, 7, 11, 8)), (96, 12, 96, ("int16",), (0, 7, 11, 8)), (100, 12, 100, ("int16",), (0, 7, 11)),
-    (112, 12, 112, ("int16",), (0, 7, 11, 8)), (120, 12, 120, ("int16",), (0, 7, 11)), (160, 12, 160, ("int16",), (0,)),
-    (200, 12, 200, ("int16",), (0, 6)), (250, 12, 250, ("int16",), (0, 6)), (280, 12, 280, ("int16",), (0, 6)),
-    (320, 12, 320, ("int16",), (0, 6)), (400, 12, 400, ("int16",), (0, 6)), (500, 12, 500, ("int16",), (0, 6)),
-    (512, 12, 512, ("int16",), (0, 6)),
-]
-
-
-FMT = {"int8": L.PFB_FMT_INT8_IQ, "int16": L.PFB_FMT_INT16_IQ, "cf32": L.PFB_FMT_CF32}
 PLANS = L.fast_plans()   # every row of the fused-kernel table (tests/test_plan_table_cpu.py checks SHAPES covers them)
 
 

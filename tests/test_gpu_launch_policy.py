@@ -6,11 +6,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from plan_support import FMT_NAME  # noqa: E402
 from sdr_channelizer_amd import Channelizer  # noqa: E402
 from sdr_channelizer_amd import _lib as L  # noqa: E402
 
 PLANS = L.fast_plans()
-FMT_NAME = {L.PFB_FMT_INT8_IQ: "int8", L.PFB_FMT_INT16_IQ: "int16", L.PFB_FMT_CF32: "cf32"}
 FIELDS = [f for f, _ in L.PfbLaunchReport._fields_]
 
 

@@ -10,26 +10,10 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle.pfb_oracle import OracleConfig  # noqa: E402
+from plan_support import REL_TOL, oracle_run, rel  # noqa: E402
 from sdr_channelizer_amd import Channelizer, synth  # noqa: E402
 from sdr_channelizer_amd import _lib as L  # noqa: E402
 
-REL_TOL = 1e-5  # north star: <= 1e-5 relative error
-
-
-def rel(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def oracle_run(oracle, iq, h, M, P, D, bw, fmt="int", **kw):
-    if fmt == "cf32":
-        x = iq[:, 0].astype(np.float64) + 1j * iq[:, 1].astype(np.float64)
-    else:
-        x = oracle.unpack(iq, bw)
-    method = "fft" if (M & (M - 1)) == 0 else "polyphase"
-    return oracle.channelize(x, np.asarray(h, dtype=np.float64), OracleConfig(M, P, D, **kw), method)
-
-
-FMT_NAME = {"int8": "int8", "int16": "int16", "cf32": "cf32"}
 # band counts M = 2^a 3^b 5^c 7^d that are plausible radio rates (numBands = fs * 1e-6, channelizer_example.m:29;
 # round(fs / 0.1e6), generate_channelized_training_iq.m:95-96): the fused shapes of csrc/pfb_kernels_mixed.hip
 MIXED_RADIX_BANDS = (12, 24, 25, 30, 48, 50, 80, 96, 100, 112, 120, 160, 200, 250, 280, 320, 400, 500, 512)

@@ -7,71 +7,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from pdw_checks import compare, synthetic_matrix  # noqa: E402
 from sdr_channelizer_amd import Channelizer, synth  # noqa: E402
 from sdr_channelizer_amd.pdw import extract_pdws, extract_pdws_raw  # noqa: E402
-
-
-def compare(got, want, fs, phase_col=None):
-    """phase_col(i) -> the complex samples pulse i's phase steps are taken over: lets the caller's data excuse the one
-    ill-conditioned point of the reference algorithm (see antipodal_slack)."""
-    assert len(got) == len(want), (len(got), len(want))
-    w = {k: np.array([p[k] for p in want]) for k in ("toa", "freq", "pw", "snr", "sat", "bin")}
-    assert np.array_equal(got["bin"], w["bin"])
-    assert np.array_equal(got["sat"] != 0, w["sat"].astype(bool))
-    assert np.allclose(got["toa"], w["toa"], rtol=0, atol=1e-9 / fs + 1e-12 * np.abs(w["toa"]).max(initial=1.0))
-    assert np.allclose(got["pw"], w["pw"], rtol=1e-12, atol=0)
-    assert np.allclose(got["snr"], w["snr"], rtol=1e-9, atol=1e-9, equal_nan=True)
-    bad = ~np.isclose(got["freq"], w["freq"], rtol=1e-9, atol=1e-6, equal_nan=True)
-    if phase_col is not None:
-        for i in np.flatnonzero(bad):
-            bad[i] = not antipodal_slack(phase_col(i), float(got["freq"][i]), float(w["freq"][i]), fs)
-    assert not bad.any(), (np.flatnonzero(bad), got["freq"][bad], w["freq"][bad])
-    assert np.allclose(got["mag"], np.array([p["mag"] for p in want]), rtol=1e-12, atol=0)
-
-
-def antipodal_slack(col, got_freq, want_freq, fs):
-    """create_pdws_channelized.m:114-117 wraps each phase step at +-180 degrees and takes the median.  Two consecutive
-    samples that are exact negative multiples of each other (quantised data has them) step by 180 +- 1 ulp, so the
-    last bit of atan2 decides between +180 and -180 there; the device's libm, this host's (the oracle) and numpy's all
-    differ in that bit (so would MATLAB's).  Every assignment of +-180 to those steps gives one legitimate median:
-    accept a device result whose distance from the oracle's is the distance between two of them, and nothing else."""
-    c = np.asarray(col, np.complex128)
-    d = np.diff(np.arctan2(c.imag, c.real) * (180.0 / np.pi))
-    anti = np.flatnonzero(np.abs(np.abs(d) - 180.0) < 1e-9)
-    if len(anti) == 0:
-        return False
-    d[d < -180.0] += 360.0
-    d[d > 180.0] -= 360.0
-    delta = 360.0 * (got_freq - want_freq) / fs   # freq = base + fs * med / 360
-    tol = 360.0 * (1e-9 * abs(want_freq) + 1e-6) / fs
-    if len(anti) > 10:  # too many assignments to list: the median is monotone in every step, so bound it
-        lo, hi = d.copy(), d.copy()
-        lo[anti], hi[anti] = -180.0, 180.0
-        return abs(delta) <= np.median(hi) - np.median(lo) + tol
-    meds = []
-    for bits in range(1 << len(anti)):
-        e = d.copy()
-        e[anti] = [180.0 if (bits >> j) & 1 else -180.0 for j in range(len(anti))]
-        meds.append(np.median(e))
-    meds = np.array(meds)
-    return bool((np.abs((meds[:, None] - meds[None, :]) - delta) <= tol).any())
-
-
-def synthetic_matrix(F=6000, M=16, seed=0):
-    rng = np.random.default_rng(seed)
-    y = 0.01 * (rng.standard_normal((F, M)) + 1j * rng.standard_normal((F, M)))
-    def pulse(b, a, n, amp=0.5, dphi=25.0):
-        y[a:a + n, b] += amp * np.exp(1j * np.deg2rad(dphi) * np.arange(n))
-    pulse(3, 100, 51)
-    pulse(3, 400, 7, dphi=-140.0)        # wraps past +-180 degrees
-    pulse(3, 500, 1)                     # single-frame pulse
-    pulse(5, 480, 80)                    # crosses the 512-frame tile boundary
-    pulse(5, 1000, 1500, amp=0.3)        # longer than the LDS cache, crosses several tiles
-    pulse(0, 2000, 40, amp=1.2)          # saturates (|re| or |im| >= 0.9999 inside)
-    pulse(M - 1, 0, 30)                  # starts on the very first frame
-    pulse(M - 1, F - 20, 20)             # still active at the end of the data: no PDW
-    pulse(9, 3000, 64); pulse(9, 3064 + 1, 10)  # one-frame gap between pulses
-    return y.astype(np.complex64)
 
 
 @pytest.mark.parametrize("quirks,unshifted", [(True, False), (False, False), (True, True), (False, True)])

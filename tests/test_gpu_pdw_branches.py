@@ -10,16 +10,16 @@ designed to land on them -- tests/pdw_cases.py, whose designs tests/test_pdw_cas
      identity over whole segments; tile_words 32 and 64 (the first wave-per-tile size)
   E  noise-floor path 4: the undecided list overflows and the device redoes the masks
 
-Everything is an exact integer outcome or goes through test_gpu_pdw.py's compare, unchanged and without phase_col."""
+Everything is an exact integer outcome or goes through pdw_checks.py's compare, unchanged and without phase_col."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 import pdw_cases as pc  # noqa: E402
+from pdw_checks import check_case, compare  # noqa: E402
 from sdr_channelizer_amd import _lib as L, synth  # noqa: E402
 from sdr_channelizer_amd.pdw import extract_pdws, extract_pdws_raw  # noqa: E402
-from test_gpu_pdw import compare  # noqa: E402
 
 _WANT = {}   # the oracle's answer per case, computed once and shared by the host- and device-input runs
 
@@ -45,14 +45,7 @@ def run_library(case, where):
 
 def check(oracle, case, where):
     got, nf = run_library(case, where)
-    want, want_nf = oracle_of(oracle, case)
-    if case.kind == "raw":
-        assert nf == pytest.approx(want_nf, rel=1e-14)
-    else:
-        assert np.allclose(nf, want_nf, rtol=1e-12, atol=0)
-    assert len(got) == case.count, (len(got), case.count)
-    compare(got, want, case.fs)
-    assert pc.triples(got, case.fs) == case.pulses
+    check_case(case, got, nf, *oracle_of(oracle, case))
     return got
 
 

@@ -7,8 +7,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from pdw_checks import compare  # noqa: E402
 from sdr_channelizer_amd.pdw import extract_pdws, extract_pdws_raw  # noqa: E402
-from test_gpu_pdw import compare  # noqa: E402
 
 CASES = int(os.environ.get("PFB_FUZZ_CASES", "40"))
 

@@ -22,10 +22,10 @@ pytestmark = pytest.mark.gpu
 
 import dwell_ref  # noqa: E402
 import pdw_cases as pc  # noqa: E402
+from gpu_support import cuda_torch  # noqa: E402
+from pdw_checks import FC, FS, check_case, check_mean, threshold_db  # noqa: E402
 from sdr_channelizer_amd import _lib as L, analyze_dwell  # noqa: E402
 from sdr_channelizer_amd.pdw import extract_pdws, extract_pdws_raw  # noqa: E402
-from test_gpu_dwell import FC, FS, check_mean, threshold_db  # noqa: E402
-from test_gpu_pdw import compare  # noqa: E402
 
 ORDER = "ABCDEACBED"
 
@@ -114,10 +114,7 @@ class Calls:
 
 @pytest.fixture(scope="module")
 def calls():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return Calls(torch)
+    return Calls(cuda_torch())
 
 
 @pytest.fixture(scope="module")
@@ -131,28 +128,17 @@ def alone(calls):
     return res
 
 
-def check_oracle(oracle, case, got, nf):
-    """tests/test_gpu_pdw_branches.py::check on a result already in hand"""
-    want, want_nf = pc.run_oracle(oracle, case)
-    if case.kind == "raw":
-        assert nf == pytest.approx(want_nf, rel=1e-14)
-    else:
-        assert np.allclose(nf, want_nf, rtol=1e-12, atol=0)
-    assert len(got) == case.count, (len(got), case.count)
-    compare(got, want, case.fs)
-    assert pc.triples(got, case.fs) == case.pulses
-
-
 def test_raw_alone_matches_the_oracle(oracle, calls, alone):
     got, (nf,) = alone["A"]
-    check_oracle(oracle, calls.a, got, nf)
+    check_case(calls.a, got, nf, *pc.run_oracle(oracle, calls.a))
 
 
 @pytest.mark.parametrize("name,path", [("B", 1), ("C", 2)])
 def test_channelized_alone_matches_the_oracle(oracle, calls, alone, name, path):
     got, (nf, took) = alone[name]
     assert took == path
-    check_oracle(oracle, calls.b if name == "B" else calls.c, got, np.frombuffer(nf, np.float64))
+    case = calls.b if name == "B" else calls.c
+    check_case(case, got, np.frombuffer(nf, np.float64), *pc.run_oracle(oracle, case))
 
 
 def test_dwell_mean_alone_matches_the_reference(calls, alone):

@@ -13,13 +13,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from sdr_channelizer_amd import Channelizer, synth  # noqa: E402
+from plan_support import (BPS, FMT_NAME, REL_TOL, device_input, draw_bit_width, draw_switches, draw_taps,  # noqa: E402
+                          family_rows, oracle_for, plan_handle)
 from sdr_channelizer_amd import _lib as L  # noqa: E402
-from test_gpu_parity import REL_TOL, oracle_run  # noqa: E402
 
 PLANS = L.fast_plans()
-FMT_NAME = {L.PFB_FMT_INT8_IQ: "int8", L.PFB_FMT_INT16_IQ: "int16", L.PFB_FMT_CF32: "cf32"}
-BPS = {"int8": 2, "int16": 4, "cf32": 8}
 RUNGS = 12           # call lengths per row, geometric from a few chunks to the top
 NWIN = 16            # frames per oracle window
 TOP_SAMPLES = 1 << 24   # the shortest top call, in input samples: what a caller hands over as one record
@@ -58,27 +56,10 @@ def row_setup(row):
     d = PLANS[row]
     fmt = FMT_NAME[d.sample_format]
     rng = np.random.default_rng(52000 + row)
-    bw = 1 if fmt == "cf32" else 8 if fmt == "int8" else int(rng.choice([12, 16]))
-    h = (rng.standard_normal(d.M * d.P) / d.M).astype(np.float32)
-    kw = dict(fftshift=bool(rng.integers(2)), conjugate_input=bool(rng.integers(2)),
-              derotate=(d.D != d.M) and bool(rng.integers(2)), input_offset=int(rng.integers(-1, d.D)))
+    bw = draw_bit_width(rng, fmt)
+    h = draw_taps(rng, d.M, d.P)
+    kw = draw_switches(rng, d)
     return d, fmt, bw, h, kw, rng
-
-
-def make_input(n, fmt, bw, seed):
-    import torch
-    if fmt == "cf32":
-        g = torch.Generator(device="cuda")
-        g.manual_seed(seed)
-        return torch.randn((n, 2), dtype=torch.float32, device="cuda", generator=g)
-    return synth.pulsed_iq_torch(n, bw, torch.int8 if fmt == "int8" else torch.int16, seed=seed, device="cuda")
-
-
-def make_handle(d, fmt, bw, h, kw, **extra):
-    ch = Channelizer(d.M, taps=h, decimation=d.D, sample_format=fmt, bit_width=bw, **kw, **extra)
-    ch.set_option(L.PFB_OPT_KERNEL, 2)   # the fused plan or an error, never the generic kernel
-    ch.set_option(L.PFB_OPT_VARIANT, d.variant)
-    return ch
 
 
 def window_error(oracle, iq, got, f0, d, fmt, bw, h, kw):
@@ -89,8 +70,7 @@ def window_error(oracle, iq, got, f0, d, fmt, bw, h, kw):
     f_lo = max(0, f0 - (M * P + D - 1) // D - 1)
     f_lo -= f_lo % period
     seg = iq[f_lo * D:(f0 + NWIN) * D].cpu().numpy()
-    want = oracle_run(oracle, seg, h, M, P, D, bw, "cf32" if fmt == "cf32" else "int", fftshift=kw["fftshift"],
-                      conj_input=kw["conjugate_input"], derotate=kw["derotate"], off=kw["input_offset"])[-NWIN:]
+    want = oracle_for(oracle, seg, h, d, fmt, bw, kw)[-NWIN:]
     g = got[f0:f0 + NWIN].cpu().numpy()
     assert g.shape == want.shape
     return float(np.abs(g - want).max() / np.abs(want).max())
@@ -106,7 +86,7 @@ def test_registered_plan_at_record_size(oracle, row):
     handles = []
 
     def handle(**extra):
-        handles.append(make_handle(d, fmt, bw, h, kw, **extra))
+        handles.append(plan_handle(d, fmt, bw, h, kw, **extra))
         return handles[-1]
 
     def call(ch, x, out):
@@ -146,7 +126,7 @@ def test_registered_plan_at_record_size(oracle, row):
         torch.cuda.empty_cache()
 
         tails = [int(rng.integers(1, D)) if D > 1 else 0 for _ in lens]
-        iq = make_input(top * D + tails[-1], fmt, bw, int(rng.integers(1 << 30)))
+        iq = device_input(top * D + tails[-1], fmt, bw, int(rng.integers(1 << 30)))
         ref = handle()
         ref.set_option(L.PFB_OPT_FRAMES_PER_BLOCK, 2 * c)   # the shortest legal run
         want = ref(iq)
@@ -226,11 +206,7 @@ def test_registered_plan_at_record_size(oracle, row):
         torch.cuda.empty_cache()
 
 
-def family(d):
-    return (d.default_schedule, d.sample_format, d.D == d.M)
-
-
-FAMILY_ROWS = [i for i, d in enumerate(PLANS) if family(d) not in {family(e) for e in PLANS[:i]}]
+FAMILY_ROWS = family_rows(PLANS)
 
 
 @pytest.mark.parametrize("row", FAMILY_ROWS, ids=[PLANS[i].name.decode() for i in FAMILY_ROWS])
@@ -251,14 +227,14 @@ def test_more_than_2_to_31_output_elements(oracle, row):
         pytest.skip(f"needs {need >> 30} GiB of HBM")
     handles = []
     try:
-        iq = make_input(n, fmt, bw, int(rng.integers(1 << 30)))
+        iq = device_input(n, fmt, bw, int(rng.integers(1 << 30)))
         nbytes = iq.numel() * iq.element_size()
         if D * BPS[fmt] >= 2 * M:   # two input bytes or more per output element
             assert nbytes > (1 << 32), (name, nbytes)
         else:
             assert nbytes > (1 << 31), (f"{name}: 2^31 outputs of a row with D = {D}, M = {M} at {BPS[fmt]} bytes a sample "
                                         f"take {nbytes} input bytes, short of 2^32: only its output offsets cross", nbytes)
-        ch = make_handle(d, fmt, bw, h, kw)
+        ch = plan_handle(d, fmt, bw, h, kw)
         handles.append(ch)
         y = ch(iq)
         rep = ch.last_launch
@@ -274,7 +250,7 @@ def test_more_than_2_to_31_output_elements(oracle, row):
             err = window_error(oracle, iq, y, f0, d, fmt, bw, h, kw)
             assert err < REL_TOL, (name, f0, err)
 
-        ref = make_handle(d, fmt, bw, h, kw)
+        ref = plan_handle(d, fmt, bw, h, kw)
         handles.append(ref)
         ref.set_option(L.PFB_OPT_FRAMES_PER_BLOCK, 2 * c)
         other = ref(iq)
@@ -282,7 +258,7 @@ def test_more_than_2_to_31_output_elements(oracle, row):
         for f0 in range(0, F, rows):
             assert torch.equal(y[f0:f0 + rows], other[f0:f0 + rows]), (name, f0)
 
-        cm = make_handle(d, fmt, bw, h, kw, channel_major=True)
+        cm = plan_handle(d, fmt, bw, h, kw, channel_major=True)
         handles.append(cm)
         y_cm = cm(iq, out=other.reshape(-1))
         rep = cm.last_launch

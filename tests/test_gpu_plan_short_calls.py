@@ -5,10 +5,10 @@ tests/test_gpu_plan_at_size.py starts its ladder at K = 4 c + 3 frames (c = the 
 every call length below that, so the two meet at K with no gap:
 
 * the stream walk: one stream cut into calls of 0, 1, 2, ... K frames, every count up to 2 c + 1 both from a frame
-  boundary and from a carried phase, calls of 1, D - 1, history - 1 and history samples (walk_lengths; its coverage is
-  checked on any machine by tests/test_plan_table_cpu.py) -- frame-major complex and magnitude, channel-major through
-  the default route and by slabs, through host pointers in one-frame staging chunks, and every schedule on the calls
-  of up to 2 c + 1 frames plus one of K (sweep_lengths);
+  boundary and from a carried phase, calls of 1, D - 1, history - 1 and history samples (plan_support.walk_lengths; its
+  coverage is checked on any machine by tests/test_plan_table_cpu.py) -- frame-major complex and magnitude,
+  channel-major through the default route and by slabs, through host pointers in one-frame staging chunks, and every
+  schedule on the calls of up to 2 c + 1 frames plus one of K (sweep_lengths);
 * the fresh walk: a reset handle and ONE call of F frames, F = 1 ... K: no history, a first run that is the last;
 * the split launch: pfb_process_shard_async on a world of one -- interior frames [head, F) with their history in the
   input, then the head frames over an input of the whole segment -- on segments from the smallest legal one up,
@@ -19,77 +19,23 @@ oracle once (the project's bound, REL_TOL); everything else is bit equality agai
 from pfb_last_launch; the policy's arithmetic is not repeated.
 
 Nothing was shortened: every row runs the full schedule sweep.  Measured on an MI355X: see SLOWEST below."""
+import functools
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-from sdr_channelizer_amd import Channelizer, synth  # noqa: E402
+from gpu_support import Mailbox  # noqa: E402
+from plan_support import (BPS, FMT_NAME, REL_TOL, SCHEDULES, draw_bit_width, draw_switches, draw_taps,  # noqa: E402
+                          family_rows, host_input, oracle_for, plan_handle, rel, sweep_lengths, top_frames, walk_lengths)
 from sdr_channelizer_amd import _lib as L  # noqa: E402
-from test_gpu_parity import REL_TOL, oracle_run, rel  # noqa: E402
-from test_gpu_plan_at_size import FAMILY_ROWS  # noqa: E402
-from test_gpu_plan_table import SCHEDULES  # noqa: E402
 
 PLANS = L.fast_plans()
 IDS = [d.name.decode() for d in PLANS]
-FMT_NAME = {L.PFB_FMT_INT8_IQ: "int8", L.PFB_FMT_INT16_IQ: "int16", L.PFB_FMT_CF32: "cf32"}
-BPS = {"int8": 2, "int16": 4, "cf32": 8}
+FAMILY_ROWS = family_rows(PLANS)
 # wall time of the slowest rows on an MI355X (pytest --durations): the three M = 8 rows (c = 64, K = 259)
 SLOWEST = "stream walk 2.4 s (pfb_fast<M8,P12,D8,int8>; M = 10: 1.4 s); every other test of the module below 0.4 s; all 189: 21 s"
-
-
-def top_frames(c):
-    """K: the longest call of the walk = the shortest rung of tests/test_gpu_plan_at_size.py's ladder."""
-    return 4 * c + 3
-
-
-def walk_lengths(D, K, hist_samples, both=None):
-    """Call lengths in samples which, played in order from a reset handle, produce
-    * every frame count 0 ... K,
-    * every count 1 ... `both` (default (K - 1) // 2, which is 2 c + 1 for K = 4 c + 3) once from a frame boundary and
-      once from a carried phase; the counts above alternate between the two,
-    * a call that leaves phase D - 1 behind,
-    * an empty call and calls of 1, D - 1, hist_samples - 1 and hist_samples samples.
-    Pure arithmetic: frames = (phase + n) // D, phase = (phase + n) % D."""
-    assert D >= 2 and K >= 1 and hist_samples > D
-    both = (K - 1) // 2 if both is None else both
-    lens, phase = [], 0
-
-    def call(n):
-        nonlocal phase
-        lens.append(n)
-        phase = (phase + n) % D
-
-    call(0)
-    call(1)                  # no frame; carries one sample
-    call(D - 1)              # the frame that sample began
-    call(hist_samples - 1)   # one sample short of replacing the whole history
-    call(hist_samples)
-    if phase:
-        call(D - phase)      # back onto a frame boundary
-    for F in range(1, K + 1):
-        r = D - 1 if F == 1 else 1 + (7 * F) % (D - 1)   # 1 ... D - 1 samples over
-        if F <= both:
-            call(F * D + r)        # F frames from a boundary ...
-            call(F * D - r)        # ... and F frames from phase r, back onto a boundary
-        elif phase == 0:
-            call(F * D + r)
-        else:
-            call(F * D - phase)
-    return lens
-
-
-def sweep_lengths(D, c, hist_samples):
-    """The shorter walk of the schedule sweep: every count 0 ... 2 c + 1 in both phase classes, then one call of K."""
-    lens = walk_lengths(D, 2 * c + 1, hist_samples, both=2 * c + 1)
-    assert sum(lens) % D == 0   # it ends on a boundary
-    return lens + [top_frames(c) * D + D // 2]
-
-
-def make_iq(n, fmt, bw, rng):
-    if fmt == "cf32":
-        return rng.standard_normal((n, 2)).astype(np.float32)
-    return synth.pulsed_iq_numpy(n, bw, np.int8 if fmt == "int8" else np.int16, seed=int(rng.integers(1 << 30)))
 
 
 class Row:
@@ -101,10 +47,9 @@ class Row:
         self.name, self.fmt = d.name.decode(), FMT_NAME[d.sample_format]
         M, P, D, c = d.M, d.P, d.D, d.chunk_frames
         rng = np.random.default_rng(73000 + row)
-        self.kw = dict(fftshift=bool(rng.integers(2)), conjugate_input=bool(rng.integers(2)),
-                       derotate=(D != M) and bool(rng.integers(2)), input_offset=int(rng.integers(-1, D)))
-        self.bw = 1 if self.fmt == "cf32" else 8 if self.fmt == "int8" else int(rng.choice([12, 16]))
-        self.h = (rng.standard_normal(M * P) / M).astype(np.float32)
+        self.kw = draw_switches(rng, d)
+        self.bw = draw_bit_width(rng, self.fmt)
+        self.h = draw_taps(rng, M, P)
         self.K = top_frames(c)
         with self.handle() as ch:
             self.hist = ch.history_samples
@@ -112,12 +57,10 @@ class Row:
         self.sweep = sweep_lengths(D, c, self.hist)
         n = sum(self.lens)
         assert n >= sum(self.sweep) and n >= self.K * D + D - 1
-        self.iq = make_iq(n, self.fmt, self.bw, rng)
+        self.iq = host_input(rng, n, self.fmt, self.bw)
         self.d_iq = torch.from_numpy(self.iq).cuda()
         self.fresh_tails = [int(x) for x in rng.integers(0, D, size=self.K + 1)]
-        ref = oracle_run(oracle, self.iq, self.h, M, P, D, self.bw, "cf32" if self.fmt == "cf32" else "int",
-                         fftshift=self.kw["fftshift"], conj_input=self.kw["conjugate_input"],
-                         derotate=self.kw["derotate"], off=self.kw["input_offset"])
+        ref = oracle_for(oracle, self.iq, self.h, d, self.fmt, self.bw, self.kw)
         # the references: the whole stream in one call at the shortest legal run length, against the oracle
         self.want = {}
         for mode, extra in (("complex", {}), ("magnitude", dict(magnitude=True))):
@@ -136,11 +79,7 @@ class Row:
         self.want_host = self.want["complex", False].cpu().numpy()
 
     def handle(self, **extra):
-        d = self.d
-        ch = Channelizer(d.M, taps=self.h, decimation=d.D, sample_format=self.fmt, bit_width=self.bw, **self.kw, **extra)
-        ch.set_option(L.PFB_OPT_KERNEL, 2)   # the fused plan or an error, never the generic kernel
-        ch.set_option(L.PFB_OPT_VARIANT, d.variant)
-        return ch
+        return plan_handle(self.d, self.fmt, self.bw, self.h, self.kw, **extra)
 
 
 _ROWS = {}
@@ -257,22 +196,16 @@ def test_split_launch_of_a_shard(row):
     d = PLANS[row]
     name, fmt, D = d.name.decode(), FMT_NAME[d.sample_format], d.D
     rng = np.random.default_rng(74000 + row)
-    kw = dict(fftshift=bool(rng.integers(2)), conjugate_input=bool(rng.integers(2)),
-              derotate=(D != d.M) and bool(rng.integers(2)), input_offset=int(rng.integers(-1, D)))
-    bw = 1 if fmt == "cf32" else 8 if fmt == "int8" else int(rng.choice([12, 16]))
-    h = (rng.standard_normal(d.M * d.P) / d.M).astype(np.float32)
-
-    def handle(**extra):
-        ch = Channelizer(d.M, taps=h, decimation=D, sample_format=fmt, bit_width=bw, **kw, **extra)
-        ch.set_option(L.PFB_OPT_KERNEL, 2)
-        ch.set_option(L.PFB_OPT_VARIANT, d.variant)
-        return ch
+    kw = draw_switches(rng, d)
+    bw = draw_bit_width(rng, fmt)
+    h = draw_taps(rng, d.M, d.P)
+    handle = functools.partial(plan_handle, d, fmt, bw, h, kw)
 
     with handle() as probe:
         head, hist = probe.shard_head_frames, probe.history_samples
     segs = shard_segments(d, head, hist, rng)
     pre, after = head + 3, 3   # frames of the plain calls in front of the first segment and behind each
-    d_iq = torch.from_numpy(make_iq((pre + sum(segs) + after * len(segs)) * D, fmt, bw, rng)).cuda()
+    d_iq = torch.from_numpy(host_input(rng, (pre + sum(segs) + after * len(segs)) * D, fmt, bw)).cuda()
     modes = (("frame-major complex", {}), ("frame-major magnitude", dict(magnitude=True)),
              ("channel-major complex", dict(channel_major=True)))
     for what, extra in modes:
@@ -300,30 +233,23 @@ def test_split_launch_of_a_shard(row):
 
 @pytest.mark.parametrize("row", FAMILY_ROWS, ids=[IDS[i] for i in FAMILY_ROWS])
 def test_two_ranks_on_the_smallest_segments(row):
-    """Two shards of the smallest legal length, the halo through the matched transport of tests/test_gpu_sharded.py:
+    """Two shards of the smallest legal length, the halo through the matched transport of tests/gpu_support.py:
     neither segment has an interior, rank 1's head frames read the landing zone; the stream of one handle, bit for bit."""
     import torch
-    from test_gpu_sharded import Mailbox
     d = PLANS[row]
     name, fmt, D = d.name.decode(), FMT_NAME[d.sample_format], d.D
     rng = np.random.default_rng(75000 + row)
-    kw = dict(fftshift=bool(rng.integers(2)), conjugate_input=bool(rng.integers(2)),
-              derotate=(D != d.M) and bool(rng.integers(2)), input_offset=int(rng.integers(-1, D)))
-    bw = 1 if fmt == "cf32" else 8 if fmt == "int8" else int(rng.choice([12, 16]))
-    h = (rng.standard_normal(d.M * d.P) / d.M).astype(np.float32)
-
-    def handle(**extra):
-        ch = Channelizer(d.M, taps=h, decimation=D, sample_format=fmt, bit_width=bw, **kw, **extra)
-        ch.set_option(L.PFB_OPT_KERNEL, 2)
-        ch.set_option(L.PFB_OPT_VARIANT, d.variant)
-        return ch
+    kw = draw_switches(rng, d)
+    bw = draw_bit_width(rng, fmt)
+    h = draw_taps(rng, d.M, d.P)
+    handle = functools.partial(plan_handle, d, fmt, bw, h, kw)
 
     for cm in (False, True):
         hs = [handle(channel_major=cm) for _ in range(2)]
         try:
             head, hist, halo = hs[0].shard_head_frames, hs[0].history_samples, hs[0].halo_samples
             F = max(head, -(-hist // D))
-            d_iq = torch.from_numpy(make_iq(2 * F * D, fmt, bw, rng)).cuda()
+            d_iq = torch.from_numpy(host_input(rng, 2 * F * D, fmt, bw)).cuda()
             with handle(channel_major=cm) as one:
                 want = one(d_iq)
                 assert one.last_kernel == name

@@ -7,14 +7,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from sdr_channelizer_amd import Channelizer, synth  # noqa: E402
+from plan_support import (FMT_NAME, REL_TOL, SCHEDULES, draw_bit_width, draw_switches, draw_taps, host_input,  # noqa: E402
+                          oracle_for, plan_handle, rel)
 from sdr_channelizer_amd import _lib as L  # noqa: E402
-from test_gpu_parity import REL_TOL, oracle_run, rel  # noqa: E402
 
 PLANS = L.fast_plans()
-FMT_NAME = {L.PFB_FMT_INT8_IQ: "int8", L.PFB_FMT_INT16_IQ: "int16", L.PFB_FMT_CF32: "cf32"}
-# every schedule pfb_set_option accepts but 9 (channel-major by slabs): a plan without one runs its sliding runs
-SCHEDULES = (-1, 0, 2, 3, 4, 6, 7, 8, 11, 13)
 SLAB_FRAMES = (0, 64)   # 0: one slab for the whole call; 64: several, the later ones reading their history from the input
 
 
@@ -26,27 +23,16 @@ def test_registered_plan_against_the_oracle(oracle, row):
     rng = np.random.default_rng(31000 + row)
     frames = int(rng.integers(200, 400))
     n = frames * D + int(rng.integers(1, D))   # a ragged tail
-    if fmt == "cf32":
-        iq, bw = rng.standard_normal((n + 1, 2)).astype(np.float32), 1
-    else:
-        bw = 8 if fmt == "int8" else int(rng.choice([12, 16]))
-        iq = synth.pulsed_iq_numpy(n + 1, bw, np.int8 if fmt == "int8" else np.int16, seed=int(rng.integers(1 << 30)))
+    bw = draw_bit_width(rng, fmt)
+    iq = host_input(rng, n + 1, fmt, bw)
     iq_pad, iq = iq, iq[1:]   # iq_pad on the device, one sample in, is the misaligned input of (d)
-    h = (rng.standard_normal(M * P) / M).astype(np.float32)
-    kw = dict(fftshift=bool(rng.integers(2)), conjugate_input=bool(rng.integers(2)),
-              derotate=(D != M) and bool(rng.integers(2)), input_offset=int(rng.integers(-1, D)))
+    h = draw_taps(rng, M, P)
+    kw = draw_switches(rng, d)
     c1 = 2 * int(rng.integers(n // 10, n // 4)) + 1   # an odd sample
     cuts = [0, c1, int(rng.integers(c1 + D, n - D)), n]
-    want = oracle_run(oracle, iq, h, M, P, D, bw, "cf32" if fmt == "cf32" else "int", fftshift=kw["fftshift"],
-                      conj_input=kw["conjugate_input"], derotate=kw["derotate"], off=kw["input_offset"])
+    want = oracle_for(oracle, iq, h, d, fmt, bw, kw)
     mag_want = np.abs(want)
     peak = float(mag_want.max())
-
-    def handle(**extra):
-        ch = Channelizer(M, taps=h, decimation=D, sample_format=fmt, bit_width=bw, **kw, **extra)
-        ch.set_option(L.PFB_OPT_KERNEL, 2)   # the fused plan or an error, never the generic kernel
-        ch.set_option(L.PFB_OPT_VARIANT, d.variant)
-        return ch
 
     def run(ch, channel_major=False):
         ch.reset()
@@ -60,8 +46,8 @@ def test_registered_plan_against_the_oracle(oracle, row):
     fm, handles = {}, {}
     try:
         for mode, extra in modes.items():
-            handles[mode, False] = handle(**extra)
-            handles[mode, True] = handle(channel_major=True, **extra)
+            handles[mode, False] = plan_handle(d, fmt, bw, h, kw, **extra)
+            handles[mode, True] = plan_handle(d, fmt, bw, h, kw, channel_major=True, **extra)
         # (a) every output mode against the oracle, in both layouts; (c) the default channel-major route gives the
         # transposed frame-major bits
         for mode in modes:

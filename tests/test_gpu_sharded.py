@@ -6,7 +6,6 @@ sharded == single stream, bit for bit.
   frames first, head frames behind the event, ring and open chains, oversampled banks whose halo is not a whole
   number of frames;
 * two devices over the nccl backend (RCCL), one process per GPU, skipped when the box has fewer than two GPUs."""
-import ctypes as C
 import os
 import socket
 import subprocess
@@ -17,74 +16,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from gpu_support import Mailbox  # noqa: E402
 from sdr_channelizer_amd import Channelizer, synth  # noqa: E402
 from sdr_channelizer_amd import _lib as L  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_hip = None
-
-
-def hip_memcpy_async(dst, src, nbytes, stream):
-    global _hip
-    if _hip is None:
-        _hip = C.CDLL("libamdhip64.so")  # the runtime torch already loaded
-        _hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    rc = _hip.hipMemcpyAsync(C.c_void_p(dst), C.c_void_p(src), nbytes, 3, C.c_void_p(stream))  # 3 = device to device
-    assert rc == 0, rc
-
-
-class Mailbox:
-    """Single-process stand-in for a MATCHED transport (what ncclSend / ncclRecv or batch_isend_irecv are): the `world`
-    handles run their shard calls on `world` host threads (ctypes drops the GIL around the library call; the callback
-    takes it back), and inside the callbacks rank r's send of call i meets rank r+1's receive of call i -- sends park
-    the tail in slot r (a copy on the side stream the library handed over, waited for), everybody meets at a barrier,
-    receives copy their predecessor's slot into the landing zone, and a second barrier keeps call i+1's sends out of the
-    slots until everyone has read."""
-
-    def __init__(self, world, nbytes):
-        import threading
-        import torch
-        self.world = world
-        self.slots = [torch.zeros(nbytes, dtype=torch.uint8, device="cuda") for _ in range(world)]
-        self.calls = []
-        self.barrier = threading.Barrier(world)
-
-    def exchange_for(self, rank):
-        def exchange(d_send, d_recv, nbytes, send_to, recv_from, stream):
-            import torch
-            self.calls.append((rank, bool(d_send), bool(d_recv), nbytes, send_to, recv_from))
-            if send_to >= 0:
-                assert d_send
-                hip_memcpy_async(self.slots[rank].data_ptr(), d_send, nbytes, stream)
-                torch.cuda.synchronize()
-            self.barrier.wait(timeout=60)
-            if recv_from >= 0:
-                assert d_recv
-                hip_memcpy_async(d_recv, self.slots[recv_from].data_ptr(), nbytes, stream)
-                torch.cuda.synchronize()
-            self.barrier.wait(timeout=60)
-            return 0
-        return exchange
-
-    def run(self, fns):
-        """fns[r](): rank r's shard call; all of them at once, like `world` processes."""
-        import threading
-        out, err = [None] * len(fns), []
-
-        def go(r):
-            try:
-                out[r] = fns[r]()
-            except Exception as e:  # noqa: BLE001
-                err.append((r, repr(e)))
-                self.barrier.abort()
-
-        ts = [threading.Thread(target=go, args=(r,)) for r in range(len(fns))]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-        assert not err, err
-        return out
 
 
 @pytest.mark.parametrize("M,P,D,fmt,bw,kw", [

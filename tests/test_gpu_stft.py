@@ -10,6 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import stft_ref  # noqa: E402
+from gpu_support import cuda_torch  # noqa: E402
 from sdr_channelizer_amd import Channelizer, Stft, iqfile, spectrogram_from_iq_file, stft, synth  # noqa: E402
 from sdr_channelizer_amd import _lib as L  # noqa: E402
 
@@ -19,10 +20,7 @@ FORMATS = (("int8", 8), ("int16", 12), ("int16", 16), ("cf32", 1))
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch
+    return cuda_torch()
 
 
 def raw_input(fmt, bw, n, seed):

@@ -7,13 +7,11 @@ import re
 
 import pytest
 
+from plan_support import FMT, SCHEDULES, SHAPES, sweep_lengths, top_frames, walk_lengths
 from sdr_channelizer_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMT = {"int8": L.PFB_FMT_INT8_IQ, "int16": L.PFB_FMT_INT16_IQ, "cf32": L.PFB_FMT_CF32}
 NAME_RE = re.compile(r"pfb_fast<M(\d+),P(\d+),D(\d+),(int8|int16|cf32)(?:,(\w+))?>")
-# every value pfb_set_option(PFB_OPT_SCHEDULE) accepts except 9 (channel-major by slabs, a route rather than a schedule)
-SCHEDULES = (-1, 0, 2, 3, 4, 6, 7, 8, 11, 13)
 # the plans a channel-major handle runs by frame-major slabs + the transpose kernel (kChannelMajorOk next to launch_fast in pfb_fast.hpp):
 # the 16-wave plans and the three-pass plans on chunks of 4 or 2 frames, whose fused stores would be 32- / 16-byte runs
 SLAB_PLANS = {
@@ -172,12 +170,11 @@ def test_plan_launch_rejects_bad_arguments():
 
 
 def test_every_shape_is_fuzzed(plans):
-    from test_gpu_fuzz import SHAPES
     fuzzed = {(M, P, D, FMT[f]) for M, P, D, fmts, _ in SHAPES for f in fmts}
     missing = sorted({shape_of(d) for d in plans} - fuzzed)
-    assert not missing, f"registered but not in test_gpu_fuzz.SHAPES: {missing}"
+    assert not missing, f"registered but not in plan_support.SHAPES: {missing}"
     extra = sorted(fuzzed - {shape_of(d) for d in plans})
-    assert not extra, f"in test_gpu_fuzz.SHAPES without a fused plan: {extra}"
+    assert not extra, f"in plan_support.SHAPES without a fused plan: {extra}"
 
 
 def simulate_calls(lens, D):
@@ -193,11 +190,11 @@ def simulate_calls(lens, D):
 
 
 def test_short_call_walk_has_no_hole(plans):
-    """The call lengths tests/test_gpu_plan_short_calls.py plays on every row: every frame count 0 ... K = 4 c + 3,
-    every count up to 2 c + 1 both from a frame boundary and from a carried phase, a call that leaves phase D - 1, and
-    the calls of 1, D - 1, history - 1 and history samples -- for every registered row, so that a plan registered
-    tomorrow is not walked with a hole.  The schedule sweep's shorter walk: 0 ... 2 c + 1 in both classes, and K."""
-    from test_gpu_plan_short_calls import sweep_lengths, top_frames, walk_lengths
+    """The call lengths tests/test_gpu_plan_short_calls.py plays on every row (plan_support.walk_lengths): every frame
+    count 0 ... K = 4 c + 3, every count up to 2 c + 1 both from a frame boundary and from a carried phase, a call that
+    leaves phase D - 1, and the calls of 1, D - 1, history - 1 and history samples -- for every registered row, so that
+    a plan registered tomorrow is not walked with a hole.  The schedule sweep's shorter walk (sweep_lengths): 0 ...
+    2 c + 1 in both classes, and K."""
     for d in plans:
         D, c = d.D, d.chunk_frames
         K, hist = top_frames(c), d.M * d.P + D   # pfb_history_samples: the GPU tests read it from the handle
