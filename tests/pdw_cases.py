@@ -1,13 +1,18 @@
 """Designed inputs for the PDW extractors (plain numpy, no GPU): data built to land on the data-dependent branches of
 sdr_channelizer_amd/csrc/pfb_pdw.hip and its stage headers -- the per-pulse median routes (pfb_pdw_pulse.hpp:
 pdw_pulse_kernel; pfb_pdw_select.hpp: cached_median, block_median and its two tie branches), the saturation scan, the
-identity elements and the word / tile / thread-segment / wave boundaries of the edge scan, and the overflow of the undecided list (noise-floor path 4).
+identity elements and the word / tile / thread-segment / wave boundaries of the edge scan, the overflow of the undecided
+list (noise-floor path 4), and the launch geometry of the channelized extractor on wide banks (pfb_pdw.hip: column
+groups of 64 past the second, the scan kernels' switch, 16-word tiles).
+
+Families: A per-pulse median routes, B saturation position, C edge-scan boundaries, D scan segmentation, E noise-floor
+path 4 (tests/test_gpu_pdw_branches.py), F wide banks on short matrices and G on long ones (tests/test_gpu_pdw_wide.py).
 
 Every builder returns a Case: the input, the extraction arguments, and the designed facts -- the pulses as
 (column, toa0, n) with toa0 the 0-based index of the first sample at or above the leading threshold and
 n = jj - toa0 + 1 counting the trailing below-threshold sample jj as the scripts do -- the PDW count and the intended
-route.  tests/test_pdw_cases_cpu.py proves the designs with the oracle alone; tests/test_gpu_pdw_branches.py runs them
-through the library.
+route.  tests/test_pdw_cases_cpu.py proves the designs with the oracle alone; tests/test_gpu_pdw_branches.py and
+tests/test_gpu_pdw_wide.py run them through the library.
 
 Backgrounds.  Raw streams: integer jitter of +-3 LSB per component (+-1 LSB for int8), whose magnitudes take a handful
 of values, so the median is one of them whatever the pulses add: 2.83 .. 3.2 LSB (1 .. 1.42 LSB for int8).  The
@@ -33,6 +38,8 @@ kPulseCache = 512
 kPulseCacheRaw = 7168
 kCountingMedian = 512
 kUndecided = 1 << 20
+kSampleRows = 65536
+kBracketRows = 1024
 
 FS_RAW = 56e6      # create_pdws.m: the recorder's rate
 FS_IN = 56e6       # create_pdws_channelized.m: rate before the bank
@@ -427,3 +434,121 @@ def path4() -> Case:
         y[a:a + L, c] = _tone(L, gain * med[c] * (1.0 + PATH4_OFFSET)).astype(np.complex64)
         pulses.append((c, a, L + 1))
     return _chan_case("E-path4", y, pulses, True, dict(noise_floor_path=4), dict(med=med, gain=gain))
+
+
+# ---- wide banks ------------------------------------------------------------------------------------------------------
+# Family F is edges_chan(M) at the M of WIDE_M: short (the full-select route), small enough for the oracle as it is.
+#
+# Family G is long as well as wide, out of the oracle's reach as a whole matrix (524 588 x 1024 is 8.6 GB of
+# complex128).  The oracle treats columns independently -- noise floor, edges, amplitude, snr and sat all come from the
+# column itself -- but for the bin's centre frequency, which depends on (bin, M), and, with matlab_quirks, the phase
+# steps, which always come from column 0.  So a wide matrix whose column j is column j mod M0 of a narrow base has an
+# exactly predictable answer from the oracle's run on the base, both runs given the same explicit decimation (WIDE_M0,
+# what Case.fs assumes for the base anyway): for each wide column j, in order, the base's records of column j mod M0
+# with bin = j and freq moved from the base bin's centre frequency to the wide bin's (widen_expected; column 0 of the
+# wide matrix is column 0 of the base, so the rule holds with quirks on).  test_pdw_cases_cpu.py proves the rule with
+# the oracle alone on explicit wide matrices.
+
+WIDE_M = (128, 130, 256, 560, 1024)
+WIDE_M0 = 9            # odd: column groups g and g + k of 64 hold different base columns unless 9 divides k
+WIDE_TIED_SIGMA = 0.01     # the tied background: Gaussian of this sigma per component ...
+WIDE_TIED_LEVELS = 200     # ... rounded to a grid of 1 / 200, as test_gpu_pdw.py's big_matrix(levels=200)
+# the lengths of family G, each the smallest that reaches its route (test_pdw_cases_cpu.py asserts the routes)
+WIDE_F1 = 8 * kSampleRows + 300   # sampled route, ragged last word: tile_words 8, 1025 tiles, pdw_tilescan_kernel<64>
+WIDE_F2 = 1048000                 # 2047 tiles of 8 words: <64> with 32 tiles per thread
+WIDE_F3 = 1 << 20                 # 2048 tiles: <1024>
+WIDE_F4 = 1049253                 # tile_words 16, 1025 tiles; two parts per channel in the candidate select at M = 128
+WIDE_FS = (WIDE_F1, WIDE_F2, WIDE_F3, WIDE_F4)
+WIDE_START0, WIDE_ENDS_LAST, WIDE_OPEN = 3, 5, 7   # base columns of the pulse from frame 0 / to the last frame / left open
+
+
+def scan_kernel_for(F: int, M: int) -> str:
+    """restates edges_and_pulses' choice in pfb_pdw_stage.hpp"""
+    tiles = -(-F // (64 * tile_words_for(F, M)))
+    return "pdw_tilescan_kernel<64>" if M >= 32 and tiles < 2048 else "pdw_tilescan_kernel<1024>"
+
+
+def bracket_row_groups(F: int, M: int) -> int:
+    """restates pfb_pdw_extract's row_groups: the bracket pass walks whole tiles in groups of kBracketRows frames"""
+    tw = tile_words_for(F, M)
+    words = -(-F // (64 * tw)) * tw
+    return -(-words * 64 // kBracketRows)
+
+
+def _wide_tone(c: int, m: int) -> np.ndarray:
+    # amplitude and phase step name the base column; 0.6 and up clears the tied background's thresholds as well (its
+    # medians are sqrt(5) .. sqrt(10) grid steps of 0.005: thresholds of 0.354 .. 0.5)
+    return _tone(m, 0.6 + 0.03 * c, 14.0 + 3.0 * c, 10.0 + 7.0 * c)
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_data(F: int, tied: bool):
+    M0 = WIDE_M0
+    # every base column has its own background level (a sample or a histogram taken from the wrong column brackets the
+    # wrong median): sigma (1 + c / 4) CHAN_SIGMA, or WIDE_TIED_SIGMA (1 + c / 32) before rounding
+    if tied:   # most of a column's magnitudes tied: the bracket's count check fails, the full select runs (path 3)
+        rng = np.random.default_rng(7000 + F % 1000)
+        scale = (WIDE_TIED_SIGMA * WIDE_TIED_LEVELS * (1.0 + np.arange(M0) / 32.0)).astype(np.float32)
+        y = np.empty((F, M0), dtype=np.complex64)
+        y.real = np.round(rng.standard_normal((F, M0), dtype=np.float32) * scale) / WIDE_TIED_LEVELS
+        y.imag = np.round(rng.standard_normal((F, M0), dtype=np.float32) * scale) / WIDE_TIED_LEVELS
+    else:
+        y, _ = _chan_background(F, M0, seed=6000 + F % 1000)
+        y *= (1.0 + np.arange(M0) / 4.0).astype(np.float32)
+    T = 64 * tile_words_for(F, 128)                       # the same for every M >= 128: max_tiles is 2048 there
+    ntiles = -(-F // T)
+    R = (bracket_row_groups(F, 128) - 1) * kBracketRows   # first frame of the last row group of the bracket pass
+    assert R + 100 < F - 70
+    pulses = []
+    for c in range(M0):
+        o1, o2 = _stagger(3 * c)                          # nine different (o1, o2), each offset from -2 to 2 on either edge
+        tone = functools.partial(_wide_tone, c)
+        a, jj = 64 * (2 + c % 3) + o1, 64 * (4 + c % 3) + o2            # a) short and early, edges at word boundaries
+        _chan_pulse(y, pulses, c, a, tone(jj - a))
+        t = ntiles * (c + 1) // (M0 + 2)                                # b) edges at tile boundaries, spread over the stream
+        a, jj = T * t + o1, T * (t + 1) + o2
+        _chan_pulse(y, pulses, c, a, tone(jj - a))
+        a, jj = R - 70 + o1, R + 90 + o2                                # c) across the last row-group boundary
+        _chan_pulse(y, pulses, c, a, tone(jj - a))
+    c = WIDE_START0
+    _chan_pulse(y, pulses, WIDE_START0, 0, _wide_tone(WIDE_START0, 30))                        # d) from frame 0
+    _chan_pulse(y, pulses, WIDE_ENDS_LAST, F - 60, _wide_tone(WIDE_ENDS_LAST, 59))             # e) trailing sample = frame F - 1
+    _chan_pulse(y, pulses, WIDE_OPEN, F - 20, _wide_tone(WIDE_OPEN, 20), terminated=False)     # f) still open: no PDW
+    return y, sorted(pulses), dict(T=T, ntiles=ntiles, R=R)
+
+
+def wide_base(F: int, tied: bool = False, quirks: bool = True) -> Case:
+    """family G: the (F, WIDE_M0) base of a wide matrix (column j of the wide one is column j mod WIDE_M0 of this).
+    Every column has a) a short pulse early on, b) one with its edges at the tile boundaries t T and (t + 1) T,
+    T = 64 tile_words_for(F, 128), c) one spanning the kBracketRows boundary where the bracket pass's last row group
+    starts, each with _stagger offsets on both edges; single columns have d) a pulse from frame 0, e) one whose trailing
+    sample is the last frame and f) one still open there (no PDW).  Amplitude, phase step and background differ per
+    column, so a record from the wrong base column is wrong in mag, snr and (quirks off) freq as well as in time, and
+    a noise floor taken from the wrong column is wrong.
+    tied: the background on a grid of 1 / 200 -- noise-floor path 3; its exactly antipodal neighbours would put phase
+    steps of +-180 degrees into column 0, so that case runs with quirks off (pulse bodies are tones in every column)."""
+    y, pulses, facts = _wide_data(F, tied)
+    name = f"G-wide-F{F}-{'tied' if tied else 'gauss'}-{'quirks' if quirks else 'plain'}"
+    return _chan_case(name, y, pulses, quirks, dict(noise_floor_path=3 if tied else 1), facts)
+
+
+def widen(y: np.ndarray, M: int) -> np.ndarray:
+    """the explicit wide matrix of a base (the GPU tests build it on the device instead)"""
+    M0 = y.shape[1]
+    return np.ascontiguousarray(np.tile(y, (1, -(-M // M0)))[:, :M])
+
+
+def widen_expected(oracle, want_base, M: int, M0: int, fs_in: float):
+    """the oracle's PDWs of the (F, M) matrix whose column j is column j mod M0 of the base, from its PDWs of the base
+    (both at the same explicit decimation)"""
+    def centre(m):
+        cf = oracle.center_frequencies(m, fs_in)
+        return lambda b: cf[(b + (m + 1) // 2) % m]
+    cf0, cf = centre(M0), centre(M)
+    by_col = [[p for p in want_base if p["bin"] == c] for c in range(M0)]   # time order kept
+    return [dict(p, bin=j, freq=p["freq"] - cf0(j % M0) + cf(j)) for j in range(M) for p in by_col[j % M0]]
+
+
+def widen_pulses(pulses, M: int, M0: int):
+    by_col = [[p for p in pulses if p[0] == c] for c in range(M0)]
+    return [(j, a, n) for j in range(M) for _, a, n in by_col[j % M0]]

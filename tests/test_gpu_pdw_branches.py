@@ -9,6 +9,9 @@ designed to land on them -- tests/pdw_cases.py, whose designs tests/test_pdw_cas
   D  the scan's segmentation: thread segments with unrolled group and remainder, empty threads, the wave boundary,
      identity over whole segments; tile_words 32 and 64 (the first wave-per-tile size)
   E  noise-floor path 4: the undecided list overflows and the device redoes the masks
+  F  wide banks, short: family C's channelized edges at M = 128 .. 1024 (tests/test_gpu_pdw_wide.py)
+  G  wide banks, long: the sampled-bracket route at M = 128 .. 1024 on an (F, 9) base expanded to M columns, the
+     oracle's answer mapped from its run on the base (tests/test_gpu_pdw_wide.py)
 
 Everything is an exact integer outcome or goes through pdw_checks.py's compare, unchanged and without phase_col."""
 import numpy as np

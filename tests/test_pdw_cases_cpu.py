@@ -1,8 +1,9 @@
 """The designs of tests/pdw_cases.py, proven with the oracle alone (no GPU): the oracle's restatement of
 create_pdws.m / create_pdws_channelized.m finds exactly the designed pulses on every designed input, the tie structures
 are what they claim to be, no phase step sits on the +-180 degree wrap, and the kernel constants the lengths were chosen
-around are still the ones in pfb_pdw.hip and its headers.  tests/test_gpu_pdw_branches.py then holds the library to the same
-answers."""
+around are still the ones in pfb_pdw.hip and its headers; for the wide banks, the rule that maps the oracle's answer on a
+narrow base to the wide matrix built from it, and the routes the chosen lengths take.  tests/test_gpu_pdw_branches.py and
+tests/test_gpu_pdw_wide.py then hold the library to the same answers."""
 import os
 import re
 
@@ -53,7 +54,7 @@ def test_kernel_constants_are_the_ones_designed_around():
     csrc = os.path.join(os.path.dirname(__file__), "..", "sdr_channelizer_amd", "csrc")
     src = open(os.path.join(csrc, "pfb_pdw.hip")).read()   # the umbrella, then the stage headers it includes
     src += "".join(open(os.path.join(csrc, h)).read() for h in re.findall(r'^#include "(pfb_(?:pdw_\w+|dwell)\.hpp)"', src, re.M))
-    for name in ("kTile", "kPulseCache", "kPulseCacheRaw", "kCountingMedian", "kUndecided"):
+    for name in ("kTile", "kPulseCache", "kPulseCacheRaw", "kCountingMedian", "kUndecided", "kSampleRows", "kBracketRows"):
         m = re.search(r"constexpr\s+int\s+" + name + r"\s*=\s*([^;]+);", src)
         assert m, name
         expr = m.group(1).strip()
@@ -173,7 +174,7 @@ def test_raw_plateau_designs(oracle, entered, count):
         assert [n - 21 for _, _, n in case.pulses[1:-1]] == list(pc.PLATEAU_LENGTHS)
 
 
-@pytest.mark.parametrize("M", [1, 33, 64, 65])
+@pytest.mark.parametrize("M", (1, 33, 64, 65) + pc.WIDE_M)
 def test_channelized_edge_designs(oracle, M):
     case = pc.edges_chan(M)
     check_design(oracle, case)
@@ -224,3 +225,92 @@ def test_path4_design():
     assert near.sum() > pc.kUndecided
     assert (mag[near] > thr[np.nonzero(near)[1]]).all()       # every one of them above its threshold: inside the pulse
     assert case.data.shape[0] >= 8 * 65536
+
+
+# ---- wide banks: family F is test_channelized_edge_designs at pc.WIDE_M; family G below --------------------------------
+
+def test_routes_of_the_wide_lengths():
+    """pfb_pdw_extract's geometry at the lengths of family G, restated from pfb_pdw.hip / pfb_pdw_stage.hpp: the
+    sampled route from 8 kSampleRows frames, the tile length, the tiles per column, the scan kernel on either side of
+    `M >= 32 && ntiles < 2048`, and the parts per channel of the candidate select"""
+    assert pc.WIDE_F1 == 8 * pc.kSampleRows + 300 == 524588 and pc.WIDE_F1 % 64 != 0
+    assert all(F >= 8 * pc.kSampleRows for F in pc.WIDE_FS)
+    assert [pc.tile_words_for(F, 128) for F in pc.WIDE_FS] == [8, 8, 8, 16]
+    assert [-(-F // (64 * pc.tile_words_for(F, 128))) for F in pc.WIDE_FS] == [1025, 2047, 2048, 1025]
+    assert [pc.scan_kernel_for(F, 128) for F in pc.WIDE_FS] == ["pdw_tilescan_kernel<64>"] * 2 + \
+        ["pdw_tilescan_kernel<1024>", "pdw_tilescan_kernel<64>"]
+    assert -(-2047 // 64) == 32                       # tiles per thread of the one-wave scan at F2
+    for M in pc.WIDE_M:                               # one tile length for every wide bank: max_tiles is 2048 from M = 128 up
+        assert [pc.tile_words_for(F, M) for F in pc.WIDE_FS] == [8, 8, 8, 16]
+        assert pc.scan_kernel_for(pc.WIDE_F1, M) == "pdw_tilescan_kernel<64>"
+
+    def parts(F, M):
+        stride = F // pc.kSampleRows
+        ns = F // stride
+        delta = int(np.ceil(2.5 * np.sqrt(ns))) + 2
+        expect = int((2 * delta + 1) / ns * F)
+        return max(1, min(16, 512 // M + 1, expect // 8192))
+    assert [parts(pc.WIDE_F1, M) for M in pc.WIDE_M] == [1] * 5
+    assert [parts(F, 128) for F in pc.WIDE_FS] == [1, 2, 2, 2] and parts(pc.WIDE_F4, 560) == 1
+    # column groups of 64 and the last one's live lanes: full groups only, and a full group followed by a partial one
+    assert [(-(-M // 64), M % 64) for M in pc.WIDE_M] == [(2, 0), (3, 2), (4, 0), (9, 48), (16, 0)]
+    assert pc.WIDE_M0 % 2 == 1 and len({(64 * g) % pc.WIDE_M0 for g in range(9)}) == 9   # every group starts on another base column
+
+
+WIDE_BASES = [(pc.WIDE_F1, False, True), (pc.WIDE_F1, False, False), (pc.WIDE_F1, True, False),
+              (pc.WIDE_F2, False, True), (pc.WIDE_F3, False, True), (pc.WIDE_F4, False, True)]
+
+
+@pytest.mark.parametrize("F,tied,quirks", WIDE_BASES)
+def test_wide_base_designs(oracle, F, tied, quirks):
+    case = pc.wide_base(F, tied, quirks)
+    check_design(oracle, case)
+    check_no_antipodal_steps(case)
+    M0 = pc.WIDE_M0
+    assert case.data.shape == (F, M0) and case.count == 3 * M0 + 2
+    T, R = case.facts["T"], case.facts["R"]
+    assert T == 64 * pc.tile_words_for(F, 128) and R % pc.kBracketRows == 0 and F - pc.kBracketRows <= R < F
+    starts = {(c, a) for c, a, _ in case.pulses}
+    ends = {(c, a + n - 1) for c, a, n in case.pulses}
+    near = lambda x: (x + T // 2) % T - T // 2         # signed distance from the nearest tile boundary
+    tile_offsets = set()
+    for c in range(M0):
+        per = [(a, a + n - 1) for cc, a, n in case.pulses if cc == c]
+        assert sum(e - a for a, e in per) < F // 4
+        assert any(e < 64 * 8 for _, e in per)                                        # a) early
+        b = [(a, e) for a, e in per if a > T and abs(near(a)) <= 2 and abs(near(e)) <= 2 and abs(e - a - T) <= 4]
+        assert len(b) == 1                                                            # b) tile boundary to tile boundary
+        tile_offsets.add((near(b[0][0]), near(b[0][1])))
+        assert any(a < R < e for a, e in per)                                         # c) across the last row-group boundary
+    assert len(tile_offsets) == M0 and all({o[k] for o in tile_offsets} == {-2, -1, 0, 1, 2} for k in (0, 1))
+    assert (pc.WIDE_START0, 0) in starts and (pc.WIDE_ENDS_LAST, F - 1) in ends
+    mag = np.abs(case.data[-20:, pc.WIDE_OPEN])
+    assert (mag > 0.5).all() and all(a + n <= F - 20 for c, a, n in case.pulses if c == pc.WIDE_OPEN)
+    nf = np.median(np.abs(case.normalised()), axis=0)
+    if tied:   # most magnitudes tied: a handful of values hold the bulk of every column, the median among them
+        col = np.abs(case.normalised()[:, 0])
+        assert len(np.unique(col[col < 0.1])) < 200 and np.count_nonzero(col == nf[0]) > F // 50
+    else:      # neighbouring base columns' floors are further apart than the sampled bracket is wide (about +-1.4 %)
+        assert (nf[1:] / nf[:-1] > 1.05).all()
+
+
+@pytest.mark.parametrize("tied,quirks", [(False, False), (False, True), (True, False)])
+def test_widening_rule_with_the_oracle_alone(oracle, tied, quirks):
+    """oracle(explicit wide matrix) == widen_expected(oracle(base)): bit-equal but for freq, which moves by one
+    reassociated addition at 1e9 Hz (a few ulp: 1e-6 Hz).  Same builder at a small F (the sampled route is the
+    library's business, not the oracle's)."""
+    F = 6 * pc.kBracketRows + 300
+    base = pc.wide_base(F, tied, quirks)
+    a, M0 = base.args, pc.WIDE_M0
+    want_base, _ = pc.run_oracle(oracle, base)
+    assert pc.triples(want_base, base.fs) == base.pulses
+    for M in (65, 130, 560):
+        wide = oracle.extract_pdws(pc.widen(base.data, M).astype(np.complex128), a["fs_in"], a["fc"], a["t0"], a["snr_db"],
+                                   matlab_quirks=quirks, decim=M0)
+        mapped = pc.widen_expected(oracle, want_base, M, M0, a["fs_in"])
+        assert len(wide) == len(mapped) == len(pc.widen_pulses(base.pulses, M, M0))
+        assert pc.triples(wide, base.fs) == pc.widen_pulses(base.pulses, M, M0)
+        for k in ("toa", "pw", "snr", "mag", "sat", "bin"):
+            assert [p[k] for p in wide] == [p[k] for p in mapped], k
+        assert np.abs(np.array([p["freq"] for p in wide]) - np.array([p["freq"] for p in mapped])).max() <= 1e-6
+    pc._wide_data.cache_clear()
