@@ -21,8 +21,10 @@ enum pfb_dev_option {
   PFB_OPT_GRID = 7,        /* schedule 13: resident workgroups to launch, each walking runs b, b + G, ... (0 = one per run) */
   PFB_OPT_TILE_WAVES = 8,  /* schedules 2 / 3 / 8: waves, 4 / 7: wave pairs per workgroup (1 ... 16)                       */
   PFB_OPT_EXPERIMENT = 9,  /* timing experiments, 0 in production.  bit 0: nontemporal row loads in the one-dword-per-lane */
-                           /* kernels; bits 8-15: extra dynamic LDS in KiB for schedule 3 (an occupancy throttle).  Neither */
-                           /* changes a result bit.                                                                         */
+                           /* kernels; bit 1: the history update always as a launch of its own behind the channelizer      */
+                           /* kernel (by default that kernel carries it for calls of at least one history with a frame);   */
+                           /* bits 8-15: extra dynamic LDS in KiB for schedule 3 (an occupancy throttle).  None changes a  */
+                           /* result bit.                                                                                   */
   PFB_OPT_VARIANT = 10     /* n-th fused kernel registered for this shape (0 = the default plan; PFB_ERR_UNSUPPORTED past   */
                            /* the last).  Rebuilds the handle's per-lane tables for the new plan; the filter state stays.   */
 };

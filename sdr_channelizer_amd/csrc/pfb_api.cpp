@@ -30,6 +30,7 @@ using pfb::hip_fail;
 namespace {
 
 constexpr uint32_t kStateMagic = 0x50464231u;  // "PFB1"
+constexpr int kExpSeparateHistory = 2;  // PFB_OPT_EXPERIMENT bit 1: the history update always as a launch of its own
 
 struct StateHeader {
   uint32_t magic, M, P, D, fmt, hist_samples, phase, reserved;
@@ -164,9 +165,12 @@ int launch_by_slabs(pfb_handle* h, const pfb::KernelParams& p, long long sf) {
 // Launch the channelizer kernel(s) for local frames [f_begin, f_end) of a device buffer of n samples.  `hist` holds
 // the hist_samples raw samples in front of d_iq[0]; it is only read when f_begin == 0 (a later range starts at
 // least hist_samples into the buffer, so its "history" is the buffer itself).  Output row f lands where a call
-// over the whole buffer would put it.  No state change, no host sync.
+// over the whole buffer would put it.  No state change, no host sync.  hist_out (enqueue only, f_begin == 0 and
+// n >= hist_samples): where the launch itself leaves the next call's history when it is a single kernel -- *carried says
+// whether it did; by slabs it does not.
 int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist, void* d_out, uint64_t f_begin,
-                  uint64_t f_end, int64_t out_ld, int64_t out_frame0) {
+                  uint64_t f_end, int64_t out_ld, int64_t out_frame0, void* hist_out = nullptr, bool* carried = nullptr) {
+  if (carried) *carried = false;
   if (f_end <= f_begin) return PFB_OK;
   if (f_begin > 0) {
     if (f_begin * (uint64_t)h->D < (uint64_t)h->hist_samples) return PFB_ERR_BAD_ARG;
@@ -221,18 +225,27 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
       const int rc = launch_by_slabs(h, p, (long long)rep.slab_frames);
       if (rc != PFB_OK) return rc;
     } else {
+      p.hist_out = hist_out;
       HIP_TRY(h->fast->launch(p, h->stream));
+      if (carried) *carried = hist_out != nullptr;
     }
     h->last_kernel = h->fast->name;
     h->last_launch = rep;
   } else {
+    p.hist_out = hist_out;
     HIP_TRY(pfb::launch_generic(p, h->stream));
+    if (carried) *carried = hist_out != nullptr;
     h->last_kernel = "pfb_generic";
     h->last_launch = pfb_launch_report{};
     h->last_launch.frames = frames;
   }
   if (ev_second) HIP_TRY(hipEventRecord(ev_second, h->stream));
   return PFB_OK;
+}
+
+void advance_counters(pfb_handle* h, uint64_t n, uint64_t frames) {
+  h->phase = (uint32_t)((h->phase + n) % (uint64_t)h->D);
+  h->frame_index += frames;
 }
 
 // carry the last hist_samples raw samples of [history | d_iq] and advance the counters
@@ -242,17 +255,25 @@ int advance_state(pfb_handle* h, const void* d_iq, uint64_t n, uint64_t frames) 
                                        h->hist_samples, h->bps, h->stream));
     h->cur ^= 1;
   }
-  h->phase = (uint32_t)((h->phase + n) % (uint64_t)h->D);
-  h->frame_index += frames;
+  advance_counters(h, n, frames);
   return PFB_OK;
 }
 
-// enqueue kernel + history update for device-resident buffers; no host sync
+// enqueue kernel + history update for device-resident buffers; no host sync.  A call that is at least one history long
+// and produces frames in a single kernel carries its history inside that launch (carry_history, pfb_fast_cfg.hpp): one
+// launch per call.  Shorter calls (old history is mixed in), calls without a frame, the slab route and
+// kExpSeparateHistory take pfb_update_history_kernel behind the channelizer kernel.
 int enqueue(pfb_handle* h, const void* d_iq, uint64_t n, void* d_out, uint64_t frames, int64_t out_ld,
             int64_t out_frame0) {
-  const int rc = launch_frames(h, d_iq, n, h->d_hist[h->cur], d_out, 0, frames, out_ld, out_frame0);
+  const bool fuse = frames > 0 && n >= (uint64_t)h->hist_samples && !(h->opt_experiment & kExpSeparateHistory);
+  bool carried = false;
+  const int rc = launch_frames(h, d_iq, n, h->d_hist[h->cur], d_out, 0, frames, out_ld, out_frame0,
+                               fuse ? h->d_hist[h->cur ^ 1] : nullptr, &carried);
   if (rc != PFB_OK) return rc;
-  return advance_state(h, d_iq, n, frames);
+  if (!carried) return advance_state(h, d_iq, n, frames);
+  h->cur ^= 1;
+  advance_counters(h, n, frames);
+  return PFB_OK;
 }
 
 // The host path stages through h->stage in chunks of whole frames, so a chunk boundary never falls inside a frame's

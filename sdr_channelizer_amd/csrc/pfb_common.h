@@ -56,6 +56,8 @@ struct KernelParams {
   int schedule;            // fast kernels: the list at the top of pfb_fast.hpp
   int tile_waves;          // schedules 2 / 3 / 8: waves, 4 / 7: wave pairs per workgroup
   int grid_override;       // schedule 13: workgroups to launch, each walking runs b, b + G, ... (0 = one per run)
+  void* hist_out = nullptr;  // non-null: the launch's first workgroup also writes the next call's history here, the last
+                             // hist_samples samples of `in` (carry_history, pfb_fast_cfg.hpp; needs n_in >= hist_samples)
 };
 
 // sample traits -----------------------------------------------------------------

@@ -120,9 +120,9 @@ hipError_t launch_fast(const KernelParams& p, hipStream_t s) {
       // profiles/r03_tiny_pair_workgroups_ab.txt; four pairs at two workgroups per CU: M = 56 0.575-0.605 against 0.608)
       if (p.tile_waves == 4) return launch_pairs_sliding<K, 4, 2>(p, s);
       if constexpr (K::MIN_WAVES >= 4 && 8 * kPair <= 160 * 1024) {
-        if (p.tile_waves >= 8) return launch_pairs_sliding<K, 8, 4>(p, s);
+        if (p.tile_waves >= 8) return launch_pairs_sliding_roles<K, 8, 4>(p, s);
       }
-      return launch_pairs_sliding<K, 6, 3>(p, s);
+      return launch_pairs_sliding_roles<K, 6, 3>(p, s);
     }
   }
   if constexpr (kOverlapOk<K>) {  // sliding runs, FIR of the next chunk scheduled into the FFT of this one
@@ -152,11 +152,13 @@ hipError_t launch_fast(const KernelParams& p, hipStream_t s) {
       // the tuned shape is 8 pairs x 64 frames (16 waves, 512 frames per workgroup); instantiations whose
       // LDS image does not fit 8 pairs take 4
       constexpr size_t kPair = sizeof(float2) * 2 * K::BUF, kSlot = sizeof(typename SampleT<K::FMT>::raw_t) * (K::W - 1) * K::D;
+      // (the shape a call runs by default has the output type and the store kind compiled in; the sweep set above and
+      // the 4-pair option test the flags per store)
       if constexpr (8 * kPair + 9 * kSlot <= 160 * 1024) {
         if (p.tile_waves == 4) return launch_paired<K, 4, 64, 2>(p, s);
-        return launch_paired<K, 8, 64, 4>(p, s);
+        return launch_paired_roles<K, 8, 64, 4>(p, s);
       } else {
-        return launch_paired<K, 4, 64, 2>(p, s);
+        return launch_paired_roles<K, 4, 64, 2>(p, s);
       }
     }
   }

@@ -70,6 +70,42 @@ PFB_DEV long long xcd_remap_block(long long blk, long long nb, int mode) {
   return blk;
 }
 
+// History carried by the channelizer launch itself: called at the top of every channelizer kernel.  When the host asks
+// for it (hist_out), the first workgroup in launch order copies the last hist_samples raw samples of `in` there, which
+// is what pfb_update_history_kernel computes for a call at least one history long -- one launch per call instead of two
+// dependent ones.  hist_out is the handle's OTHER history buffer, which no workgroup of this launch reads.  Every other
+// workgroup pays one scalar compare; there is no barrier in here.  16-byte moves where source and destination allow,
+// samples otherwise, four loads in flight per thread (bps = bytes per sample: 2, 4 or 8; nt = threads of the workgroup).
+template <class T>
+PFB_DEV void carry_copy(T* dst, const T* src, int count, int tid, int nt) {
+  int i = tid;
+  for (; i + 3 * nt < count; i += 4 * nt) {
+    const T a = src[i], b = src[i + nt], c = src[i + 2 * nt], d = src[i + 3 * nt];
+    dst[i] = a;
+    dst[i + nt] = b;
+    dst[i + 2 * nt] = c;
+    dst[i + 3 * nt] = d;
+  }
+  for (; i < count; i += nt) dst[i] = src[i];
+}
+
+PFB_DEV void carry_history(const KernelParams& p, int bps, int nt) {
+  if (p.hist_out == nullptr || blockIdx.x != 0) return;
+  const char* src = static_cast<const char*>(p.in) + (p.n_in - p.hist_samples) * (long long)bps;
+  char* dst = static_cast<char*>(p.hist_out);
+  const int bytes = p.hist_samples * bps;
+  const int tid = threadIdx.x;
+  int done = 0;
+  if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+    carry_copy(reinterpret_cast<uint4*>(dst), reinterpret_cast<const uint4*>(src), bytes / 16, tid, nt);
+    done = bytes / 16 * 16;
+  }
+  const int rest = (bytes - done) / bps;  // samples: all of them, or the few behind the last whole 16 bytes
+  if (bps == 2) carry_copy(reinterpret_cast<uint16_t*>(dst + done), reinterpret_cast<const uint16_t*>(src + done), rest, tid, nt);
+  else if (bps == 4) carry_copy(reinterpret_cast<uint32_t*>(dst + done), reinterpret_cast<const uint32_t*>(src + done), rest, tid, nt);
+  else carry_copy(reinterpret_cast<uint2*>(dst + done), reinterpret_cast<const uint2*>(src + done), rest, tid, nt);
+}
+
 // Sample conversion and the row loads of every schedule (FastKernel's base: the schedules reach both through one alias).
 template <class K>
 struct FastRows {

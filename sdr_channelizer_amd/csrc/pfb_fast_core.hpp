@@ -18,11 +18,14 @@ struct FastKernel : FastRows<K> {
   // vector-memory operations per step is the same on every path -- the compiler's s_waitcnt counts stay exact across
   // the chunk loop (a conditional store makes it assume the fewest, i.e. wait for MORE than the load it needs)
   // MAGSEL: -1 = PFB_FLAG_MAGNITUDE is tested here, 0 / 1 = the caller has (outside its chunk loop: same reason as FULL)
-  template <int I, bool FULL = false, int MAGSEL = -1>
+  // NTSEL: the same for KernelParams.nontemporal (the wave-pair kernels: their FFT role's unrolled chunk bodies then
+  // carry neither flag test nor the store they do not use)
+  template <int I, bool FULL = false, int MAGSEL = -1, int NTSEL = -1>
   PFB_DEV void pass(const KernelParams& p, float2* src, float2* dst, int tid, long long f0,
                     const v2f (&tw)[2][16]) {
     float2* const p_out = p.out;
     const long long p_frames = p.frames;
+    const int nontemporal = NTSEL < 0 ? p.nontemporal : NTSEL;
     constexpr int R = K::R(I), S = K::S(I), KK = K::K(I), RS = K::RS(I);
     constexpr int IPF = M / R, ITEMS = C * IPF, ITERS = (ITEMS + NT - 1) / NT;
     constexpr bool LAST = (I == K::NP - 1);
@@ -134,7 +137,7 @@ struct FastKernel : FastRows<K> {
             // asm keeps the compiler from materialising all R 64-bit addresses ahead of the butterfly,
             // which spilled.  The single-wave frame-major kernels with a non-power-of-two M (56) take the same
             // route with column stride 1 (+5 %); the 576-thread M=560 kernel measured 7 % slower that way.
-            const bool mag = (p.flags & PFB_FLAG_MAGNITUDE) != 0;
+            const bool mag = MAGSEL < 0 ? (p.flags & PFB_FLAG_MAGNITUDE) != 0 : MAGSEL == 1;
             const long long esz = mag ? 4 : 8;
             const long long cs = CM ? p.out_ld : 1;  // elements between adjacent channels
             int col = col_of(kk);
@@ -147,7 +150,7 @@ struct FastKernel : FastRows<K> {
                 *reinterpret_cast<float*>(ptr) = mag_out(v.x, v.y, p.flags);
               } else {
                 v = derot(v, k);
-                store_c64(reinterpret_cast<float2*>(ptr), v, p.nontemporal);
+                store_c64(reinterpret_cast<float2*>(ptr), v, nontemporal);
               }
               asm volatile("" : "+v"(ptr) : : "memory");
               col += KK;
@@ -166,7 +169,7 @@ struct FastKernel : FastRows<K> {
 #pragma unroll
             for (int k = 0; k < R; ++k) {
               const v2f v = derot(x[k], k);
-              store_c64(slot(row, k), v, p.nontemporal);
+              store_c64(slot(row, k), v, nontemporal);
             }
           }
         }
@@ -395,11 +398,12 @@ struct FastKernel : FastRows<K> {
       }
   }
 
+  template <bool FULL = false, int MAGSEL = -1, int NTSEL = -1>
   PFB_DEV void fft_from_lds(const KernelParams& p, const Consts& k, float2* buf, int tid, long long f0) {
     static_assert(K::NP == 2 && !K::PINGPONG, "two in-place passes");
     pass<0>(p, buf, buf, tid, f0, k.tw);
     team_sync<true>();
-    pass<1>(p, buf, nullptr, tid, f0, k.tw);
+    pass<1, FULL, MAGSEL, NTSEL>(p, buf, nullptr, tid, f0, k.tw);
   }
 };
 

@@ -161,7 +161,8 @@ struct HaloShare : FastKernel<K> {
     __syncthreads();    // the FFT wave's last step
   }
 
-  template <int NPAIR, int L>
+  // MAGSEL / NTSEL: PFB_FLAG_MAGNITUDE and KernelParams.nontemporal as the host saw them (pass<>), -1 = tested per store
+  template <int NPAIR, int L, int MAGSEL = -1, int NTSEL = -1>
   PFB_DEV void run_paired(const KernelParams& p, float2* lds_fft, raw_t* lds_halo) {
     static_assert(NT == 64, "one wave per run and role");
     static_assert(L % C == 0 && L >= W - 1, "runs are whole chunks and at least one halo long");
@@ -185,10 +186,22 @@ struct HaloShare : FastKernel<K> {
       Consts k;
       setup(p, tid, k);
       __syncthreads();  // A
+      // an interior workgroup's frames all exist: its stores are unconditional (pass<>'s FULL); both loops meet the
+      // same NCH + 1 barriers
+      if (interior) {
 #pragma unroll
-      for (int s = 0; s <= NCH; ++s) {
-        if (s >= 1) fft_from_lds(p, k, bufs + ((s - 1) & 1) * K::BUF, tid, f_begin + (long long)(s - 1) * C);
-        __syncthreads();
+        for (int s = 0; s <= NCH; ++s) {
+          if (s >= 1)
+            F::template fft_from_lds<true, MAGSEL, NTSEL>(p, k, bufs + ((s - 1) & 1) * K::BUF, tid, f_begin + (long long)(s - 1) * C);
+          __syncthreads();
+        }
+      } else {
+#pragma unroll
+        for (int s = 0; s <= NCH; ++s) {
+          if (s >= 1)
+            F::template fft_from_lds<false, MAGSEL, NTSEL>(p, k, bufs + ((s - 1) & 1) * K::BUF, tid, f_begin + (long long)(s - 1) * C);
+          __syncthreads();
+        }
       }
     }
   }
@@ -196,23 +209,33 @@ struct HaloShare : FastKernel<K> {
 
 template <class K, int NWV, int L>
 __global__ void __launch_bounds__(64 * NWV) pfb_shared_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, 64 * NWV);
   using raw_t = typename SampleT<K::FMT>::raw_t;
   __shared__ float2 lds_fft[NWV * K::LDS_ELEMS];
   __shared__ raw_t lds_halo[(NWV + 1) * (K::W - 1) * K::D];
   HaloShare<K>::template run_shared<NWV, L>(p, lds_fft, lds_halo);
 }
 
-template <class K, int NPAIR, int L, int MINW>
+template <class K, int NPAIR, int L, int MINW, int MAGSEL = -1, int NTSEL = -1>
 __global__ void __launch_bounds__(128 * NPAIR, MINW) pfb_paired_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, 128 * NPAIR);
   using raw_t = typename SampleT<K::FMT>::raw_t;
   __shared__ float2 lds_fft[NPAIR * 2 * K::BUF];
   __shared__ raw_t lds_halo[(NPAIR + 1) * (K::W - 1) * K::D];
-  HaloShare<K>::template run_paired<NPAIR, L>(p, lds_fft, lds_halo);
+  HaloShare<K>::template run_paired<NPAIR, L, MAGSEL, NTSEL>(p, lds_fft, lds_halo);
 }
 
-template <class K, int NPAIR, int L, int MINW>
+template <class K, int NPAIR, int L, int MINW, int MAGSEL = -1, int NTSEL = -1>
 hipError_t launch_paired(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(&pfb_paired_kernel<K, NPAIR, L, MINW>, blocks_for(p, (long long)NPAIR * L), 128 * NPAIR, p, s);
+  return launch_blocks(&pfb_paired_kernel<K, NPAIR, L, MINW, MAGSEL, NTSEL>, blocks_for(p, (long long)NPAIR * L), 128 * NPAIR, p, s);
+}
+
+// The call's output type and store kind as compile-time roles of the kernel: complex temporal, complex nontemporal, or
+// magnitudes (whose stores are always temporal).
+template <class K, int NPAIR, int L, int MINW>
+hipError_t launch_paired_roles(const KernelParams& p, hipStream_t s) {
+  if (wants_magnitude(p)) return launch_paired<K, NPAIR, L, MINW, 1, 0>(p, s);
+  return p.nontemporal ? launch_paired<K, NPAIR, L, MINW, 0, 1>(p, s) : launch_paired<K, NPAIR, L, MINW, 0, 0>(p, s);
 }
 
 template <class K, int NWV>

@@ -221,6 +221,7 @@ struct Overlap : FastKernel<K> {
 
 template <class K, bool MAG>
 __global__ void __launch_bounds__(K::NT, (K::MIN_WAVES > 2 ? K::MIN_WAVES - 1 : K::MIN_WAVES)) pfb_overlap_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, K::NT);
   __shared__ float2 lds[2 * K::BUF];
   Overlap<K>::template run_overlap<MAG ? 1 : 0>(p, lds);
 }

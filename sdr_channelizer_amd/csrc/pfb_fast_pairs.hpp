@@ -60,7 +60,8 @@ struct PairSlide : FastKernel<K> {
     __syncthreads();      // the FFT wave's last step
   }
 
-  template <int NPAIR>
+  // MAGSEL / NTSEL: PFB_FLAG_MAGNITUDE and KernelParams.nontemporal as the host saw them (pass<>), -1 = tested per store
+  template <int NPAIR, int MAGSEL = -1, int NTSEL = -1>
   PFB_DEV void run_pairs_sliding(const KernelParams& p, float2* lds_fft) {
     static_assert(NT == 64 && K::NP == 2 && !K::PINGPONG, "one wave per role, two in-place passes");
     const int wave = threadIdx.x >> 6, tid = threadIdx.x & 63;
@@ -82,25 +83,41 @@ struct PairSlide : FastKernel<K> {
       } else {
         pair_fir_run<false>(p, k, bufs, f_begin, nch);
       }
+    } else if (f_begin + p.frames_per_block <= p.frames) {  // every frame of the run exists: unconditional stores
+#pragma unroll 1
+      for (int s = 0; s <= nch; ++s) {
+        if (s >= 1)
+          F::template fft_from_lds<true, MAGSEL, NTSEL>(p, k, bufs + ((s - 1) & 1) * K::BUF, tid, f_begin + (long long)(s - 1) * C);
+        __syncthreads();
+      }
     } else {
 #pragma unroll 1
       for (int s = 0; s <= nch; ++s) {
-        if (s >= 1 && f_begin < p.frames) fft_from_lds(p, k, bufs + ((s - 1) & 1) * K::BUF, tid, f_begin + (long long)(s - 1) * C);
+        if (s >= 1 && f_begin < p.frames)
+          F::template fft_from_lds<false, MAGSEL, NTSEL>(p, k, bufs + ((s - 1) & 1) * K::BUF, tid, f_begin + (long long)(s - 1) * C);
         __syncthreads();
       }
     }
   }
 };
 
-template <class K, int NPAIR, int MINW>
+template <class K, int NPAIR, int MINW, int MAGSEL = -1, int NTSEL = -1>
 __global__ void __launch_bounds__(128 * NPAIR, MINW) pfb_pairs_sliding_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, 128 * NPAIR);
   __shared__ float2 lds_fft[NPAIR * 2 * K::BUF];
-  PairSlide<K>::template run_pairs_sliding<NPAIR>(p, lds_fft);
+  PairSlide<K>::template run_pairs_sliding<NPAIR, MAGSEL, NTSEL>(p, lds_fft);
 }
 
-template <class K, int NPAIR, int MINW>
+template <class K, int NPAIR, int MINW, int MAGSEL = -1, int NTSEL = -1>
 hipError_t launch_pairs_sliding(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(&pfb_pairs_sliding_kernel<K, NPAIR, MINW>, blocks_for(p, (long long)NPAIR * p.frames_per_block), 128 * NPAIR, p, s);
+  return launch_blocks(&pfb_pairs_sliding_kernel<K, NPAIR, MINW, MAGSEL, NTSEL>, blocks_for(p, (long long)NPAIR * p.frames_per_block), 128 * NPAIR, p, s);
+}
+
+// as launch_paired_roles (pfb_fast_halo.hpp): output type and store kind as compile-time roles
+template <class K, int NPAIR, int MINW>
+hipError_t launch_pairs_sliding_roles(const KernelParams& p, hipStream_t s) {
+  if (wants_magnitude(p)) return launch_pairs_sliding<K, NPAIR, MINW, 1, 0>(p, s);
+  return p.nontemporal ? launch_pairs_sliding<K, NPAIR, MINW, 0, 1>(p, s) : launch_pairs_sliding<K, NPAIR, MINW, 0, 0>(p, s);
 }
 
 }  // namespace pfb

@@ -183,6 +183,7 @@ struct SegKernel {
 
 template <class K, bool MAG, bool CMAJ>
 __global__ void __launch_bounds__(64, K::MIN_WAVES) pfb_seg_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, 64);
   __shared__ float2 lds[2 * SegKernel<K>::CT * K::FS];
   SegKernel<K>::template run<MAG ? 1 : 0, CMAJ ? 1 : 0>(p, lds);
 }

@@ -94,6 +94,7 @@ constexpr int kMagnitudeSchedule = kMagStagedOk<K> ? (K::FMT == PFB_FMT_CF32 ? 7
 // at launch (the frame-major kernels: their store count per chunk is then path-independent, see run_impl)
 template <class K, bool CM = false, bool MS = false, int MAGSEL = -1>
 __global__ void __launch_bounds__(K::NT, K::MIN_WAVES) pfb_fast_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, K::NT);
   __shared__ float2 lds[K::LDS_ELEMS];
   SlidingRun<K, CM, MS>::template run<MAGSEL>(p, lds);
 }

@@ -185,6 +185,7 @@ constexpr bool kTeamsOk = !K::WAVE_FRAMES && K::NP == 3 && !K::PINGPONG && K::NT
 // step look path-dependent to the compiler, whose s_waitcnt for the row prefetch then also waited for the stores
 template <class K, bool MAG>
 __global__ void __launch_bounds__(K::NT + 64 * K::C, K::MIN_WAVES) pfb_teams_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, K::NT + 64 * K::C);
   __shared__ float2 bufs[3 * K::BUF];
   Teams<K>::template run_teams<MAG ? 1 : 0>(p, bufs);
 }

@@ -146,6 +146,7 @@ struct Tiles : FastKernel<K, CM> {
 
 template <class K, int NWV, bool CM = false>
 __global__ void __launch_bounds__(64 * NWV) pfb_tile_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, 64 * NWV);
   __shared__ float2 lds[NWV * K::LDS_ELEMS];
   Tiles<K, CM>::template run_tile<NWV>(p, lds);
 }
@@ -157,6 +158,7 @@ hipError_t launch_tile(const KernelParams& p, hipStream_t s) {
 
 template <class K, int NWV, int CPW>
 __global__ void __launch_bounds__(64 * NWV) pfb_tile_t_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, 64 * NWV);
   __shared__ float2 lds[NWV * CPW * Tiles<K, true>::TSLOT];
   Tiles<K, true>::template run_tile_t<NWV, CPW>(p, lds);
 }

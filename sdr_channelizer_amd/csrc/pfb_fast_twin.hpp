@@ -404,6 +404,7 @@ constexpr bool kTwinOk = K::WAVE_FRAMES && K::NP == 3 && !K::PINGPONG && K::C % 
 
 template <class K, bool MAG>
 __global__ void __launch_bounds__(K::NT, K::MIN_WAVES) pfb_twin_kernel(const KernelParams p) {
+  carry_history(p, SampleT<K::FMT>::kBytes, K::NT);
   __shared__ float2 lds[K::BUF + Twin<K>::TWL_ELEMS];
   Twin<K>::template run_twin<MAG>(p, lds, lds + K::BUF);
 }

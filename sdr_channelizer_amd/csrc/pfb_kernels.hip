@@ -39,6 +39,7 @@ __device__ __forceinline__ int bit_reverse(int v, int bits) { return (int)(__bre
 // tile_frames frames per workgroup; sm holds tile_frames*M complex (x2 when M is not 2^k)
 __global__ void __launch_bounds__(256) pfb_generic_kernel(const KernelParams p, int tile_frames, int log2m, GenericPlan plan) {
   extern __shared__ float2 sm[];
+  carry_history(p, p.fmt == PFB_FMT_INT8_IQ ? 2 : (p.fmt == PFB_FMT_INT16_IQ ? 4 : 8), 256);
   const int M = p.M, P = p.P, D = p.D;
   const int tid = threadIdx.x, nt = blockDim.x;
   const long long f0 = (long long)blockIdx.x * tile_frames;
