@@ -526,6 +526,104 @@ const char* pfb_stft_last_kernel(const pfb_stft_handle* h);
 /* The device the handle lives on (pfb_stft_config.device_id resolved, as pfb_get_device). */
 int pfb_stft_get_device(const pfb_stft_handle* h, int* device_id);
 
+/* ---- pulse-train source -----------------------------------------------------------------------------
+ * Replaces the reference's signal source:
+ *   matlab/generate_pulsed_iq.m:12-19,27-77    rectangular pulses of PW every PRI on a carrier whose phase restarts at
+ *                                              every pulse; LFM sweep (:43-47), Barker-13 chips (:33-40,49-59), only
+ *                                              pulses that fit the record (:67)
+ *   matlab/generate_training_iq.m:34-62,95-98  the same train from a random start index, phase from zero (:44-48),
+ *                                              int16(x*2^15) (:97-98)
+ *   matlab/generate_training_iq.m:107-127      the hand-written format-1 record (pfb_synth_write_iq_file)
+ * The stream is a function from the global sample index i (uint64) to a value, in integers only, so the device, the
+ * host and any cutting of the stream into calls give the same bits; it is sdr_channelizer_amd/synth.py's counter-based
+ * benchmark stream with the scripts' switches added.  With full = 2^(bit_width-1), derived once on the host in double
+ * with round-half-even (pfb_synth_describe reports them):
+ *   chip, pw (Barker)  chip = max(round(pw/13), 1), pw <- 13*chip             (generate_pulsed_iq.m:33-40)
+ *   fcw                llrint(f0/fs * 2^32) mod 2^32                          carrier, turns per sample in 2^-32
+ *   dcw                llrint(ldexp((lfm_extent_hz/(pw-1))/fs, 64)) mod 2^64  sweep step per sample (0 when pw == 1)
+ *   noise_gain         llrint(noise_sigma * full * 2^20 / sqrt(4*(65536^2-1)/12))
+ *   tab[j]             llrint(amplitude * full * 2^20 * cos(2 pi j / 65536)), j = 0..65535
+ *   barker_offset      llrint(fmod(90/(2 pi), 1) * 2^32): the script adds +-90 to a phase in RADIANS (:50-58,61);
+ *                      2^30 (90 degrees) with PFB_SYNTH_BARKER_DEGREES
+ * Per sample: rel = i - first_pulse (off when negative), k = rel mod period, s = i - k; the sample is ON iff k < pw and
+ * (record_samples == 0 or s + 1 + pw < record_samples: the script's (idx+numSamplesForPw) < length(mag) with its
+ * 1-based idx).  kk = k + 1 (the cumsum phase of generate_pulsed_iq.m:45), or k with PFB_SYNTH_PHASE_FROM_ZERO
+ * (freq_phi(1) = 0, generate_training_iq.m:44-48); T = k(k+1)/2;
+ *   ph = (kk*fcw + ((T*dcw mod 2^64) >> 32) [+ Barker: + barker_offset or + 2^32 - barker_offset by the code of chip
+ *        min(k/chip, 12)]) mod 2^32;  ci = ph >> 16, si = (ci - 16384) & 65535
+ *   noise (per component, lane 0 = I, 1 = Q): base = lo32(i) ^ (hi32(i)*0x9E3779B1 mod 2^32) ^ seed,
+ *        a = mix32(base ^ (0x68E31DA4*(2*lane+1) mod 2^32)), b = mix32(a ^ 0x5BD1E995),
+ *        noise = (a & 65535) + (a >> 16) + (b & 65535) + (b >> 16) - 2*65535  (Irwin-Hall, sigma 37837.2 counts)
+ *   v = tab[ci or si]*on + noise*noise_gain                                   (2^-20 LSB fixed point)
+ *   integer formats: clamp((v + 2^19) >> 20, -full, full-1), round half up; with PFB_SYNTH_ROUND_MATLAB half away from
+ *        zero, -((-v + 2^19) >> 20) for v < 0: MATLAB's int16() (generate_training_iq.m:97-98)
+ *   PFB_FMT_CF32: (float)((double)v * 2^-(20 + bit_width - 1)), no clamp
+ * Against the float64 scripts: the phase of an ON sample agrees with theirs to 3.4e-6 rad (the 32-bit fcw); the
+ * resolution that matters is the 16-bit table index, 9.6e-5 rad.
+ * Every argument is validated before the device is touched.  PFB_ERR_BAD_ARG: null pointers, a wrong struct_size,
+ * not 1 <= pulse_samples <= period_samples < 2^31 (after the Barker adjustment too), amplitude outside [0, 2],
+ * noise_sigma outside [0, 1], fs <= 0, a non-finite double, |f0/fs| > 2^20, |lfm step/fs| >= 0.5, unknown flag bits,
+ * PFB_SYNTH_BARKER_DEGREES without PFB_SYNTH_BARKER13, start + num_samples overflowing, an output pointer not aligned
+ * to one sample.  PFB_ERR_BAD_FORMAT: an unknown sample format, bit_width outside 2..8 (int8) or 2..16 (int16; cf32,
+ * where it only scales the table), a cf32 handle or a format-1 record from an int8 handle asked of
+ * pfb_synth_write_iq_file.  Then PFB_ERR_NO_DEVICE without a HIP device. */
+enum {
+  PFB_SYNTH_BARKER13 = 1u << 0,         /* BARKER_13 = true, generate_pulsed_iq.m:17                  */
+  PFB_SYNTH_BARKER_DEGREES = 1u << 1,   /* chips of +-90 degrees instead of the script's +-90 radians */
+  PFB_SYNTH_PHASE_FROM_ZERO = 1u << 2,  /* generate_training_iq.m:44-48                               */
+  PFB_SYNTH_ROUND_MATLAB = 1u << 3      /* int16(): half away from zero                               */
+};
+
+typedef struct pfb_synth_config {
+  uint32_t struct_size;     /* = sizeof(pfb_synth_config)                                        */
+  uint32_t sample_format;   /* pfb_sample_format of the output                                   */
+  uint32_t bit_width;       /* full scale 2^(bit_width-1)                                        */
+  uint32_t flags;           /* PFB_SYNTH_*                                                       */
+  uint32_t pulse_samples;   /* pw: round(fs*PW), generate_training_iq.m:37                       */
+  uint32_t period_samples;  /* pri: round(fs*PRI), :38                                           */
+  uint32_t seed;            /* of the noise                                                      */
+  int32_t device_id;        /* HIP device ordinal, -1 = current device                           */
+  uint64_t first_pulse;     /* index of the first pulse's first sample (startIdx, :24-26,40)     */
+  uint64_t record_samples;  /* length(mag) of the fit rule; 0 = an endless stream                */
+  double fs, f0;            /* sample rate and carrier (f / f_start), Hz                         */
+  double lfm_extent_hz;     /* LFM_EXTENT, generate_pulsed_iq.m:18: f_stop - f_start             */
+  double amplitude;         /* of an ON sample, in full scales (the scripts: 1)                  */
+  double noise_sigma;       /* per component, in full scales (the scripts: 0)                    */
+} pfb_synth_config;
+
+typedef struct pfb_synth_params {  /* what the host derived: host only, needs no device */
+  uint32_t pulse_samples;          /* after the Barker adjustment */
+  uint32_t chip_samples;           /* 0 without PFB_SYNTH_BARKER13 */
+  uint32_t fcw, barker_offset;
+  uint64_t dcw;
+  int64_t noise_gain;
+} pfb_synth_params;
+
+typedef struct pfb_synth_handle pfb_synth_handle;
+
+/* Host only: validate cfg and report the derived integers; table_out (65536 values, or NULL) receives tab. */
+int pfb_synth_describe(const pfb_synth_config* cfg, pfb_synth_params* out, int64_t* table_out);
+/* The handle owns the table in device memory, and holds no stream position: every call names its own. */
+int pfb_synth_create(const pfb_synth_config* cfg, pfb_synth_handle** out);
+int pfb_synth_destroy(pfb_synth_handle* h);
+int pfb_synth_set_stream(pfb_synth_handle* h, void* hip_stream);  /* as pfb_set_stream */
+/* Samples start .. start + num_samples - 1 of the stream into `out`: interleaved I,Q of cfg.sample_format, aligned to
+ * one sample.  mem = PFB_MEM_DEVICE: one kernel on the handle's stream, complete on return.  PFB_MEM_HOST: generated
+ * into page-locked chunks and copied out. */
+int pfb_synth_generate(pfb_synth_handle* h, uint64_t start, uint64_t num_samples, void* out, uint32_t mem);
+/* Same, device pointer, enqueued on the handle's stream without a host sync. */
+int pfb_synth_generate_async(pfb_synth_handle* h, uint64_t start, uint64_t num_samples, void* d_out);
+int pfb_synth_sync(pfb_synth_handle* h);
+int pfb_synth_get_device(const pfb_synth_handle* h, int* device_id);
+/* Write samples start .. start + num_samples - 1 as one .iq record: the header (pfb_iq_serialize_header), then the
+ * payload, generated in chunks and never held whole in memory.  file_format 1 is the record
+ * generate_training_iq.m:107-127 writes (int16 handles only: the script writes 16-bit), 3 the recorders'.
+ * header_fields NULL: link speed 1 (format 1) or 0 (format 3), frequency 0, bandwidth = sample rate = fs, gain 0,
+ * board "simulated", start time 0; otherwise its fields, with the marker, numSamples and bitWidth set by the library
+ * (bitWidth = cfg.bit_width; the script's own record is bit_width 16).  fs must fit a uint32. */
+int pfb_synth_write_iq_file(pfb_synth_handle* h, const char* path, int file_format, uint64_t start,
+                            uint32_t num_samples, const pfb_iq_packet* header_fields);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,16 @@ void pfb_iq_fill_packet(pfb_iq_packet* p, uint32_t marker, uint64_t frequency_hz
                         uint32_t num_samples, uint32_t bit_width, const char* board_name,
                         const char* serial_number, double sample_start_time);
 
+/* The on-disk header of a record in file_format 1, 2 or 3, little-endian, into `bytes`: 104 bytes for format 1
+ * (what matlab/generate_training_iq.m:109-123 writes by hand: 32-bit frequency, integer gain, no spare0 word, the
+ * four strings as one 64-byte block), 112 for formats 2 and 3 (cpp/IqPacket.h:9-25 as the recorders write it,
+ * cpp/blade_record_iq_12bit.cpp:318-323).  The marker word is the format's, whatever p->endianness holds.  Formats 1
+ * and 2 store the gain as the uint32 that convert_my_iq_to_mat.m:73-77 reads (rxGainDb rounded), format 3 as float32.
+ * *written (optional) receives the header length.  The inverse of pfb_iq_parse_header.  PFB_ERR_BAD_ARG: a null
+ * pointer, an unknown format, capacity below the header length, a frequency (format 1) or gain (formats 1, 2) that
+ * the narrower word cannot hold. */
+int pfb_iq_serialize_header(const pfb_iq_packet* p, int file_format, void* bytes, size_t capacity, size_t* written);
+
 /* UTC "YYYY_MM_DD_hh_mm_ss_mmm.iq" from milliseconds since the epoch
  * (cpp/Helper.cpp:6-23).  Returns the number of characters written. */
 int pfb_iq_filename(int64_t epoch_ms, char* out, int out_len);

@@ -38,6 +38,7 @@ PFB_STFT_CENTERED, PFB_STFT_TWOSIDED = 0, 1
 PFB_STFT_KERNEL_AUTO, PFB_STFT_KERNEL_GENERIC, PFB_STFT_KERNEL_FUSED = 0, 1, 2
 PFB_DWELL_STAT_MEAN, PFB_DWELL_STAT_MEDIAN = 0, 1
 PFB_DWELL_SKIP_FREQ = 1
+PFB_SYNTH_BARKER13, PFB_SYNTH_BARKER_DEGREES, PFB_SYNTH_PHASE_FROM_ZERO, PFB_SYNTH_ROUND_MATLAB = 1, 2, 4, 8
 
 
 class PfbConfig(C.Structure):
@@ -88,6 +89,21 @@ class PfbDwellStats(C.Structure):
         ("noise_floor", C.c_double), ("threshold", C.c_double), ("any_pulse_saturated", C.c_int32),
         ("reserved", C.c_int32),
     ]
+
+
+class PfbSynthConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("sample_format", C.c_uint32), ("bit_width", C.c_uint32), ("flags", C.c_uint32),
+        ("pulse_samples", C.c_uint32), ("period_samples", C.c_uint32), ("seed", C.c_uint32), ("device_id", C.c_int32),
+        ("first_pulse", C.c_uint64), ("record_samples", C.c_uint64),
+        ("fs", C.c_double), ("f0", C.c_double), ("lfm_extent_hz", C.c_double), ("amplitude", C.c_double),
+        ("noise_sigma", C.c_double),
+    ]
+
+
+class PfbSynthParams(C.Structure):
+    _fields_ = [("pulse_samples", C.c_uint32), ("chip_samples", C.c_uint32), ("fcw", C.c_uint32),
+                ("barker_offset", C.c_uint32), ("dcw", C.c_uint64), ("noise_gain", C.c_int64)]
 
 
 class PfbFastPlanDesc(C.Structure):
@@ -148,6 +164,9 @@ EXPORTS = (
     "pfb_stft_process_async", "pfb_stft_sync", "pfb_stft_frames_for", "pfb_stft_process_iq_file", "pfb_stft_axes",
     "pfb_stft_last_kernel", "pfb_stft_get_device",
     "pfb_dwell_analyze", "pfb_dwell_from_iq_file", "pfb_event_fit", "pfb_event_next",
+    "pfb_synth_describe", "pfb_synth_create", "pfb_synth_destroy", "pfb_synth_set_stream", "pfb_synth_generate",
+    "pfb_synth_generate_async", "pfb_synth_sync", "pfb_synth_get_device", "pfb_synth_write_iq_file",
+    "pfb_iq_serialize_header",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -264,6 +283,16 @@ def load() -> C.CDLL:
     lib.pfb_event_fit.argtypes = [C.POINTER(PfbPdw), u64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double)]
     lib.pfb_event_next.argtypes = [C.POINTER(C.c_double), u64, u32, C.POINTER(C.c_double), C.POINTER(i32)]
+    lib.pfb_synth_describe.argtypes = [C.POINTER(PfbSynthConfig), C.POINTER(PfbSynthParams), C.POINTER(i64)]
+    lib.pfb_synth_create.argtypes = [C.POINTER(PfbSynthConfig), C.POINTER(vp)]
+    lib.pfb_synth_destroy.argtypes = [vp]
+    lib.pfb_synth_set_stream.argtypes = [vp, vp]
+    lib.pfb_synth_generate.argtypes = [vp, u64, u64, vp, u32]
+    lib.pfb_synth_generate_async.argtypes = [vp, u64, u64, vp]
+    lib.pfb_synth_sync.argtypes = [vp]
+    lib.pfb_synth_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_synth_write_iq_file.argtypes = [vp, C.c_char_p, C.c_int, u64, u32, C.POINTER(PfbIqPacket)]
+    lib.pfb_iq_serialize_header.argtypes = [C.POINTER(PfbIqPacket), C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]

@@ -81,6 +81,48 @@ void pfb_iq_fill_packet(pfb_iq_packet* p, uint32_t marker, uint64_t frequency_hz
   p->sampleStartTime = sample_start_time;
 }
 
+static void wr32(unsigned char* p, uint32_t v) {
+  p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24);
+}
+static void wr64(unsigned char* p, uint64_t v) { wr32(p, (uint32_t)v); wr32(p + 4, (uint32_t)(v >> 32)); }
+
+int pfb_iq_serialize_header(const pfb_iq_packet* k, int file_format, void* bytes, size_t capacity, size_t* written) {
+  if (!k || !bytes || file_format < 1 || file_format > 3) return PFB_ERR_BAD_ARG;
+  const size_t len = file_format == 1 ? PFB_IQ_HEADER_BYTES_FMT1 : PFB_IQ_HEADER_BYTES;
+  if (capacity < len) return PFB_ERR_BAD_ARG;
+  uint32_t gain;
+  if (file_format >= 3) {
+    memcpy(&gain, &k->rxGainDb, 4);
+  } else { /* the uint32 convert_my_iq_to_mat.m:73-77 reads back */
+    if (!(k->rxGainDb >= 0.0f && k->rxGainDb < 4294967296.0f)) return PFB_ERR_BAD_ARG;
+    gain = (uint32_t)(k->rxGainDb + 0.5f);
+  }
+  if (file_format == 1 && k->frequencyHz > 0xFFFFFFFFu) return PFB_ERR_BAD_ARG;
+  unsigned char* b = (unsigned char*)bytes;
+  size_t pos = 0;
+  wr32(b + pos, file_format == 1 ? PFB_IQ_MARKER_FMT1 : file_format == 2 ? PFB_IQ_MARKER_FMT2 : PFB_IQ_MARKER_FMT3); pos += 4;
+  wr32(b + pos, k->linkSpeed); pos += 4;
+  if (file_format == 1) { wr32(b + pos, (uint32_t)k->frequencyHz); pos += 4; } /* generate_training_iq.m:111 */
+  else { wr64(b + pos, k->frequencyHz); pos += 8; }
+  wr32(b + pos, k->bandwidthHz); pos += 4;
+  wr32(b + pos, k->sampleRateSps); pos += 4;
+  wr32(b + pos, gain); pos += 4;
+  wr32(b + pos, k->numSamples); pos += 4;
+  wr32(b + pos, k->bitWidth); pos += 4;
+  if (file_format >= 2) { wr32(b + pos, k->spare0); pos += 4; }
+  memcpy(b + pos, k->boardName, 16); pos += 16;                                /* :118-121: 4*16 bytes of strings */
+  memcpy(b + pos, k->serialNumber, 16); pos += 16;
+  memcpy(b + pos, k->fpgaVersion, 16); pos += 16;
+  memcpy(b + pos, k->fwVersion, 16); pos += 16;
+  {
+    uint64_t t;
+    memcpy(&t, &k->sampleStartTime, 8);
+    wr64(b + pos, t); pos += 8;
+  }
+  if (written) *written = pos;
+  return PFB_OK;
+}
+
 int pfb_iq_filename(int64_t epoch_ms, char* out, int out_len) {
   if (!out || out_len <= 0) return PFB_ERR_BAD_ARG;
   int64_t secs = epoch_ms / 1000, ms = epoch_ms % 1000;
