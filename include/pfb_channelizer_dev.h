@@ -65,7 +65,8 @@ int pfb_fast_plan_count(void);
 int pfb_fast_plan_info(int index, pfb_fast_plan_desc* out); /* PFB_ERR_BAD_ARG past the end or for NULL */
 
 /* How the handle's last kernel launch went: what the launch policy actually handed to the kernel, so that a test can
- * tell which regime a call ran in without repeating the policy's arithmetic.  One call of pfb_process(_async) is one
+ * tell which regime a call ran in without repeating the policy's arithmetic.  This is what was asked of the kernel;
+ * which kernel ran, and on what grid, is pfb_last_entry below.  One call of pfb_process(_async) is one
  * launch (each staged chunk of a host-pointer call is one; pfb_process_shard_async makes two).  Host only, touches no
  * device; all zeros before the first launch.  A launch of the generic kernel reports fused = 0, its frames, and zeros. */
 typedef struct {
@@ -96,6 +97,53 @@ typedef struct {
   int64_t slab_frames;    /* PFB_OPT_SLAB_FRAMES, 0 = default */
 } pfb_launch_request;
 int pfb_plan_launch(int plan_index, const pfb_launch_request* rq, uint64_t frames, pfb_launch_report* out);
+
+/* The kernel entry: which kernel a launch resolved to.  pfb_launch_report is what was ASKED of the kernel -- the policy's
+ * hand-down, "as passed" -- and a forced option the plan lacks falls through to another kernel without changing it; the
+ * entry is what RAN.  Host only, touches no device.
+ *
+ * tag grammar (one place; static storage):   family [ "<" int { "," int } ">" ] { "+" role }
+ *   family  sliding | tile | tile_t | shared | paired | pairs_sliding | overlap | teams | twin | seg (the fused kernels of
+ *           pfb_fast_*.hpp), or generic
+ *   ints    the kernel's integer template arguments behind the plan, as the source writes them: tile<waves>,
+ *           tile_t<waves,chunks per wave>, shared<waves,run length>, paired<pairs,run length,min waves per SIMD>,
+ *           pairs_sliding<pairs,min waves per SIMD>
+ *   roles   what the instantiation has compiled in, in this order: cm = channel-major stores, ms = magnitudes staged in
+ *           LDS, c64 / mag = complex or magnitude output, nt = nontemporal stores (after c64 only)
+ *   e.g. paired<8,64,4>+c64, sliding+ms, tile_t<4,2>, seg+cm+mag.  Within one plan row two entries have the same tag if
+ *   and only if they have the same kernel. */
+typedef struct {
+  int schedule;           /* of the kernel that ran (the list in pfb_fast.hpp): 0 when a forced schedule the plan lacks fell */
+                          /* to its sliding runs, 8 / 2 / 0 where the report says -1; -1 = the generic kernel                */
+  int threads;            /* per workgroup */
+  uint32_t dyn_lds;       /* dynamic LDS in bytes */
+  int reserved;
+  uint64_t blocks;        /* workgroups launched (after PFB_OPT_GRID's cap) */
+  uint64_t kernel;        /* address of the kernel's host stub: opaque, meaningful only for equality within a process */
+  const char* tag;
+} pfb_kernel_entry;
+/* The entry of the handle's last kernel launch (by slabs: the last slab's frame-major launch; the transpose is not a
+ * channelizer kernel).  All zeros and an empty tag before the first launch; PFB_ERR_BAD_ARG for NULL. */
+int pfb_last_entry(const pfb_handle* h, pfb_kernel_entry* out);
+
+/* The selection on its own, as pfb_plan_launch is the policy on its own (no device needed): runs the policy for
+ * `launch` and `frames` on row plan_index, fills the kernel's parameters the way a handle with these options does and
+ * returns the entry the row's select resolves them to.  By slabs it describes one full slab's launch.  A kernel of 0
+ * means the plan has no kernel for the call (the launch would fail).  PFB_ERR_BAD_ARG for NULL, an index past the end
+ * or a struct_size (either one) that does not match. */
+typedef struct {
+  uint32_t struct_size;
+  int plan_index;
+  pfb_launch_request launch; /* what the policy sees */
+  int tile_waves;         /* PFB_OPT_TILE_WAVES (a handle's default: 8) */
+  int nontemporal;        /* PFB_OPT_NONTEMPORAL */
+  int grid;               /* PFB_OPT_GRID */
+  int experiment;         /* PFB_OPT_EXPERIMENT */
+  int out_aligned16;      /* the output pointer is a multiple of 16 bytes */
+  int reserved;
+  uint64_t frames;
+} pfb_entry_request;
+int pfb_plan_entry(const pfb_entry_request* rq, pfb_kernel_entry* out);
 
 /* Diagnostic: throws a C++ exception of the given kind (0 = std::bad_alloc, 1 = std::runtime_error,
  * 2 = a non-std type) INSIDE the guard every entry point runs under and returns what the guard

@@ -130,6 +130,29 @@ class PfbLaunchRequest(C.Structure):
     ]
 
 
+class PfbKernelEntry(C.Structure):
+    _fields_ = [
+        ("schedule", C.c_int), ("threads", C.c_int), ("dyn_lds", C.c_uint32), ("reserved", C.c_int),
+        ("blocks", C.c_uint64), ("kernel", C.c_uint64), ("_tag", C.c_char_p),
+    ]
+
+    @property
+    def tag(self) -> str:
+        return (self._tag or b"").decode()
+
+    def fields(self) -> tuple:
+        """every field, for comparing two entries"""
+        return (self.schedule, self.threads, self.dyn_lds, self.blocks, self.kernel, self.tag)
+
+
+class PfbEntryRequest(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("plan_index", C.c_int), ("launch", PfbLaunchRequest), ("tile_waves", C.c_int),
+        ("nontemporal", C.c_int), ("grid", C.c_int), ("experiment", C.c_int), ("out_aligned16", C.c_int),
+        ("reserved", C.c_int), ("frames", C.c_uint64),
+    ]
+
+
 PFB_PDW_MATLAB_QUIRKS = 1        # phase(toa:jj) linear-indexes column 1 (create_pdws_channelized.m:114)
 PFB_PDW_CHANNEL_MAJOR = 2
 PFB_PDW_BINFREQ_UNSHIFTED = 4    # binFreqs(bin) from the FFT-ordered list (:42/:80 if centerFrequencies is unshifted; unpinned)
@@ -170,7 +193,7 @@ EXPORTS = (
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
-               "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch")
+               "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch", "pfb_last_entry", "pfb_plan_entry")
 
 _lib = None
 
@@ -298,6 +321,8 @@ def load() -> C.CDLL:
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
     lib.pfb_last_launch.argtypes = [vp, C.POINTER(PfbLaunchReport)]
     lib.pfb_plan_launch.argtypes = [C.c_int, C.POINTER(PfbLaunchRequest), u64, C.POINTER(PfbLaunchReport)]
+    lib.pfb_last_entry.argtypes = [vp, C.POINTER(PfbKernelEntry)]
+    lib.pfb_plan_entry.argtypes = [C.POINTER(PfbEntryRequest), C.POINTER(PfbKernelEntry)]
     for name in EXPORTS + DEV_EXPORTS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     _lib = lib
@@ -329,3 +354,17 @@ def plan_launch(row: int, frames: int, num_cus: int, schedule: int = -1, frames_
     rep = PfbLaunchReport()
     check(load().pfb_plan_launch(row, C.byref(rq), frames, C.byref(rep)), "pfb_plan_launch")
     return rep
+
+
+def plan_entry(row: int, frames: int, num_cus: int, schedule: int = -1, frames_per_block: int = 0, xcd_remap: int = -1,
+               slab_frames: int = 0, channel_major: bool = False, magnitude: bool = False, tile_waves: int = 8,
+               nontemporal: bool = False, grid: int = 0, experiment: int = 0, out_aligned16: bool = True) -> PfbKernelEntry:
+    """The kernel entry row ``row`` of the table resolves these options and ``frames`` frames to (pfb_plan_entry; host
+    only): the policy of plan_launch, then the row's select -- what a handle's last_entry holds after that launch."""
+    launch = PfbLaunchRequest(C.sizeof(PfbLaunchRequest), schedule, frames_per_block, xcd_remap, int(channel_major),
+                              int(magnitude), num_cus, slab_frames)
+    rq = PfbEntryRequest(C.sizeof(PfbEntryRequest), row, launch, tile_waves, int(nontemporal), grid, experiment,
+                         int(out_aligned16), 0, frames)
+    e = PfbKernelEntry()
+    check(load().pfb_plan_entry(C.byref(rq), C.byref(e)), "pfb_plan_entry")
+    return e

@@ -140,6 +140,13 @@ class Channelizer(Handle):
         L.check(self._lib.pfb_last_launch(self._h, C.byref(rep)), "pfb_last_launch")
         return rep
 
+    @property
+    def last_entry(self) -> L.PfbKernelEntry:
+        """The kernel the last launch ran: schedule, grid and tag of the instantiation (pfb_last_entry; host only)."""
+        e = L.PfbKernelEntry()
+        L.check(self._lib.pfb_last_entry(self._h, C.byref(e)), "pfb_last_entry")
+        return e
+
     def set_stream(self, hip_stream: int) -> None:
         L.check(self._lib.pfb_set_stream(self._h, C.c_void_p(hip_stream)), "pfb_set_stream")
 

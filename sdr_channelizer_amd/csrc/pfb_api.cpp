@@ -20,6 +20,7 @@
 
 #include "pfb_common.h"
 #include "pfb_channelizer_dev.h"
+#include "pfb_fast_cfg.hpp"  // launch_blocks: the one launch of a kernel entry
 #include "pfb_host.h"
 #include "pfb_launch_policy.h"
 
@@ -77,6 +78,7 @@ struct pfb_handle {
   size_t matrix_bytes = 0;
   const char* last_kernel = "";
   pfb_launch_report last_launch{};  // what launch_frames handed to the kernel last time (pfb_last_launch)
+  pfb::KernelEntry last_entry{};    // the kernel that launch ran (pfb_last_entry)
   pfb::HostStage stage;  // host-pointer calls (stage.d_in[0] is also pfb_prime's scratch)
   // PFB_OPT_PROFILE: event pairs around each channelizer kernel launch
   int opt_profile = 0;
@@ -135,6 +137,22 @@ int begin_profile(pfb_handle* h, hipEvent_t* second) {
   return PFB_OK;
 }
 
+// What the launch policy decided goes into a fused call's KernelParams here, for launch_frames and pfb_plan_entry alike.
+void apply_policy(pfb::KernelParams& p, const pfb_launch_report& rep) {
+  p.schedule = rep.schedule;
+  p.frames_per_block = rep.frames_per_block;
+  p.xcd_remap = rep.xcd_remap;
+}
+
+// Every fused launch: resolve p to its kernel entry (the plan's select, a pure function), launch that entry, and keep it
+// next to last_launch -- the report is what was asked of the kernel, the entry is what ran.
+int launch_fused(pfb_handle* h, const pfb::KernelParams& p) {
+  const pfb::KernelEntry e = h->fast->select(p);
+  HIP_TRY(pfb::launch_blocks(e, p, h->stream));
+  h->last_entry = e;
+  return PFB_OK;
+}
+
 // Channel-major by slabs of sf frames: the frame-major kernel fills the handle's scratch slab (grown here), the
 // transpose kernel moves it into place.  p is the whole call's launch; its output fields say where the matrix is.
 int launch_by_slabs(pfb_handle* h, const pfb::KernelParams& p, long long sf) {
@@ -156,7 +174,8 @@ int launch_by_slabs(pfb_handle* h, const pfb::KernelParams& p, long long sf) {
     q.n_in = p.n_in - f0 * h->D;
     if (f0 > 0)  // "history" of a later slab = the input samples in front of it
       q.hist = static_cast<const char*>(q.in) - (size_t)h->hist_samples * h->bps;
-    HIP_TRY(h->fast->launch(q, h->stream));
+    const int rc = launch_fused(h, q);
+    if (rc != PFB_OK) return rc;
     HIP_TRY(pfb::launch_transpose_slab(h->d_slab, q.frames, h->M, p.out, p.out_ld, p.out_frame0 + f0, h->out_elem, h->stream));
   }
   return PFB_OK;
@@ -215,9 +234,7 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
     const pfb::LaunchRequest rq{h->opt_schedule, h->opt_frames_per_block, h->opt_xcd_remap, h->opt_slab_frames,
                                 h->layout == PFB_LAYOUT_CHANNEL_MAJOR, (h->flags & PFB_FLAG_MAGNITUDE) != 0, h->num_cus};
     const pfb_launch_report rep = pfb::plan_launch(h->plan, rq, frames);
-    p.schedule = rep.schedule;
-    p.frames_per_block = rep.frames_per_block;
-    p.xcd_remap = rep.xcd_remap;
+    apply_policy(p, rep);
     const int cpt = h->fast->cols_per_thread;
     const int bmod = ((p.base % cpt) + cpt) % cpt;
     p.vec_ok = (bmod == 0) && (reinterpret_cast<uintptr_t>(d_iq) % (uintptr_t)(h->bps * cpt) == 0);
@@ -226,14 +243,15 @@ int launch_frames(pfb_handle* h, const void* d_iq, uint64_t n, const void* hist,
       if (rc != PFB_OK) return rc;
     } else {
       p.hist_out = hist_out;
-      HIP_TRY(h->fast->launch(p, h->stream));
+      const int rc = launch_fused(h, p);
+      if (rc != PFB_OK) return rc;
       if (carried) *carried = hist_out != nullptr;
     }
     h->last_kernel = h->fast->name;
     h->last_launch = rep;
   } else {
     p.hist_out = hist_out;
-    HIP_TRY(pfb::launch_generic(p, h->stream));
+    HIP_TRY(pfb::launch_generic(p, h->stream, &h->last_entry));
     if (carried) *carried = hist_out != nullptr;
     h->last_kernel = "pfb_generic";
     h->last_launch = pfb_launch_report{};
@@ -996,6 +1014,38 @@ const char* pfb_last_kernel(const pfb_handle* h) { return h ? h->last_kernel : "
 int pfb_last_launch(const pfb_handle* h, pfb_launch_report* out) {
   if (!h || !out) return PFB_ERR_BAD_ARG;
   *out = h->last_launch;
+  return PFB_OK;
+}
+
+static void export_entry(const pfb::KernelEntry& e, pfb_kernel_entry* out) {
+  *out = pfb_kernel_entry{e.schedule, e.threads, e.dyn_lds, 0, (uint64_t)e.blocks, reinterpret_cast<uintptr_t>(e.kernel), e.tag};
+}
+
+int pfb_last_entry(const pfb_handle* h, pfb_kernel_entry* out) {
+  if (!h || !out) return PFB_ERR_BAD_ARG;
+  export_entry(h->last_entry, out);
+  return PFB_OK;
+}
+
+int pfb_plan_entry(const pfb_entry_request* rq, pfb_kernel_entry* out) {
+  pfb_fast_plan_desc plan;
+  pfb_launch_report rep;
+  if (!rq || !out || rq->struct_size != sizeof(pfb_entry_request) ||
+      pfb_fast_plan_info(rq->plan_index, &plan) != PFB_OK || pfb_plan_launch(rq->plan_index, &rq->launch, rq->frames, &rep) != PFB_OK)
+    return PFB_ERR_BAD_ARG;
+  const pfb::FastKernelInfo* fast = pfb::find_fast_kernel(plan.M, plan.P, plan.D, plan.sample_format, plan.variant);
+  if (!fast) return PFB_ERR_INTERNAL;
+  pfb::KernelParams p{};  // the fields a select may read, as launch_frames and launch_by_slabs fill them
+  p.frames = (long long)(rep.by_slabs ? std::min(rep.slab_frames, rq->frames) : rq->frames);
+  p.layout = rq->launch.channel_major && !rep.by_slabs ? PFB_LAYOUT_CHANNEL_MAJOR : PFB_LAYOUT_FRAME_MAJOR;
+  p.flags = rq->launch.magnitude ? PFB_FLAG_MAGNITUDE : 0u;
+  p.out = reinterpret_cast<float2*>((uintptr_t)(rq->out_aligned16 || rep.by_slabs ? 0 : 8));  // (a slab is a device allocation)
+  p.nontemporal = rq->nontemporal ? 1 : 0;
+  p.experiment = rq->experiment;
+  p.grid_override = rq->grid;
+  p.tile_waves = rq->tile_waves;
+  apply_policy(p, rep);
+  export_entry(fast->select(p), out);
   return PFB_OK;
 }
 

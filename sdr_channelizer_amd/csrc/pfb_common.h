@@ -97,12 +97,24 @@ static inline int bytes_per_sample(int fmt) {
   return fmt == PFB_FMT_INT8_IQ ? 2 : (fmt == PFB_FMT_INT16_IQ ? 4 : 8);
 }
 
+// The kernel one call runs: what a plan's `select` resolves a filled KernelParams to (select_fast: pfb_fast.hpp,
+// select_seg: pfb_fast_seg.hpp) and launch_blocks (pfb_fast_cfg.hpp) launches.  Selecting makes no HIP call.
+using KernelFn = void (*)(const KernelParams);
+struct KernelEntry {
+  KernelFn kernel = nullptr;  // null: the plan has no kernel for this call (launch_blocks: hipErrorInvalidValue)
+  long long blocks = 0;       // the grid as launched (after schedule 13's grid_override cap)
+  int threads = 0;
+  unsigned dyn_lds = 0;       // dynamic LDS in bytes (schedule 3: PFB_OPT_EXPERIMENT bits 8-15)
+  int schedule = 0;           // of the kernel that runs (the list at the top of pfb_fast.hpp); -1: the generic kernel
+  const char* tag = "";       // names the instantiation (grammar: pfb_channelizer_dev.h, pfb_kernel_entry), static storage
+};
+
 // Launchers implemented in pfb_kernels.hip ------------------------------------------
 // Returns nullptr if there is no fast kernel for this configuration.
-using FastLaunchFn = hipError_t (*)(const KernelParams&, hipStream_t);
+using FastSelectFn = KernelEntry (*)(const KernelParams&);
 using FastInitFn = hipError_t (*)(const float* taps, const float2* tw, float* taps_lane, float2* tw_lane, hipStream_t);
 struct FastKernelInfo {
-  FastLaunchFn launch;
+  FastSelectFn select;
   FastInitFn init_tables;
   int taps_lane_floats;
   int tw_lane_elems;
@@ -119,7 +131,7 @@ struct FastKernelInfo {
 const FastKernelInfo* find_fast_kernel(int M, int P, int D, int fmt, int variant = 0, bool channel_major = false,
                                        int* row = nullptr);
 
-hipError_t launch_generic(const KernelParams& p, hipStream_t s);
+hipError_t launch_generic(const KernelParams& p, hipStream_t s, KernelEntry* ran);  // *ran: tag `generic`, the grid it launched
 hipError_t launch_update_history(const void* old_hist, const void* in, long long n_in, void* new_hist,
                                  int hist_samples, int bytes_per_sample, hipStream_t s);
 hipError_t launch_transpose_slab(const void* slab, long long frames, int M, void* out, long long out_ld,

@@ -46,7 +46,9 @@
 //  13 (W)  pfb_fast_twin.hpp     independent workgroups of a few waves, a frame per wave and chunk, all passes of a frame by
 //          one wave                                                        (variant 3 of M = 1024 int16)
 //  small banks (M < 64): pfb_fast_seg.hpp, SegKernel
-// launch_fast below picks the schedule of a call.
+// select_fast below resolves a call -- the KernelParams the launch policy (pfb_launch_policy.h) filled -- to the one kernel
+// entry it runs: a pure function, no HIP call.  launch_blocks (pfb_fast_cfg.hpp) launches that entry, and the handle keeps
+// it (pfb_last_entry), so what ran is on record next to what was asked for.
 // Numbers 1, 5, 10 and 12 were studies that lost to the above (persistent strided chunks, persistent wave pairs, the team
 // kernel transposing through scratch tiles, the PDW screen fused into the last pass); their measurements are in
 // DESIGN.md sections 5 and 9, their code is gone.
@@ -69,9 +71,10 @@ namespace pfb {
 template <class K>
 constexpr bool kChannelMajorOk = K::NT < 1024 && !(K::NP == 3 && K::C <= 4);
 
+// Every forced combination a plan lacks falls through to the next block, at the end to the plain sliding runs: the
+// entry's schedule and tag say where it ended.
 template <class K>
-hipError_t launch_fast(const KernelParams& p, hipStream_t s) {
-  if (p.frames <= 0) return hipSuccess;
+KernelEntry select_fast(const KernelParams& p) {
   if (p.layout == PFB_LAYOUT_CHANNEL_MAJOR) {  // schedules 8, 2 and 0; the others are frame-major tuning
     if constexpr (kChannelMajorOk<K>) {
       if constexpr (K::NT == 64) {
@@ -80,17 +83,17 @@ hipError_t launch_fast(const KernelParams& p, hipStream_t s) {
             // tile_waves = waves per workgroup, frames_per_block / C = chunks per wave
             const int key = p.tile_waves * 100 + (p.schedule == 8 ? p.frames_per_block / K::C : 0);
             switch (key) {
-              case 401: if constexpr (kTileTOk<K, 4, 1>) return launch_tile_t<K, 4, 1>(p, s); break;
-              case 801: if constexpr (kTileTOk<K, 8, 1>) return launch_tile_t<K, 8, 1>(p, s); break;
-              case 202: if constexpr (kTileTOk<K, 2, 2>) return launch_tile_t<K, 2, 2>(p, s); break;
-              case 402: if constexpr (kTileTOk<K, 4, 2>) return launch_tile_t<K, 4, 2>(p, s); break;
-              case 104: if constexpr (kTileTOk<K, 1, 4>) return launch_tile_t<K, 1, 4>(p, s); break;
-              case 204: if constexpr (kTileTOk<K, 2, 4>) return launch_tile_t<K, 2, 4>(p, s); break;
+              case 401: if constexpr (kTileTOk<K, 4, 1>) return tile_t_entry<K, 4, 1>(p); break;
+              case 801: if constexpr (kTileTOk<K, 8, 1>) return tile_t_entry<K, 8, 1>(p); break;
+              case 202: if constexpr (kTileTOk<K, 2, 2>) return tile_t_entry<K, 2, 2>(p); break;
+              case 402: if constexpr (kTileTOk<K, 4, 2>) return tile_t_entry<K, 4, 2>(p); break;
+              case 104: if constexpr (kTileTOk<K, 1, 4>) return tile_t_entry<K, 1, 4>(p); break;
+              case 204: if constexpr (kTileTOk<K, 2, 4>) return tile_t_entry<K, 2, 4>(p); break;
               default: break;
             }
             // measured best: 4 waves x 2 chunks on M = 56, 64, 128; 2 waves x 4 chunks on M = 32
-            if constexpr (K::M <= 32 && kTileTOk<K, 2, 4>) return launch_tile_t<K, 2, 4>(p, s);
-            return launch_tile_t<K, 4, 2>(p, s);
+            if constexpr (K::M <= 32 && kTileTOk<K, 2, 4>) return tile_t_entry<K, 2, 4>(p);
+            return tile_t_entry<K, 4, 2>(p);
           }
         }
         // one chunk per wave, NWV adjacent chunks per workgroup: the workgroup writes NWV * C consecutive frames of
@@ -99,14 +102,14 @@ hipError_t launch_fast(const KernelParams& p, hipStream_t s) {
         if (p.schedule == 2 || p.schedule < 0) {
           const int nwv = p.schedule < 0 ? (K::M <= 64 ? 16 : 8) : p.tile_waves;
           if constexpr (16 * sizeof(float2) * K::LDS_ELEMS <= 160 * 1024) {
-            if (nwv == 16) return launch_tile<K, 16, true>(p, s);
+            if (nwv == 16) return tile_entry<K, 16, true>(p);
           }
-          return launch_tile<K, 8, true>(p, s);
+          return tile_entry<K, 8, true>(p);
         }
       }
-      return launch_sliding<K, true>(p, s);
+      return sliding_entry<K, true>(p);
     } else {
-      return hipErrorInvalidValue;  // find_fast_kernel never hands this plan to a channel-major handle
+      return KernelEntry{};  // no kernel: find_fast_kernel never hands this plan to a channel-major handle
     }
   }
   // (measured on cfg3, cfg5 and M=56 too: slower than their sliding runs, so only the M=64 kernels carry it)
@@ -118,34 +121,34 @@ hipError_t launch_fast(const KernelParams& p, hipStream_t s) {
       // (workgroups of ONE or TWO pairs -- a barrier that couples 2 or 4 waves, 8 or 4 workgroups per CU -- measured: cfg2
       // 0.61-0.65 against 0.72 for its 8 halo-sharing pairs, M = 56 0.58-0.61 against 0.62, cfg5 0.44-0.49 against 0.68;
       // profiles/r03_tiny_pair_workgroups_ab.txt; four pairs at two workgroups per CU: M = 56 0.575-0.605 against 0.608)
-      if (p.tile_waves == 4) return launch_pairs_sliding<K, 4, 2>(p, s);
+      if (p.tile_waves == 4) return pairs_sliding_entry<K, 4, 2>(p);
       if constexpr (K::MIN_WAVES >= 4 && 8 * kPair <= 160 * 1024) {
-        if (p.tile_waves >= 8) return launch_pairs_sliding_roles<K, 8, 4>(p, s);
+        if (p.tile_waves >= 8) return pairs_sliding_roles_entry<K, 8, 4>(p);
       }
-      return launch_pairs_sliding_roles<K, 6, 3>(p, s);
+      return pairs_sliding_roles_entry<K, 6, 3>(p);
     }
   }
   if constexpr (kOverlapOk<K>) {  // sliding runs, FIR of the next chunk scheduled into the FFT of this one
-    if (p.schedule == 11) return launch_overlap<K>(p, s);
+    if (p.schedule == 11) return overlap_entry<K>(p);
   }
   if constexpr (kTwinOk<K>) {  // independent workgroups, a frame per wave and chunk
     if (p.schedule == 13) {
-      if (p.layout != PFB_LAYOUT_FRAME_MAJOR) return hipErrorInvalidValue;
-      return launch_twin<K>(p, s);
+      if (p.layout != PFB_LAYOUT_FRAME_MAJOR) return KernelEntry{};  // no kernel
+      return twin_entry<K>(p);
     }
   }
   if constexpr (kTeamsOk<K>) {  // FIR team + FFT team
-    if (p.schedule == 6) return launch_teams<K>(p, s);
+    if (p.schedule == 6) return teams_entry<K>(p);
   }
   if constexpr (K::NT == 64 && K::NP == 2 && !K::PINGPONG && K::M == 64 && K::C == 8) {
     if (p.schedule == 4) {  // FIR / FFT wave pairs: tile_waves = pairs per workgroup, frames_per_block = run length
       const int key = p.tile_waves * 1000 + p.frames_per_block;
       if constexpr (K::FMT == PFB_FMT_INT16_IQ && K::M == 64 && K::P == 12) {  // tuning sweep set (cfg2 only, keeps build time sane)
         switch (key) {
-          case 4064: return launch_paired<K, 4, 64, 4>(p, s);
-          case 5064: return launch_paired<K, 5, 64, 5>(p, s);   // 10-wave workgroups, 5 waves per SIMD
-          case 8048: return launch_paired<K, 8, 48, 4>(p, s);
-          case 8128: return launch_paired<K, 8, 128, 4>(p, s);
+          case 4064: return paired_entry<K, 4, 64, 4>(p);
+          case 5064: return paired_entry<K, 5, 64, 5>(p);   // 10-wave workgroups, 5 waves per SIMD
+          case 8048: return paired_entry<K, 8, 48, 4>(p);
+          case 8128: return paired_entry<K, 8, 128, 4>(p);
           default: break;
         }
       }
@@ -155,46 +158,46 @@ hipError_t launch_fast(const KernelParams& p, hipStream_t s) {
       // (the shape a call runs by default has the output type and the store kind compiled in; the sweep set above and
       // the 4-pair option test the flags per store)
       if constexpr (8 * kPair + 9 * kSlot <= 160 * 1024) {
-        if (p.tile_waves == 4) return launch_paired<K, 4, 64, 2>(p, s);
-        return launch_paired_roles<K, 8, 64, 4>(p, s);
+        if (p.tile_waves == 4) return paired_entry<K, 4, 64, 2>(p);
+        return paired_roles_entry<K, 8, 64, 4>(p);
       } else {
-        return launch_paired_roles<K, 4, 64, 2>(p, s);
+        return paired_roles_entry<K, 4, 64, 2>(p);
       }
     }
   }
   if constexpr (K::NT == 64 && K::C == 8 && !K::PINGPONG) {
     if (p.schedule == 3) {  // shared-halo sliding windows: tile_waves runs of frames_per_block frames
       const int key = p.tile_waves * 1000 + p.frames_per_block;
-      hipError_t r = hipErrorNotSupported;
-      if (key == 8024) r = launch_shared<K, 8, 24>(p, s);
-      else if (key == 8032) r = launch_shared<K, 8, 32>(p, s);
-      else if (key == 8064) r = launch_shared<K, 8, 64>(p, s);
-      else if (key == 4064) r = launch_shared<K, 4, 64>(p, s);
+      KernelEntry e;
+      if (key == 8024) e = shared_entry<K, 8, 24>(p);
+      else if (key == 8032) e = shared_entry<K, 8, 32>(p);
+      else if (key == 8064) e = shared_entry<K, 8, 64>(p);
+      else if (key == 4064) e = shared_entry<K, 4, 64>(p);
       else {
         bool done = false;
         if constexpr (K::FMT == PFB_FMT_INT16_IQ && K::M == 64 && K::P == 12) {  // tuning sweep set (cfg2 only, keeps build time sane)
           switch (key) {
-            case 4032: r = launch_shared<K, 4, 32>(p, s); done = true; break;
-            case 8048: r = launch_shared<K, 8, 48>(p, s); done = true; break;
-            case 16024: r = launch_shared<K, 16, 24>(p, s); done = true; break;
+            case 4032: e = shared_entry<K, 4, 32>(p); done = true; break;
+            case 8048: e = shared_entry<K, 8, 48>(p); done = true; break;
+            case 16024: e = shared_entry<K, 16, 24>(p); done = true; break;
             default: break;
           }
         }
-        if (!done) r = launch_shared<K, 8, 24>(p, s);  // any other shape: the tuned default
+        if (!done) e = shared_entry<K, 8, 24>(p);  // any other shape: the tuned default
       }
-      if (r != hipErrorNotSupported) return r;  // (no tile fits this sample format: the plain sliding runs below)
+      if (e.kernel) return e;  // (no tile fits this sample format: the plain sliding runs below)
     }
   }
   if constexpr (K::NT == 64 && K::M == 64 && K::FMT == PFB_FMT_INT16_IQ && K::C == 8 && K::P == 12) {  // access-shape study schedules (cfg2 only)
     if (p.schedule == 2) {  // one chunk per wave, tile_waves adjacent chunks per workgroup
-      if (p.tile_waves == 1) return launch_tile<K, 1>(p, s);
-      return launch_tile<K, 8>(p, s);
+      if (p.tile_waves == 1) return tile_entry<K, 1>(p);
+      return tile_entry<K, 8>(p);
     }
   }
   if constexpr (kMagStagedOk<K>) {
-    if (wants_magnitude(p) && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0) return launch_sliding<K, false, true>(p, s);
+    if (wants_magnitude(p) && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0) return sliding_entry<K, false, true>(p);
   }
-  return wants_magnitude(p) ? launch_sliding<K, false, false, 1>(p, s) : launch_sliding<K, false, false, 0>(p, s);
+  return wants_magnitude(p) ? sliding_entry<K, false, false, 1>(p) : sliding_entry<K, false, false, 0>(p);
 }
 
 }  // namespace pfb

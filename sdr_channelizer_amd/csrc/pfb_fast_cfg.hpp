@@ -1,5 +1,5 @@
 // pfb_fast_cfg.hpp -- what every fused kernel is configured and launched with: the plan (FastCfg), the workgroup
-// remap over the XCDs, the row loads, the per-handle tables and the host-side launch helper.  See pfb_fast.hpp.
+// remap over the XCDs, the row loads, the per-handle tables, the kernel tags and the one host-side launch.  See pfb_fast.hpp.
 #pragma once
 
 #include "pfb_cplx.hpp"
@@ -240,16 +240,55 @@ hipError_t init_tables(const float* taps, const float2* tw, float* taps_lane, fl
   return hipGetLastError();
 }
 
-// Host side of every launch of the family: `blocks` workgroups of `threads` threads, then the launch's own error.
-inline hipError_t launch_blocks(void (*kernel)(const KernelParams), long long blocks, int threads, const KernelParams& p,
-                                hipStream_t s, unsigned dyn_lds = 0) {
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)threads), dyn_lds, s, p);
+// Host side of every launch of the family, and the only one: the entry a plan's select resolved the call to.
+inline hipError_t launch_blocks(const KernelEntry& e, const KernelParams& p, hipStream_t s) {
+  if (p.frames <= 0) return hipSuccess;
+  if (e.kernel == nullptr) return hipErrorInvalidValue;  // the plan has no kernel for this call
+  hipLaunchKernelGGL(e.kernel, dim3((unsigned)e.blocks), dim3((unsigned)e.threads), e.dyn_lds, s, p);
   return hipGetLastError();
 }
 
-// workgroups that cover the call's frames, `per` frames each
-inline long long blocks_for(const KernelParams& p, long long per) { return (p.frames + per - 1) / per; }
-
 inline bool wants_magnitude(const KernelParams& p) { return (p.flags & PFB_FLAG_MAGNITUDE) != 0; }
+
+// A kernel's tag (grammar: pfb_channelizer_dev.h): its family, its integer template arguments as the source writes them
+// and its compile-time roles.  Every schedule header builds the tag in the function that takes the kernel's address, from
+// that function's own template arguments, so that one kernel has one tag.
+struct KernelTag {
+  char s[40] = {};
+  int n = 0;
+  constexpr void put(const char* t) { while (*t) s[n++] = *t++; }
+  constexpr void num(int v) { if (v >= 10) num(v / 10); s[n++] = (char)('0' + v % 10); }
+};
+struct TagRoles { bool cm = false, ms = false; int magsel = -1, ntsel = -1; };
+
+template <int... ARGS>
+constexpr KernelTag kernel_tag(const char* family, TagRoles r = {}) {
+  KernelTag t;
+  t.put(family);
+  if constexpr (sizeof...(ARGS) > 0) {
+    bool first = true;
+    ((t.put(first ? "<" : ","), t.num(ARGS), first = false), ...);
+    t.put(">");
+  }
+  if (r.cm) t.put("+cm");
+  if (r.ms) t.put("+ms");
+  if (r.magsel >= 0) t.put(r.magsel ? "+mag" : "+c64");
+  if (r.ntsel > 0) t.put("+nt");
+  return t;
+}
+
+// the entry of `kernel` (schedule number `schedule`) for this call: workgroups of `threads` threads, `per` frames each
+inline KernelEntry entry_for(KernelFn kernel, int schedule, const char* tag, const KernelParams& p, long long per,
+                             int threads, unsigned dyn_lds = 0) {
+  return KernelEntry{kernel, (p.frames + per - 1) / per, threads, dyn_lds, schedule, tag};
+}
+
+// The call's output type and store kind as compile-time roles <MAGSEL, NTSEL> of a kernel: complex temporal, complex
+// nontemporal, or magnitudes (whose stores are always temporal).
+template <class F>
+KernelEntry with_store_roles(const KernelParams& p, F&& entry) {
+  if (wants_magnitude(p)) return entry.template operator()<1, 0>();
+  return p.nontemporal ? entry.template operator()<0, 1>() : entry.template operator()<0, 0>();
+}
 
 }  // namespace pfb

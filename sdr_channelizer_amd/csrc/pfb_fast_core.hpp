@@ -78,7 +78,7 @@ struct FastKernel : FastRows<K> {
           // distinct banks) and leave as 16 bytes per lane: 4 frames x 256 contiguous bytes per instruction.
           // (the sliding-run kernel only: there it is worth 7 %, 2.07 -> 1.93 ms per 2^30 samples, and makes sliding
           // runs the fastest way to magnitudes; on the FFT wave of the pair schedules the extra LDS trip costs 2 %.
-          // launch_fast picks this instantiation when the flag is set and `out` is 16-byte aligned.)
+          // select_fast picks this instantiation when the flag is set and `out` is 16-byte aligned.)
           static_assert(!CM && NT == 64 && ITERS == 1 && K::NP == 2 && !K::PINGPONG && M % 4 == 0, "single-wave two-pass plans");
           {
             constexpr int SR = M + ((8 - M % 64) + 64) % 64;  // = 8 (mod 64), a multiple of 4

@@ -226,39 +226,34 @@ __global__ void __launch_bounds__(128 * NPAIR, MINW) pfb_paired_kernel(const Ker
 }
 
 template <class K, int NPAIR, int L, int MINW, int MAGSEL = -1, int NTSEL = -1>
-hipError_t launch_paired(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(&pfb_paired_kernel<K, NPAIR, L, MINW, MAGSEL, NTSEL>, blocks_for(p, (long long)NPAIR * L), 128 * NPAIR, p, s);
+KernelEntry paired_entry(const KernelParams& p) {
+  static constexpr KernelTag tag = kernel_tag<NPAIR, L, MINW>("paired", {false, false, MAGSEL, NTSEL});
+  return entry_for(&pfb_paired_kernel<K, NPAIR, L, MINW, MAGSEL, NTSEL>, 4, tag.s, p, (long long)NPAIR * L, 128 * NPAIR);
 }
 
-// The call's output type and store kind as compile-time roles of the kernel: complex temporal, complex nontemporal, or
-// magnitudes (whose stores are always temporal).
+// with the call's output type and store kind compiled in (with_store_roles, pfb_fast_cfg.hpp)
 template <class K, int NPAIR, int L, int MINW>
-hipError_t launch_paired_roles(const KernelParams& p, hipStream_t s) {
-  if (wants_magnitude(p)) return launch_paired<K, NPAIR, L, MINW, 1, 0>(p, s);
-  return p.nontemporal ? launch_paired<K, NPAIR, L, MINW, 0, 1>(p, s) : launch_paired<K, NPAIR, L, MINW, 0, 0>(p, s);
+KernelEntry paired_roles_entry(const KernelParams& p) {
+  return with_store_roles(p, [&]<int MAGSEL, int NTSEL>() { return paired_entry<K, NPAIR, L, MINW, MAGSEL, NTSEL>(p); });
 }
 
 template <class K, int NWV>
 constexpr bool kSharedFits = sizeof(float2) * NWV * K::LDS_ELEMS +
                                  sizeof(typename SampleT<K::FMT>::raw_t) * (NWV + 1) * (K::W - 1) * K::D <= 160 * 1024;
 
-template <class K, int NWV, int L>
-hipError_t launch_shared_impl(const KernelParams& p, hipStream_t s) {
-  // experiment bits 8.. : extra dynamic LDS in KiB (occupancy throttle for access-window studies)
-  const unsigned extra_lds = (unsigned)((p.experiment >> 8) & 0xff) * 1024u;
-  return launch_blocks(&pfb_shared_kernel<K, NWV, L>, blocks_for(p, (long long)NWV * L), 64 * NWV, p, s, extra_lds);
-}
-
 // a tile of NWV waves whose chunk buffers + shared halo do not fit one CU's LDS for this sample format (8-byte samples
-// at M = 128) takes the 4-wave tile; hipErrorNotSupported = not even that: the caller goes on to the plain sliding runs
+// at M = 128) takes the 4-wave tile; no kernel = not even that: the caller goes on to the plain sliding runs
 template <class K, int NWV, int L>
-hipError_t launch_shared(const KernelParams& p, hipStream_t s) {
+KernelEntry shared_entry(const KernelParams& p) {
   if constexpr (kSharedFits<K, NWV>) {
-    return launch_shared_impl<K, NWV, L>(p, s);
+    static constexpr KernelTag tag = kernel_tag<NWV, L>("shared");
+    // experiment bits 8.. : extra dynamic LDS in KiB (occupancy throttle for access-window studies)
+    const unsigned extra_lds = (unsigned)((p.experiment >> 8) & 0xff) * 1024u;
+    return entry_for(&pfb_shared_kernel<K, NWV, L>, 3, tag.s, p, (long long)NWV * L, 64 * NWV, extra_lds);
   } else if constexpr (NWV > 4 && kSharedFits<K, 4>) {
-    return launch_shared_impl<K, 4, 64>(p, s);
+    return shared_entry<K, 4, 64>(p);
   } else {
-    return hipErrorNotSupported;
+    return KernelEntry{};
   }
 }
 

@@ -230,9 +230,10 @@ template <class K>
 constexpr bool kOverlapOk = K::NT == 64 && K::NP == 2 && !K::PINGPONG;
 
 template <class K>
-hipError_t launch_overlap(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(wants_magnitude(p) ? &pfb_overlap_kernel<K, true> : &pfb_overlap_kernel<K, false>,
-                       blocks_for(p, p.frames_per_block), K::NT, p, s);
+KernelEntry overlap_entry(const KernelParams& p) {
+  static constexpr KernelTag mag = kernel_tag<>("overlap", {.magsel = 1}), c64 = kernel_tag<>("overlap", {.magsel = 0});
+  return wants_magnitude(p) ? entry_for(&pfb_overlap_kernel<K, true>, 11, mag.s, p, p.frames_per_block, K::NT)
+                            : entry_for(&pfb_overlap_kernel<K, false>, 11, c64.s, p, p.frames_per_block, K::NT);
 }
 
 }  // namespace pfb

@@ -109,15 +109,15 @@ __global__ void __launch_bounds__(128 * NPAIR, MINW) pfb_pairs_sliding_kernel(co
 }
 
 template <class K, int NPAIR, int MINW, int MAGSEL = -1, int NTSEL = -1>
-hipError_t launch_pairs_sliding(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(&pfb_pairs_sliding_kernel<K, NPAIR, MINW, MAGSEL, NTSEL>, blocks_for(p, (long long)NPAIR * p.frames_per_block), 128 * NPAIR, p, s);
+KernelEntry pairs_sliding_entry(const KernelParams& p) {
+  static constexpr KernelTag tag = kernel_tag<NPAIR, MINW>("pairs_sliding", {false, false, MAGSEL, NTSEL});
+  return entry_for(&pfb_pairs_sliding_kernel<K, NPAIR, MINW, MAGSEL, NTSEL>, 7, tag.s, p, (long long)NPAIR * p.frames_per_block, 128 * NPAIR);
 }
 
-// as launch_paired_roles (pfb_fast_halo.hpp): output type and store kind as compile-time roles
+// with the call's output type and store kind compiled in (with_store_roles, pfb_fast_cfg.hpp)
 template <class K, int NPAIR, int MINW>
-hipError_t launch_pairs_sliding_roles(const KernelParams& p, hipStream_t s) {
-  if (wants_magnitude(p)) return launch_pairs_sliding<K, NPAIR, MINW, 1, 0>(p, s);
-  return p.nontemporal ? launch_pairs_sliding<K, NPAIR, MINW, 0, 1>(p, s) : launch_pairs_sliding<K, NPAIR, MINW, 0, 0>(p, s);
+KernelEntry pairs_sliding_roles_entry(const KernelParams& p) {
+  return with_store_roles(p, [&]<int MAGSEL, int NTSEL>() { return pairs_sliding_entry<K, NPAIR, MINW, MAGSEL, NTSEL>(p); });
 }
 
 }  // namespace pfb

@@ -188,13 +188,17 @@ __global__ void __launch_bounds__(64, K::MIN_WAVES) pfb_seg_kernel(const KernelP
   SegKernel<K>::template run<MAG ? 1 : 0, CMAJ ? 1 : 0>(p, lds);
 }
 
+template <class K, bool MAG, bool CMAJ>
+KernelEntry seg_entry_for(const KernelParams& p) {
+  static constexpr KernelTag tag = kernel_tag<>("seg", {.cm = CMAJ, .magsel = MAG ? 1 : 0});
+  return entry_for(&pfb_seg_kernel<K, MAG, CMAJ>, 0, tag.s, p, p.frames_per_block, 64);
+}
+
 template <class K>
-hipError_t launch_seg(const KernelParams& p, hipStream_t s) {
-  if (p.frames <= 0) return hipSuccess;
+KernelEntry select_seg(const KernelParams& p) {
   const bool mag = wants_magnitude(p), cm = p.layout == PFB_LAYOUT_CHANNEL_MAJOR;
-  return launch_blocks(mag ? (cm ? &pfb_seg_kernel<K, true, true> : &pfb_seg_kernel<K, true, false>)
-                           : (cm ? &pfb_seg_kernel<K, false, true> : &pfb_seg_kernel<K, false, false>),
-                       blocks_for(p, p.frames_per_block), 64, p, s);
+  return mag ? (cm ? seg_entry_for<K, true, true>(p) : seg_entry_for<K, true, false>(p))
+             : (cm ? seg_entry_for<K, false, true>(p) : seg_entry_for<K, false, false>(p));
 }
 
 }  // namespace pfb

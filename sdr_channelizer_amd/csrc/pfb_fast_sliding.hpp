@@ -100,8 +100,9 @@ __global__ void __launch_bounds__(K::NT, K::MIN_WAVES) pfb_fast_kernel(const Ker
 }
 
 template <class K, bool CM = false, bool MS = false, int MAGSEL = -1>
-hipError_t launch_sliding(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(&pfb_fast_kernel<K, CM, MS, MAGSEL>, blocks_for(p, p.frames_per_block), K::NT, p, s);
+KernelEntry sliding_entry(const KernelParams& p) {
+  static constexpr KernelTag tag = kernel_tag<>("sliding", {CM, MS, MAGSEL});
+  return entry_for(&pfb_fast_kernel<K, CM, MS, MAGSEL>, 0, tag.s, p, p.frames_per_block, K::NT);
 }
 
 }  // namespace pfb

@@ -191,9 +191,10 @@ __global__ void __launch_bounds__(K::NT + 64 * K::C, K::MIN_WAVES) pfb_teams_ker
 }
 
 template <class K>
-hipError_t launch_teams(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(wants_magnitude(p) ? &pfb_teams_kernel<K, true> : &pfb_teams_kernel<K, false>,
-                       blocks_for(p, p.frames_per_block), K::NT + 64 * K::C, p, s);
+KernelEntry teams_entry(const KernelParams& p) {
+  static constexpr KernelTag mag = kernel_tag<>("teams", {.magsel = 1}), c64 = kernel_tag<>("teams", {.magsel = 0});
+  return wants_magnitude(p) ? entry_for(&pfb_teams_kernel<K, true>, 6, mag.s, p, p.frames_per_block, K::NT + 64 * K::C)
+                            : entry_for(&pfb_teams_kernel<K, false>, 6, c64.s, p, p.frames_per_block, K::NT + 64 * K::C);
 }
 
 }  // namespace pfb

@@ -152,8 +152,9 @@ __global__ void __launch_bounds__(64 * NWV) pfb_tile_kernel(const KernelParams p
 }
 
 template <class K, int NWV, bool CM = false>
-hipError_t launch_tile(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(&pfb_tile_kernel<K, NWV, CM>, blocks_for(p, (long long)NWV * K::C), 64 * NWV, p, s);
+KernelEntry tile_entry(const KernelParams& p) {
+  static constexpr KernelTag tag = kernel_tag<NWV>("tile", {CM});
+  return entry_for(&pfb_tile_kernel<K, NWV, CM>, 2, tag.s, p, (long long)NWV * K::C, 64 * NWV);
 }
 
 template <class K, int NWV, int CPW>
@@ -164,8 +165,9 @@ __global__ void __launch_bounds__(64 * NWV) pfb_tile_t_kernel(const KernelParams
 }
 
 template <class K, int NWV, int CPW>
-hipError_t launch_tile_t(const KernelParams& p, hipStream_t s) {
-  return launch_blocks(&pfb_tile_t_kernel<K, NWV, CPW>, blocks_for(p, (long long)NWV * CPW * K::C), 64 * NWV, p, s);
+KernelEntry tile_t_entry(const KernelParams& p) {
+  static constexpr KernelTag tag = kernel_tag<NWV, CPW>("tile_t");
+  return entry_for(&pfb_tile_t_kernel<K, NWV, CPW>, 8, tag.s, p, (long long)NWV * CPW * K::C, 64 * NWV);
 }
 
 // the transposed tile: single-wave two-pass plans whose chunk buffer holds the transposed chunk, rows of whole

@@ -411,10 +411,12 @@ __global__ void __launch_bounds__(K::NT, K::MIN_WAVES) pfb_twin_kernel(const Ker
 
 // grid_override: resident workgroups walking runs b, b + G, ...
 template <class K>
-hipError_t launch_twin(const KernelParams& p, hipStream_t s) {
-  long long nb = blocks_for(p, p.frames_per_block);
-  if (p.grid_override > 0 && nb > p.grid_override) nb = p.grid_override;
-  return launch_blocks(wants_magnitude(p) ? &pfb_twin_kernel<K, true> : &pfb_twin_kernel<K, false>, nb, K::NT, p, s);
+KernelEntry twin_entry(const KernelParams& p) {
+  static constexpr KernelTag mag = kernel_tag<>("twin", {.magsel = 1}), c64 = kernel_tag<>("twin", {.magsel = 0});
+  KernelEntry e = wants_magnitude(p) ? entry_for(&pfb_twin_kernel<K, true>, 13, mag.s, p, p.frames_per_block, K::NT)
+                                     : entry_for(&pfb_twin_kernel<K, false>, 13, c64.s, p, p.frames_per_block, K::NT);
+  if (p.grid_override > 0 && e.blocks > p.grid_override) e.blocks = p.grid_override;
+  return e;
 }
 
 }  // namespace pfb

@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(256) pfb_generic_kernel(const KernelParams p, 
   }
 }
 
-hipError_t launch_generic(const KernelParams& p, hipStream_t s) {
+hipError_t launch_generic(const KernelParams& p, hipStream_t s, KernelEntry* ran) {
   if (p.frames <= 0) return hipSuccess;
   const int M = p.M;
   int log2m = -1;
@@ -137,6 +137,8 @@ hipError_t launch_generic(const KernelParams& p, hipStream_t s) {
   if (log2m < 0) plan = make_generic_plan(M);  // band counts 2^a 3^b 5^c 7^d without a fused shape
   const long long blocks = (p.frames + tile - 1) / tile;
   hipLaunchKernelGGL(pfb_generic_kernel, dim3((unsigned)blocks), dim3(256), shmem, s, p, tile, log2m, plan);
+  // (its kernel takes more than the KernelParams: the address is kept for comparison only, launch_blocks never sees it)
+  *ran = KernelEntry{reinterpret_cast<KernelFn>(&pfb_generic_kernel), blocks, 256, (unsigned)shmem, -1, "generic"};
   return hipGetLastError();
 }
 

@@ -11,7 +11,9 @@ REL_TOL = 1e-5  # north star: <= 1e-5 relative error
 FMT = {"int8": L.PFB_FMT_INT8_IQ, "int16": L.PFB_FMT_INT16_IQ, "cf32": L.PFB_FMT_CF32}
 FMT_NAME = {code: name for name, code in FMT.items()}
 BPS = {"int8": 2, "int16": 4, "cf32": 8}   # bytes per input sample
-# every schedule pfb_set_option accepts but 9 (channel-major by slabs, a route): a plan without one runs its sliding runs
+# every schedule pfb_set_option accepts but 9 (channel-major by slabs, a route).  A forced schedule, pair count or tile a
+# plan lacks falls through inside select_fast (pfb_fast.hpp) -- in the end to the plan's sliding runs -- while the launch
+# report keeps saying what was asked for: which kernel ran is the kernel entry's schedule and tag (last_entry, plan_entry)
 SCHEDULES = (-1, 0, 2, 3, 4, 6, 7, 8, 11, 13)
 
 # tests/test_gpu_fuzz.py's list: (M, P, D, formats, schedules worth forcing besides the default)
@@ -149,3 +151,122 @@ def sweep_lengths(D, c, hist_samples):
     lens = walk_lengths(D, 2 * c + 1, hist_samples, both=2 * c + 1)
     assert sum(lens) % D == 0   # it ends on a boundary
     return lens + [top_frames(c) * D + D // 2]
+
+
+# ---- kernel entries (pfb_kernel_entry, pfb_channelizer_dev.h) --------------------------------------------------------
+
+def tag_parts(tag):
+    """family, integer arguments and roles of a kernel tag (the grammar in pfb_channelizer_dev.h)"""
+    head, *roles = tag.split("+")
+    family, _, args = head.partition("<")
+    return family, tuple(int(a) for a in args.rstrip(">").split(",")) if args else (), tuple(roles)
+
+
+def entry_geometry(tag, d, frames_per_block):
+    """(frames per workgroup, threads per workgroup) of the kernel `tag` names on table row d, from the kernels' own
+    headers: what blocks and threads of an entry must be consistent with."""
+    family, a, _ = tag_parts(tag)
+    c, fpb = d.chunk_frames, frames_per_block
+    return {"sliding": lambda: (fpb, d.threads), "overlap": lambda: (fpb, d.threads), "twin": lambda: (fpb, d.threads),
+            "seg": lambda: (fpb, 64), "teams": lambda: (fpb, d.threads + 64 * c),
+            "tile": lambda: (a[0] * c, 64 * a[0]), "tile_t": lambda: (a[0] * a[1] * c, 64 * a[0]),
+            "shared": lambda: (a[0] * a[1], 64 * a[0]), "paired": lambda: (a[0] * a[1], 128 * a[0]),
+            "pairs_sliding": lambda: (a[0] * fpb, 128 * a[0])}[family]()
+
+
+CFG2, M64F32, M64I8, M64P16 = ("pfb_fast<M64,P12,D64,int16>", "pfb_fast<M64,P12,D64,cf32>", "pfb_fast<M64,P12,D64,int8>",
+                               "pfb_fast<M64,P16,D64,int16>")
+CFG5, CFG5F32, M56 = "pfb_fast<M128,P12,D64,int16>", "pfb_fast<M128,P12,D64,cf32>", "pfb_fast<M56,P12,D56,int16>"
+M32, M1024, DUO = "pfb_fast<M32,P12,D32,int16>", "pfb_fast<M1024,P16,D1024,int16>", "pfb_fast<M1024,P16,D1024,int16,duo>"
+M8F32, CFG3I8 = "pfb_fast<M8,P12,D8,cf32>", "pfb_fast<M256,P8,D256,int8>"
+
+# (family of the GPU test, row, options, frames of the call, entry schedule, tag): literals read off the dispatch of the
+# commit before select_fast existed (launch_fast in pfb_fast.hpp), not off what the library answers.  Options: schedule,
+# frames_per_block, tile_waves, nontemporal, grid, experiment, magnitude, channel_major, out_aligned16.  The frames cover
+# two whole workgroups of the entry and a partial third where the options fix the workgroup's frames; the policy's own
+# run lengths (no frames_per_block) spread a call this short over more workgroups than that.
+ENTRY_CASES = [
+    # cfg2, schedule 4: key = tile_waves * 1000 + frames_per_block; the four keys of the sweep set, then the tuned
+    # 8 x 64 shape in its three compiled-in roles
+    ("cfg2", CFG2, dict(schedule=4, tile_waves=4, frames_per_block=64), 643, 4, "paired<4,64,4>"),
+    ("cfg2", CFG2, dict(schedule=4, tile_waves=5, frames_per_block=64), 803, 4, "paired<5,64,5>"),
+    ("cfg2", CFG2, dict(schedule=4, tile_waves=8, frames_per_block=48), 963, 4, "paired<8,48,4>"),
+    ("cfg2", CFG2, dict(schedule=4, tile_waves=8, frames_per_block=128), 2563, 4, "paired<8,128,4>"),
+    ("cfg2", CFG2, dict(schedule=4, tile_waves=8, frames_per_block=64), 1283, 4, "paired<8,64,4>+c64"),
+    ("cfg2", CFG2, dict(schedule=4, nontemporal=True), 1283, 4, "paired<8,64,4>+c64+nt"),
+    ("cfg2", CFG2, dict(schedule=4, magnitude=True), 1283, 4, "paired<8,64,4>+mag"),
+    # tile_waves = 4 without a run length is key 4064 on cfg2 (the sweep set), 4 x 64 at 2 waves per SIMD elsewhere
+    ("cfg2", CFG2, dict(schedule=4, tile_waves=4), 643, 4, "paired<4,64,4>"),
+    ("cfg2", CFG2, dict(schedule=4, tile_waves=4, frames_per_block=48), 643, 4, "paired<4,64,2>"),
+    ("m64", M64F32, dict(schedule=4, tile_waves=4), 643, 4, "paired<4,64,2>"),
+    ("m64", M64I8, dict(schedule=4, tile_waves=4), 643, 4, "paired<4,64,2>"),
+    ("m64", M64P16, dict(schedule=4, tile_waves=4), 643, 4, "paired<4,64,2>"),
+    # a forced run length no key names: the report says 16-frame runs, the kernel runs 8 x 64
+    ("cfg2", CFG2, dict(schedule=4, frames_per_block=16), 1283, 4, "paired<8,64,4>+c64"),
+    ("cfg2", CFG2, dict(schedule=4, frames_per_block=40), 1283, 4, "paired<8,64,4>+c64"),
+    # cfg2, schedule 3: the four keys every plan has, the three of the sweep set, and the tuned default for any other
+    ("cfg2", CFG2, dict(schedule=3, tile_waves=8, frames_per_block=24), 483, 3, "shared<8,24>"),
+    ("cfg2", CFG2, dict(schedule=3, tile_waves=8, frames_per_block=32), 643, 3, "shared<8,32>"),
+    ("cfg2", CFG2, dict(schedule=3, tile_waves=8, frames_per_block=64), 1283, 3, "shared<8,64>"),
+    ("cfg2", CFG2, dict(schedule=3, tile_waves=4, frames_per_block=64), 643, 3, "shared<4,64>"),
+    ("cfg2", CFG2, dict(schedule=3, tile_waves=4, frames_per_block=32), 323, 3, "shared<4,32>"),
+    ("cfg2", CFG2, dict(schedule=3, tile_waves=8, frames_per_block=48), 963, 3, "shared<8,48>"),
+    ("cfg2", CFG2, dict(schedule=3, tile_waves=16, frames_per_block=24), 963, 3, "shared<16,24>"),
+    ("cfg2", CFG2, dict(schedule=3, tile_waves=6, frames_per_block=40), 483, 3, "shared<8,24>"),
+    # cfg2: the access-shape tiles, the defaults per output type and layout, the staged magnitudes and their fall-back
+    ("cfg2", CFG2, dict(schedule=2, tile_waves=1), 23, 2, "tile<1>"),
+    ("cfg2", CFG2, dict(schedule=2, tile_waves=4), 163, 2, "tile<8>"),
+    ("cfg2", CFG2, dict(), 1283, 4, "paired<8,64,4>+c64"),
+    ("cfg2", CFG2, dict(channel_major=True), 163, 8, "tile_t<4,2>"),
+    ("cfg2", CFG2, dict(channel_major=True, schedule=2), 323, 2, "tile<8>+cm"),
+    ("cfg2", CFG2, dict(channel_major=True, schedule=2, tile_waves=16), 323, 2, "tile<16>+cm"),
+    ("cfg2", CFG2, dict(channel_major=True, schedule=0, frames_per_block=64), 163, 0, "sliding+cm"),
+    ("cfg2", CFG2, dict(magnitude=True, frames_per_block=64), 163, 0, "sliding+ms"),
+    ("cfg2", CFG2, dict(magnitude=True, frames_per_block=64, out_aligned16=False), 163, 0, "sliding+mag"),
+    # M = 64 cf32: magnitudes stay on wave pairs
+    ("m64", M64F32, dict(), 1283, 4, "paired<8,64,4>+c64"),
+    ("m64", M64F32, dict(magnitude=True, frames_per_block=64), 1283, 7, "pairs_sliding<8,4>+mag"),
+    # schedule 7: 4 pairs on request, 8 where the single-wave kernel runs 4 waves per SIMD and the LDS holds them, else 6
+    ("m56", M56, dict(schedule=7, tile_waves=4, frames_per_block=64), 643, 7, "pairs_sliding<4,2>"),
+    ("m56", M56, dict(schedule=7, tile_waves=6, frames_per_block=64), 963, 7, "pairs_sliding<6,3>+c64"),
+    ("m56", M56, dict(schedule=7, tile_waves=8, frames_per_block=64), 1283, 7, "pairs_sliding<8,4>+c64"),
+    ("m56", M56, dict(), 2603, 7, "pairs_sliding<8,4>+c64"),
+    ("m128", CFG5, dict(schedule=7, tile_waves=4, frames_per_block=64), 643, 7, "pairs_sliding<4,2>"),
+    ("m128", CFG5, dict(schedule=7, tile_waves=6, frames_per_block=64), 963, 7, "pairs_sliding<6,3>+c64"),
+    ("m128", CFG5, dict(schedule=7, tile_waves=8, frames_per_block=64), 963, 7, "pairs_sliding<6,3>+c64"),
+    ("m128", CFG5, dict(), 2603, 11, "overlap+c64"),
+    ("m128", CFG5, dict(magnitude=True), 2603, 11, "overlap+mag"),
+    ("m128", CFG5, dict(schedule=3), 483, 3, "shared<8,24>"),
+    # 8-byte samples at M = 128: no 8-wave tile fits the LDS, every key takes the 4-wave tile of 64-frame runs
+    ("m128", CFG5F32, dict(schedule=3), 643, 3, "shared<4,64>"),
+    ("m128", CFG5F32, dict(schedule=3, tile_waves=8, frames_per_block=64), 643, 3, "shared<4,64>"),
+    ("m128", CFG5F32, dict(), 2603, 0, "sliding+c64"),
+    # channel-major defaults per band count: 2 waves x 4 chunks up to M = 32, 4 x 2 above
+    ("m32", M32, dict(channel_major=True), 163, 8, "tile_t<2,4>"),
+    ("m32", M32, dict(channel_major=True, schedule=8, tile_waves=4, frames_per_block=8), 83, 8, "tile_t<4,1>"),
+    ("m32", M32, dict(channel_major=True, schedule=2), 163, 2, "tile<8>+cm"),   # forced: tile_waves, not the default's 16
+    ("m32", M32, dict(channel_major=True, schedule=2, tile_waves=16), 323, 2, "tile<16>+cm"),
+    # M = 1024: the teams by default (by slabs for a channel-major handle), the twin kernel with and without a grid cap
+    ("m1024", M1024, dict(), 2603, 6, "teams+c64"),
+    ("m1024", M1024, dict(magnitude=True), 2603, 6, "teams+mag"),
+    ("m1024", M1024, dict(channel_major=True), 2603, 6, "teams+c64"),
+    ("m1024", DUO, dict(), 2603, 13, "twin+c64"),
+    ("m1024", DUO, dict(frames_per_block=64, grid=2), 163, 13, "twin+c64"),
+    ("m1024", DUO, dict(magnitude=True, frames_per_block=64), 163, 13, "twin+mag"),
+    # small banks: output type and layout compiled in
+    ("m8", M8F32, dict(), 2603, 0, "seg+c64"),
+    ("m8", M8F32, dict(magnitude=True), 2603, 0, "seg+mag"),
+    ("m8", M8F32, dict(channel_major=True), 2603, 0, "seg+cm+c64"),
+    ("m8", M8F32, dict(channel_major=True, magnitude=True), 2603, 0, "seg+cm+mag"),
+    # a schedule the plan lacks: its sliding runs, at the run length the policy gives that schedule
+    ("m256", CFG3I8, dict(schedule=4), 163, 0, "sliding+c64"),
+    ("m256", CFG3I8, dict(schedule=3), 63, 0, "sliding+c64"),
+    ("m256", CFG3I8, dict(schedule=6, frames_per_block=64), 163, 0, "sliding+c64"),
+]
+ENTRY_REQUEST_KEYS = ("schedule", "frames_per_block", "channel_major", "magnitude", "tile_waves", "nontemporal", "grid",
+                      "experiment", "out_aligned16")
+
+
+def plan_entry_for(row, frames, num_cus, opts):
+    assert set(opts) <= set(ENTRY_REQUEST_KEYS), opts
+    return L.plan_entry(row, frames, num_cus, **opts)

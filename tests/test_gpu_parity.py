@@ -545,6 +545,10 @@ def test_every_schedule_gives_identical_bits(oracle, opts):
             ch.set_option(k, v)
         got = ch(iq[:M * 1000 + 5])          # second call starts mid-frame: unaligned, history rows
         got2 = ch(iq[M * 1000 + 5:])
+        # the forced option took effect: the kernel that ran (pfb_last_entry), not only the schedule that was asked for
+        sched, tw, fpb = opts[L.PFB_OPT_SCHEDULE], opts.get(L.PFB_OPT_TILE_WAVES), opts.get(L.PFB_OPT_FRAMES_PER_BLOCK)
+        tag = {0: "sliding+c64", 2: f"tile<{tw}>", 3: f"shared<{tw},{fpb}>", 11: "overlap+c64"}[sched]
+        assert ch.last_launch.schedule == sched and (ch.last_entry.schedule, ch.last_entry.tag) == (sched, tag), ch.last_entry.fields()
     want = oracle_run(oracle, iq, h, M, P, M, 12)
     assert rel(ref, want) < REL_TOL
     assert np.array_equal(np.concatenate([got, got2]), ref)
@@ -629,6 +633,10 @@ def test_paired_schedule_gives_identical_bits(oracle, tw, fpb):
         ch.set_option(L.PFB_OPT_TILE_WAVES, tw)
         ch.set_option(L.PFB_OPT_FRAMES_PER_BLOCK, fpb)
         got = np.concatenate([ch(iq[:M * 2000 + 7]), ch(iq[M * 2000 + 7:])])
+        # each (tile_waves, run length) is a kernel of its own: the tuned 8 x 64 with the output type compiled in, the
+        # others from cfg2's sweep set
+        tag = "paired<8,64,4>+c64" if (tw, fpb) == (8, 64) else f"paired<{tw},{fpb},{5 if tw == 5 else 4}>"
+        assert ch.last_launch.schedule == 4 and (ch.last_entry.schedule, ch.last_entry.tag) == (4, tag), ch.last_entry.fields()
     assert np.array_equal(got, ref)
 
 
@@ -674,6 +682,9 @@ def test_pairs_over_sliding_runs_give_identical_bits(M, P, D, fmt, bw, pairs):
             cut = D * 1777 + 5
             got = np.concatenate([ch(iq[:cut]), ch(iq[cut:])])
             assert np.array_equal(got, ref), fpb
+            # 4 pairs on request (store kind tested per store); 6 or 8 with the output type compiled in
+            tag = "pairs_sliding<4,2>" if pairs == 4 else f"pairs_sliding<{pairs},{pairs // 2}>+c64"
+            assert ch.last_launch.schedule == 7 and (ch.last_entry.schedule, ch.last_entry.tag) == (7, tag), ch.last_entry.fields()
 
 
 @pytest.mark.parametrize("M,P,D,fmt,bw", [(128, 12, 64, "int16", 12), (256, 8, 256, "int8", 8), (256, 8, 256, "int16", 12),
@@ -698,6 +709,7 @@ def test_software_pipelined_runs_give_identical_bits(M, P, D, fmt, bw):
             cut = D * 1777 + 5
             got = np.concatenate([ch(iq[:cut]), ch(iq[cut:])])
             assert np.array_equal(got, ref), fpb
+            assert ch.last_launch.schedule == 11 and (ch.last_entry.schedule, ch.last_entry.tag) == (11, "overlap+c64"), fpb
     with Channelizer(M, taps=h, decimation=D, sample_format=fmt, bit_width=bw, magnitude=True) as ch:
         ch.set_option(L.PFB_OPT_SCHEDULE, 0)
         ch.set_option(L.PFB_OPT_FRAMES_PER_BLOCK, 512)
@@ -707,6 +719,7 @@ def test_software_pipelined_runs_give_identical_bits(M, P, D, fmt, bw):
             ch.set_option(L.PFB_OPT_SCHEDULE, 11)
             ch.set_option(L.PFB_OPT_FRAMES_PER_BLOCK, fpb)
             assert np.array_equal(ch(iq), ref), ("magnitude", fpb)
+            assert ch.last_launch.schedule == 11 and (ch.last_entry.schedule, ch.last_entry.tag) == (11, "overlap+mag"), fpb
 
 
 def test_iq_file_front_end(oracle, tmp_path):

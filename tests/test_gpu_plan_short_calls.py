@@ -61,7 +61,9 @@ class Row:
         self.d_iq = torch.from_numpy(self.iq).cuda()
         self.fresh_tails = [int(x) for x in rng.integers(0, D, size=self.K + 1)]
         ref = oracle_for(oracle, self.iq, self.h, d, self.fmt, self.bw, self.kw)
-        # the references: the whole stream in one call at the shortest legal run length, against the oracle
+        # the references: the whole stream in one call at the shortest legal run length, against the oracle.  (The run
+        # length asserted below is the one handed down; the schedule-4 rows run their compiled-in 8 x 64-frame workgroups
+        # whatever it says -- which kernel ran is pfb_last_entry, tests/test_gpu_kernel_entry.py)
         self.want = {}
         for mode, extra in (("complex", {}), ("magnitude", dict(magnitude=True))):
             with self.handle(**extra) as ch:

@@ -69,7 +69,7 @@ def check_split(torch, oracle, M, P, D, fmt, bw, lens, seed, opts=(), variant=0,
         forced.set_option(L.PFB_OPT_EXPERIMENT, SEPARATE_HISTORY)
         one = whole(d_iq)
         if want_kernel is not None:
-            assert want_kernel(whole), (whole.last_kernel, whole.last_launch.schedule)
+            assert want_kernel(whole), (whole.last_kernel, whole.last_launch.schedule, whole.last_entry.fields())
         got, blobs = play(torch, fused, d_iq, lens, cm)
         ref, ref_blobs = play(torch, forced, d_iq, lens, cm)
         assert torch.equal(got, ref)
@@ -97,7 +97,8 @@ def test_state_across_calls_cfg2(torch, oracle):
     lens.append(total - sum(lens))
     assert lens[-1] > hs
     check_split(torch, oracle, M, P, M, "int16", 12, lens, 41,
-                want_kernel=lambda ch: ch.last_kernel == "pfb_fast<M64,P12,D64,int16>" and ch.last_launch.schedule == 4)
+                want_kernel=lambda ch: ch.last_kernel == "pfb_fast<M64,P12,D64,int16>" and ch.last_launch.schedule == 4 and
+                ran(ch, 4, "paired<8,64,4>+c64"))
 
 
 def entry_lengths(D, hs, big, mid):
@@ -111,27 +112,40 @@ def twin_variant():
     return rows[0].variant
 
 
+def ran(ch, schedule, tag):
+    """the kernel the last launch resolved to (pfb_last_entry): what ran, where last_launch is what was asked for"""
+    e = ch.last_entry
+    return (e.schedule, e.tag) == (schedule, tag) and e.kernel != 0 and e.blocks > 0
+
+
 # (id, M, P, D, format, bit width, frames of the long call, handle switches, options, what the whole-stream call ran)
 ENTRIES = [
-    ("M56-pairs-sliding", 56, 12, 56, "int16", 12, 1300, {}, (), lambda ch: ch.last_launch.schedule == 7),
-    ("M128-D64-overlap", 128, 12, 64, "int16", 12, 1300, {}, (), lambda ch: ch.last_launch.schedule == 11),
-    ("M256-int8-sliding", 256, 8, 256, "int8", 8, 700, {}, (), lambda ch: ch.last_launch.schedule == 0),
-    ("M1024-P16-teams", 1024, 16, 1024, "int16", 16, 70, {}, (), lambda ch: ch.last_launch.schedule == 6),
+    ("M56-pairs-sliding", 56, 12, 56, "int16", 12, 1300, {}, (),
+     lambda ch: ch.last_launch.schedule == 7 and ran(ch, 7, "pairs_sliding<8,4>+c64")),
+    ("M128-D64-overlap", 128, 12, 64, "int16", 12, 1300, {}, (),
+     lambda ch: ch.last_launch.schedule == 11 and ran(ch, 11, "overlap+c64")),
+    ("M256-int8-sliding", 256, 8, 256, "int8", 8, 700, {}, (),
+     lambda ch: ch.last_launch.schedule == 0 and ran(ch, 0, "sliding+c64")),
+    ("M1024-P16-teams", 1024, 16, 1024, "int16", 16, 70, {}, (),
+     lambda ch: ch.last_launch.schedule == 6 and ran(ch, 6, "teams+c64")),
     ("M560", 560, 12, 560, "int16", 12, 70, {}, (), lambda ch: ch.last_kernel.startswith("pfb_fast<M560,")),
-    ("M8-cf32-seg", 8, 12, 8, "cf32", 0, 2100, {}, (), lambda ch: ch.last_kernel.startswith("pfb_fast<M8,")),
+    ("M8-cf32-seg", 8, 12, 8, "cf32", 0, 2100, {}, (), lambda ch: ch.last_kernel.startswith("pfb_fast<M8,") and ran(ch, 0, "seg+c64")),
     ("M64-channel-major-tile-t", 64, 12, 64, "int16", 12, 1300, dict(channel_major=True), (),
-     lambda ch: ch.last_kernel.startswith("pfb_fast<M64,") and ch.last_launch.by_slabs == 0),
+     lambda ch: ch.last_kernel.startswith("pfb_fast<M64,") and ch.last_launch.by_slabs == 0 and ran(ch, 8, "tile_t<4,2>")),
     ("M64-shared-halo", 64, 12, 64, "int16", 12, 1300, {}, ((L.PFB_OPT_SCHEDULE, 3),),
-     lambda ch: ch.last_launch.schedule == 3),
-    ("M64-tiles", 64, 12, 64, "int16", 12, 1300, {}, ((L.PFB_OPT_SCHEDULE, 2),), lambda ch: ch.last_launch.schedule == 2),
+     lambda ch: ch.last_launch.schedule == 3 and ran(ch, 3, "shared<8,24>")),
+    ("M64-tiles", 64, 12, 64, "int16", 12, 1300, {}, ((L.PFB_OPT_SCHEDULE, 2),),
+     lambda ch: ch.last_launch.schedule == 2 and ran(ch, 2, "tile<8>")),
     ("M64-channel-major-tiles", 64, 12, 64, "int16", 12, 1300, dict(channel_major=True), ((L.PFB_OPT_SCHEDULE, 2),),
-     lambda ch: ch.last_launch.by_slabs == 0),
+     lambda ch: ch.last_launch.by_slabs == 0 and ran(ch, 2, "tile<8>+cm")),
     ("M64-channel-major-sliding", 64, 12, 64, "int16", 12, 1300, dict(channel_major=True), ((L.PFB_OPT_SCHEDULE, 0),),
-     lambda ch: ch.last_launch.by_slabs == 0),
-    ("M36-generic", 36, 12, 36, "int16", 12, 900, {}, (), lambda ch: ch.last_kernel == "pfb_generic"),
-    ("M64-generic-forced", 64, 12, 64, "int8", 8, 900, {}, ((L.PFB_OPT_KERNEL, 1),), lambda ch: ch.last_kernel == "pfb_generic"),
+     lambda ch: ch.last_launch.by_slabs == 0 and ran(ch, 0, "sliding+cm")),
+    ("M36-generic", 36, 12, 36, "int16", 12, 900, {}, (),
+     lambda ch: ch.last_kernel == "pfb_generic" and ran(ch, -1, "generic")),
+    ("M64-generic-forced", 64, 12, 64, "int8", 8, 900, {}, ((L.PFB_OPT_KERNEL, 1),),
+     lambda ch: ch.last_kernel == "pfb_generic" and ran(ch, -1, "generic")),
     ("M1024-channel-major-slabs", 1024, 16, 1024, "int16", 16, 70, dict(channel_major=True), (),
-     lambda ch: ch.last_launch.by_slabs == 1),
+     lambda ch: ch.last_launch.by_slabs == 1 and ran(ch, 6, "teams+c64")),   # the last slab's frame-major launch
 ]
 
 
@@ -146,7 +160,7 @@ def test_twin_kernel_entry(torch, oracle):
     M, P = 1024, 16
     hs = M * P + M
     check_split(torch, oracle, M, P, M, "int16", 16, entry_lengths(M, hs, 70, 64), 77, variant=twin_variant(),
-                want_kernel=lambda ch: ch.last_launch.schedule == 13)
+                want_kernel=lambda ch: ch.last_launch.schedule == 13 and ran(ch, 13, "twin+c64"))
 
 
 @pytest.mark.parametrize("fmt,bw", [("int16", 12), ("int8", 8), ("cf32", 0)])
@@ -178,6 +192,10 @@ def test_pair_kernel_variants(torch, oracle, P, fmt, bw):
                         where = (P, fmt, shift, out_kw, sched, nt, ch.last_kernel, ch.last_launch.schedule)
                         if ch.last_kernel.startswith("pfb_fast"):
                             assert ch.last_launch.schedule == sched, where
+                            # the forced schedule took effect, with the output type and store kind compiled in
+                            roles = "+mag" if out_kw else "+c64+nt" if nt else "+c64"
+                            tag = ("paired<8,64,4>" if sched == 4 else "pairs_sliding<8,4>") + roles
+                            assert ran(ch, sched, tag), (where, ch.last_entry.fields())
                         assert torch.equal(got, ref), where
 
 

@@ -1,13 +1,15 @@
 """The fused-kernel table as the library lists it (pfb_fast_plan_count / pfb_fast_plan_info, host only): every row is
 what its name says, the variants of a shape are numbered the way PFB_OPT_VARIANT counts them, every shape is fuzzed,
-and the channel-major route of every plan is the one DESIGN.md names.  No GPU needed."""
+the channel-major route of every plan is the one DESIGN.md names, and every selection a handle can be put into
+resolves to one named kernel entry (pfb_plan_entry).  No GPU needed."""
 import json
 import os
 import re
 
 import pytest
 
-from plan_support import FMT, SCHEDULES, SHAPES, sweep_lengths, top_frames, walk_lengths
+from plan_support import (ENTRY_CASES, FMT, SCHEDULES, SHAPES, entry_geometry, plan_entry_for, sweep_lengths, tag_parts,
+                          top_frames, walk_lengths)
 from sdr_channelizer_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -234,3 +236,141 @@ def test_design_names_the_slab_plans():
     end = sec.find("\n* ", start + 1)
     para = sec[start:end if end > 0 else len(sec)]
     assert set(NAME_RE.findall(para)) and {m.group(0) for m in NAME_RE.finditer(para)} == SLAB_PLANS
+
+
+# ---- kernel entries: which kernel a launch resolves to (pfb_plan_entry: the policy, then the row's select) ------------
+
+NUM_CUS = 256
+FAMILY_SCHEDULE = {"sliding": 0, "seg": 0, "tile": 2, "shared": 3, "paired": 4, "teams": 6, "pairs_sliding": 7,
+                   "tile_t": 8, "overlap": 11, "twin": 13}
+
+
+# single-wave plans whose chunk buffer cannot hold the transposed chunk (kTileTOk, pfb_fast_tiles.hpp): their channel-major
+# default is schedule 2
+TILE_PLANS = {"pfb_fast<M50,P12,D50,int16>", "pfb_fast<M100,P12,D100,int16>", "pfb_fast<M120,P12,D120,int16>"}
+
+
+def check_entry(d, e, rep, opts, where):
+    """What every entry must satisfy, whatever was asked for."""
+    # the two cases without a kernel -- a channel-major call on a plan without a channel-major instantiation, schedule 13
+    # on a channel-major call -- are unreachable through the policy (it sends the first by slabs and hands a fused
+    # channel-major call schedule -1, 0, 2 or 8), so here every entry has one
+    assert e.kernel != 0 and e.reserved == 0, where
+    family, _, roles = tag_parts(e.tag)
+    assert FAMILY_SCHEDULE[family] == e.schedule, where
+    if rep.schedule >= 0:   # the schedule asked for, or the plan lacks it: its sliding runs (the small banks: their one kernel)
+        assert e.schedule == rep.schedule or (e.schedule == 0 and family in ("sliding", "seg")), where
+    else:                   # a fused channel-major launch, the kernel's own pick
+        assert e.schedule in (8, 2, 0) and opts.get("channel_major") and not rep.by_slabs, where
+    cm = bool(opts.get("channel_major")) and not rep.by_slabs
+    mag, nt = bool(opts.get("magnitude")), bool(opts.get("nontemporal"))
+    assert ("cm" in roles) <= cm and ("mag" in roles) <= mag and ("c64" in roles) <= (not mag), where
+    assert ("ms" in roles) <= (mag and opts.get("out_aligned16", True)) and ("nt" in roles) <= (nt and not mag), where
+    if cm and family != "tile_t":   # (tile_t is channel-major by construction)
+        assert "cm" in roles, where
+    frames = min(rep.frames, rep.slab_frames) if rep.by_slabs else rep.frames
+    per, threads = entry_geometry(e.tag, d, rep.frames_per_block)
+    blocks = -(-frames // per)
+    if family == "twin" and opts.get("grid", 0) > 0:
+        blocks = min(blocks, opts["grid"])
+    assert (e.threads, e.blocks) == (threads, blocks) and 64 <= e.threads <= 1024, where
+    assert e.dyn_lds == (((opts.get("experiment", 0) >> 8) & 0xff) * 1024 if family == "shared" else 0), where
+
+
+def test_every_selection_resolves_to_one_named_kernel(plans):
+    """Every row, over every schedule pfb_set_option accepts, tile_waves 1 ... 16, both layouts, complex / magnitude /
+    nontemporal output and run lengths from the default to 128 frames: the entry has a kernel, its schedule is the one
+    asked for or the documented fall-back, its grid covers the call's frames with the workgroups its tag names, and
+    within a row tag and kernel map one to one."""
+    points = 0
+    for i, d in enumerate(plans):
+        by_tag, by_kernel = {}, {}
+        for sched in SCHEDULES + (9,):
+            for tw in (1, 4, 5, 6, 8, 16):
+                for cm in (False, True):
+                    for mag, nt in ((False, False), (True, False), (False, True)):
+                        for fpb in (0, 2 * d.chunk_frames, 24, 32, 48, 64, 128):
+                            opts = dict(schedule=sched, tile_waves=tw, channel_major=cm, magnitude=mag, nontemporal=nt,
+                                        frames_per_block=fpb)
+                            e = plan_entry_for(i, 2603, NUM_CUS, opts)
+                            rep = L.plan_launch(i, 2603, NUM_CUS, schedule=sched, frames_per_block=fpb, channel_major=cm,
+                                                magnitude=mag)
+                            check_entry(d, e, rep, opts, (d.name, opts, e.fields()))
+                            assert by_tag.setdefault(e.tag, e.kernel) == e.kernel, (d.name, e.tag)
+                            assert by_kernel.setdefault(e.kernel, e.tag) == e.tag, (d.name, e.tag)
+                            points += 1
+        assert len(by_tag) == len(by_kernel) >= 2, d.name
+    print(f"{points} selections over {len(plans)} rows")
+
+
+def test_default_requests_run_the_rows_own_schedules(plans):
+    for i, d in enumerate(plans):
+        for frames in (1, 2603, 1 << 20):
+            assert plan_entry_for(i, frames, NUM_CUS, {}).schedule == d.default_schedule, d.name
+            want = d.magnitude_schedule if d.magnitude_schedule >= 0 else d.default_schedule
+            assert plan_entry_for(i, frames, NUM_CUS, dict(magnitude=True)).schedule == want, d.name
+            e = plan_entry_for(i, frames, NUM_CUS, dict(channel_major=True))
+            rep = L.plan_launch(i, frames, NUM_CUS, channel_major=True)
+            if rep.by_slabs:      # the frame-major kernel fills the slabs
+                assert e.schedule == d.default_schedule and not d.channel_major_ok, d.name
+            elif d.threads != 64:                    # multi-wave plans: channel-major sliding runs
+                assert (e.schedule, e.tag) == (0, "sliding+cm"), (d.name, e.tag)
+            elif tag_parts(e.tag)[0] == "seg":       # the small banks' one kernel
+                assert (e.schedule, e.tag) == (0, "seg+cm+c64") and d.M <= 40, (d.name, e.tag)
+            elif d.name.decode() in TILE_PLANS:      # one chunk per wave: 16 waves up to M = 64, 8 above
+                assert (e.schedule, e.tag) == (2, "tile<16>+cm" if d.M <= 64 else "tile<8>+cm"), (d.name, e.tag)
+            else:                                    # short runs transposed in LDS: 2 waves x 4 chunks up to M = 32, 4 x 2 above
+                assert (e.schedule, e.tag) == (8, "tile_t<2,4>" if d.M <= 32 else "tile_t<4,2>"), (d.name, e.tag)
+
+
+def test_pinned_entries(plans):
+    """plan_support.ENTRY_CASES: the literals of the dispatch as the commit before select_fast had it."""
+    index = {d.name.decode(): i for i, d in enumerate(plans)}
+    for fam, name, opts, frames, schedule, tag in ENTRY_CASES:
+        i = index[name]
+        e = plan_entry_for(i, frames, NUM_CUS, opts)
+        policy = {k: v for k, v in opts.items() if k in ("schedule", "frames_per_block", "channel_major", "magnitude")}
+        rep = L.plan_launch(i, frames, NUM_CUS, **policy)
+        where = (name, opts, e.fields())
+        assert (e.schedule, e.tag) == (schedule, tag), where
+        check_entry(plans[i], e, rep, opts, where)
+        per, _ = entry_geometry(tag, plans[i], rep.frames_per_block)
+        assert frames <= 2650 and frames % per != 0 and frames > 2 * per, where   # two whole workgroups and a partial one
+        assert e.blocks == (opts["grid"] if "grid" in opts else -(-frames // per)) and (e.blocks >= 3 or "grid" in opts), where
+        if "frames_per_block" in opts and tag_parts(tag)[0] not in ("sliding", "pairs_sliding") and "grid" not in opts:
+            assert e.blocks == 3, where
+    assert {c[0] for c in ENTRY_CASES} == {"cfg2", "m64", "m128", "m56", "m32", "m1024", "m8", "m256"}
+    # the run length the report hands down is not the run length of the kernel that runs: 16 asked for, 8 x 64 run
+    e = plan_entry_for(index["pfb_fast<M64,P12,D64,int16>"], 2603, NUM_CUS, dict(schedule=4, frames_per_block=16))
+    rep = L.plan_launch(index["pfb_fast<M64,P12,D64,int16>"], 2603, NUM_CUS, schedule=4, frames_per_block=16)
+    assert (rep.frames_per_block, rep.runs) == (16, -(-2603 // 16)) and (e.tag, e.blocks) == ("paired<8,64,4>+c64", -(-2603 // 512))
+    # schedule 3's occupancy throttle: PFB_OPT_EXPERIMENT bits 8-15 are KiB of dynamic LDS
+    e = plan_entry_for(index["pfb_fast<M64,P12,D64,int16>"], 483, NUM_CUS, dict(schedule=3, experiment=0x401))
+    assert (e.tag, e.dyn_lds) == ("shared<8,24>", 4096)
+
+
+def test_plan_entry_rejects_bad_arguments():
+    lib = L.load()
+    launch = L.PfbLaunchRequest(L.C.sizeof(L.PfbLaunchRequest), -1, 0, -1, 0, 0, NUM_CUS, 0)
+    rq = L.PfbEntryRequest(L.C.sizeof(L.PfbEntryRequest), 0, launch, 8, 0, 0, 0, 1, 0, 100)
+    e = L.PfbKernelEntry()
+    assert lib.pfb_plan_entry(None, L.C.byref(e)) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_plan_entry(L.C.byref(rq), None) == L.PFB_ERR_BAD_ARG
+    assert lib.pfb_last_entry(None, L.C.byref(e)) == L.PFB_ERR_BAD_ARG and lib.pfb_last_entry(None, None) == L.PFB_ERR_BAD_ARG
+    for size in (0, L.C.sizeof(L.PfbEntryRequest) - 8, L.C.sizeof(L.PfbEntryRequest) + 8):
+        rq.struct_size = size
+        assert lib.pfb_plan_entry(L.C.byref(rq), L.C.byref(e)) == L.PFB_ERR_BAD_ARG
+    rq.struct_size = L.C.sizeof(L.PfbEntryRequest)
+    rq.launch.struct_size = 0
+    assert lib.pfb_plan_entry(L.C.byref(rq), L.C.byref(e)) == L.PFB_ERR_BAD_ARG
+    rq.launch.struct_size = L.C.sizeof(L.PfbLaunchRequest)
+    for row in (-1, lib.pfb_fast_plan_count()):
+        rq.plan_index = row
+        assert lib.pfb_plan_entry(L.C.byref(rq), L.C.byref(e)) == L.PFB_ERR_BAD_ARG
+    rq.plan_index = 0
+    assert lib.pfb_plan_entry(L.C.byref(rq), L.C.byref(e)) == L.PFB_OK and e.tag == "paired<8,64,4>+c64" and e.blocks == 1
+    rq.frames = 0   # no frames: an entry with an empty grid (launching it is a no-op)
+    assert lib.pfb_plan_entry(L.C.byref(rq), L.C.byref(e)) == L.PFB_OK and e.blocks == 0 and e.kernel != 0
+    # the mirrors have the header's layout
+    assert L.C.sizeof(L.PfbKernelEntry) == 40 and L.PfbKernelEntry.blocks.offset == 16 and L.PfbKernelEntry._tag.offset == 32
+    assert L.C.sizeof(L.PfbEntryRequest) == 80 and L.PfbEntryRequest.launch.offset == 8 and L.PfbEntryRequest.frames.offset == 72

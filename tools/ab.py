@@ -80,11 +80,19 @@ for r in range(a.rounds + 1):
 cp = L.C.c_double()
 L.load().pfb_measure_stream_copy(0, 1 << 30, 10, L.C.byref(cp))
 print(f"# box yardstick: 1:2 stream copy {cp.value / 1e9:.1f} GB/s")
-print(f"{'case':34s} {'min ms':>8s} {'med ms':>8s} {'max ms':>8s} {'GB/s(med)':>10s} {'frac':>6s}  kernel")
+# which kernel each case resolved to (pfb_last_entry): an option set the plan lacks falls through to another kernel
+ran = {}
 for name, opts in cases:
-    t = np.array(times[name])
     for k, v in opts.items():
         ch.set_option(OPT[k], v)
     ch(iq, out=out, sync=True)
+    e = ch.last_entry
+    ran[name] = (ch.last_kernel, e.tag, e.kernel)
+if len(cases) > 1 and len({r[2] for r in ran.values()}) == 1:
+    sys.exit(f"every case resolved to one kernel, {ran[cases[0][0]][0]} {ran[cases[0][0]][1]}: there is nothing to compare "
+             "(unless the cases differ in options the kernel reads at run time: then compare them one per run)")
+print(f"{'case':34s} {'min ms':>8s} {'med ms':>8s} {'max ms':>8s} {'GB/s(med)':>10s} {'frac':>6s}  kernel")
+for name, opts in cases:
+    t = np.array(times[name])
     gbs = n * bytes_per_sample / (np.median(t) * 1e-3) / 1e9
-    print(f"{name:34s} {t.min():8.4f} {np.median(t):8.4f} {t.max():8.4f} {gbs:10.1f} {gbs / 8000:6.3f}  {ch.last_kernel}")
+    print(f"{name:34s} {t.min():8.4f} {np.median(t):8.4f} {t.max():8.4f} {gbs:10.1f} {gbs / 8000:6.3f}  {ran[name][0]} {ran[name][1]}")

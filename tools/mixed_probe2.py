@@ -46,10 +46,10 @@ for M in [int(a) for a in sys.argv[1:]] or [25, 48, 50, 320, 400]:
                         ch(big, out=out, sync=False)
                     t = np.median(ch.kernel_times_ms())
                     ch.set_option(L.PFB_OPT_PROFILE, 0)
-                    res.append((sched, fpb, nbig * 12 / (t * 1e-3) / 8e12))
+                    res.append((sched, fpb, nbig * 12 / (t * 1e-3) / 8e12, ch.last_entry.tag))   # the tag: what the option set ran
                 except PfbError:
                     pass
             best = max(res, key=lambda r: r[2])
-            print(f"M={M:4d} v{v} {ch.last_kernel:40s} err={err:.1e} " + " ".join(f"s{r[0]}/{r[1]}={r[2]:.3f}" for r in res) + f"  BEST s{best[0]}/{best[1]} {best[2]:.3f}", flush=True)
+            print(f"M={M:4d} v{v} {ch.last_kernel:40s} err={err:.1e} " + " ".join(f"s{r[0]}/{r[1]}[{r[3]}]={r[2]:.3f}" for r in res) + f"  BEST s{best[0]}/{best[1]} {best[2]:.3f}", flush=True)
     del big, out
     torch.cuda.empty_cache()

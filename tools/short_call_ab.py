@@ -27,6 +27,7 @@ for M, P, D, fmt, bw, tuned in SHAPES:
             iq = synth.pulsed_iq_torch(n, bw, torch.int8 if fmt == "int8" else torch.int16, device="cuda")
         res = {}
         outs = {}
+        ran = {}
         for name, fpb in (("auto", 0), ("tuned", tuned)):
             with Channelizer(M, taps=design_prototype(M, P), decimation=D, sample_format=fmt, bit_width=bw) as ch:
                 ch.set_option(L.PFB_OPT_FRAMES_PER_BLOCK, fpb)
@@ -42,6 +43,7 @@ for M, P, D, fmt, bw, tuned in SHAPES:
                 t = np.array(ch.kernel_times_ms())
                 res[name] = float(np.median(t)) * 1e3
                 outs[name] = out.clone()
+                ran[name] = f"{ch.last_kernel} {ch.last_entry.tag} x{ch.last_entry.blocks}"
         same = torch.equal(outs["auto"], outs["tuned"])
         print(f"M={M:5d} {fmt:5s} frames={frames:7d}: auto {res['auto']:8.1f} us   tuned runs ({tuned:4d}) {res['tuned']:8.1f} us   "
-              f"x{res['tuned'] / res['auto']:.2f}   bits {'same' if same else 'DIFFER'}")
+              f"x{res['tuned'] / res['auto']:.2f}   bits {'same' if same else 'DIFFER'}   auto: {ran['auto']}   tuned: {ran['tuned']}")

@@ -39,7 +39,7 @@ for kw in ({}, {"fftshift": True, "conjugate_input": True}, {"magnitude": True})
                     bad += 1
                     d = (y - ref).abs().max().item() / ref.abs().max().item()
                     d2 = (y2 - ref).abs().max().item() / ref.abs().max().item()
-                    print("MISMATCH", kw, v, ch.last_kernel, "fpb", fpb, "one-shot", same, d, "chunked", same2, d2)
-            print(kw, v, ch.last_kernel, "ok" if not bad else "")
+                    print("MISMATCH", kw, v, ch.last_kernel, ch.last_entry.tag, "fpb", fpb, "one-shot", same, d, "chunked", same2, d2)
+            print(kw, v, ch.last_kernel, ch.last_entry.tag, "ok" if not bad else "")
 print("bit-identity:", "ALL OK" if bad == 0 else f"{bad} FAILURES")
 sys.exit(1 if bad else 0)
