@@ -624,6 +624,88 @@ int pfb_synth_get_device(const pfb_synth_handle* h, int* device_id);
 int pfb_synth_write_iq_file(pfb_synth_handle* h, const char* path, int file_format, uint64_t start,
                             uint32_t num_samples, const pfb_iq_packet* header_fields);
 
+/* ---- magnitude / phase traces and plot envelopes ------------------------------------------------------
+ * Replaces the arithmetic of the reference's plotters (drawing stays with the caller):
+ *   matlab/plot_my_iq.m:105-108   iq = double(iq)/2^(bitWidth-1); iq = iq(1,:) + 1j*iq(2,:)
+ *   matlab/plot_my_iq.m:110-111   mag = abs(iq); phase = rad2deg(angle(iq))            (plotted at :122,129)
+ *   the same lines of generate_training_iq.m and generate_channelized_training_iq.m:68-91
+ * Per sample, with full = 2^(bit_width-1):
+ *   integer formats  u = I^2 + Q^2 as an exact unsigned integer (u <= 2^31, reached by (-32768,-32768): it does not
+ *                    fit an int32); power p = u * 2^-(2(bit_width-1))
+ *   PFB_FMT_CF32     p = (double)I*(double)I + (double)Q*(double)Q; the products are exact in double, so contraction
+ *                    cannot change the result.  Inputs must be finite: a non-finite sample may leave the fields of its
+ *                    bin unspecified, and never causes a fault or an access outside the buffers.
+ * Envelope: the stream is cut into bins of bin_samples = B consecutive samples, counted from the handle's origin (0
+ * after create / reset); pfb_trace_flush starts a new grid at the next sample.  Each bin gives one pfb_trace_bin.
+ *   integer formats  everything is integer work: min, max and first-index argmax of u, S = sum of u in uint64
+ *                    (B <= 2^31 keeps S < 2^63), converted at the very end: power_min/max = (double)u * scale,
+ *                    power_mean = ((double)S / (double)count) * scale, scale = 2^-(2(bit_width-1)).  Every field is
+ *                    therefore the same bits under any cutting of the stream into calls, on any pointer alignment, and
+ *                    whether the samples come from device memory, host memory or a file.
+ *   PFB_FMT_CF32     power_min, power_max and peak_* are exact selections with the same guarantees.  power_mean is a
+ *                    double sum taken without floating-point atomics in an order fixed by the call's lengths and its
+ *                    pointer's alignment to 16 bytes: the same call gives the same bits every time, another cutting
+ *                    may change the last bits.
+ * Magnitudes and the peak's phase are the host's in double -- sqrt(power_*), atan2(peak_q, peak_i): one value per bin.
+ * No atan2 and no sqrt run on the device for an envelope.
+ * Full-rate trace of a stretch (pfb_trace_samples): mag[n] = sqrt(p) and phase_deg[n] = atan2(Q, I)*180/pi, both
+ * float32 (mag within 1 ulp of the double value).  Stateless: it reads no carried bin and moves no origin.
+ * Every argument is validated before the device is touched.  PFB_ERR_BAD_ARG: null pointers, a wrong struct_size,
+ * bin_samples outside 1 .. 2^31, any flag bit (none is defined), an unknown mem, a device iq not aligned to one sample,
+ * out not aligned to 8 bytes (mag / phase_deg: to 4).  PFB_ERR_BAD_FORMAT: an unknown sample format, bit_width outside
+ * 1..8 (int8) or 1..16 (int16; ignored for cf32).  Then PFB_ERR_NO_DEVICE without a HIP device. */
+typedef struct pfb_trace_bin {
+  uint64_t peak_sample;   /* global index of the FIRST sample of the bin holding the largest power   */
+  double power_min, power_max, power_mean;   /* of p over the bin's samples                           */
+  float peak_i, peak_q;   /* that sample's components, normalised (int * 2^-(bit_width-1): exact)     */
+  uint32_t count;         /* samples in the bin: B, fewer only for the bin pfb_trace_flush returns    */
+  uint32_t reserved;      /* 0 */
+} pfb_trace_bin;
+
+typedef struct pfb_trace_config {
+  uint32_t struct_size;    /* = sizeof(pfb_trace_config)                 */
+  uint32_t sample_format;  /* pfb_sample_format                          */
+  uint32_t bit_width;      /* full scale 2^(bit_width-1)                 */
+  uint32_t bin_samples;    /* B, 1 .. 2^31                               */
+  uint32_t flags;          /* 0                                          */
+  int32_t device_id;       /* HIP device ordinal, -1 = current device    */
+} pfb_trace_config;
+
+typedef struct pfb_trace_handle pfb_trace_handle;
+
+/* Lifecycle as pfb_stft_*.  The handle holds the stream position and, on the device, the bin a call left open. */
+int pfb_trace_create(const pfb_trace_config* cfg, pfb_trace_handle** out);
+int pfb_trace_destroy(pfb_trace_handle* h);
+int pfb_trace_reset(pfb_trace_handle* h);   /* origin back to 0, no open bin */
+int pfb_trace_set_stream(pfb_trace_handle* h, void* hip_stream);
+int pfb_trace_sync(pfb_trace_handle* h);
+int pfb_trace_get_device(const pfb_trace_handle* h, int* device_id);
+/* The bins the next call of num_samples samples completes. */
+int pfb_trace_bins_for(const pfb_trace_handle* h, uint64_t num_samples, uint64_t* bins_out);
+/* The records of the bins these samples complete, to `out` (room for capacity_bins); *bins_out = their number.
+ * PFB_ERR_CAPACITY sets *bins_out to the number needed and changes no state.  mem: iq and out are both host pointers
+ * (PFB_MEM_HOST, staged as pfb_stft_process stages them) or both device pointers (PFB_MEM_DEVICE).  Synchronous. */
+int pfb_trace_envelope(pfb_trace_handle* h, const void* iq, uint64_t num_samples, pfb_trace_bin* out,
+                       uint64_t capacity_bins, uint64_t* bins_out, uint32_t mem);
+/* Same, device pointers, enqueued on the handle's stream without a host sync (bins longer than 4096 samples use a
+ * device scratch that grows with the longest call so far: a call that grows it waits for the device). */
+int pfb_trace_envelope_async(pfb_trace_handle* h, const void* d_iq, uint64_t num_samples, pfb_trace_bin* d_out,
+                             uint64_t capacity_bins, uint64_t* bins_out);
+/* The open bin, if any, to host memory (*have = 0 / 1; its count < B), and a new bin grid from the next sample. */
+int pfb_trace_flush(pfb_trace_handle* h, pfb_trace_bin* out_host, int32_t* have);
+/* mag and phase_deg of num_samples samples; either output may be NULL.  mem names all the pointers of the call. */
+int pfb_trace_samples(pfb_trace_handle* h, const void* iq, uint64_t num_samples, float* mag, float* phase_deg,
+                      uint32_t mem);
+/* Host only: B = max(1, ceil(num_samples / max_bins)), the bin that shows num_samples samples in at most max_bins
+ * columns.  PFB_ERR_BAD_ARG when max_bins == 0 or B > 2^31. */
+int pfb_trace_choose_bin(uint64_t num_samples, uint32_t max_bins, uint32_t* bin_samples);
+/* One whole .iq record: format, bit width and length from its header (checked as pfb_dwell_from_iq_file checks it),
+ * B from pfb_trace_choose_bin, the payload streamed as pfb_stft_process_iq_file streams it; the final partial bin is
+ * included.  `out` is host memory; *bins_out = ceil(numSamples / B), also on PFB_ERR_CAPACITY. */
+int pfb_trace_envelope_from_iq_file(const char* path, uint32_t max_bins, pfb_trace_bin* out, uint64_t capacity_bins,
+                                    uint64_t* bins_out, uint32_t* bin_samples_out, pfb_iq_info* info_out,
+                                    int32_t device_id);
+
 #ifdef __cplusplus
 }
 #endif

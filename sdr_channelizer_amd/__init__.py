@@ -9,8 +9,10 @@ from .channelizer import Channelizer, center_frequencies, design_prototype, pinn
 from .event import DwellStats, EventPredictor, analyze_dwell, dwell_from_iq_file, fit_event, next_event  # noqa: F401
 from .pulse_source import PulseTrain, pulse_train, synth_params  # noqa: F401
 from .stft import Stft, spectrogram_from_iq_file, stft, stft_axes  # noqa: F401
+from .trace import Envelope, Trace, envelope, envelope_from_iq_file  # noqa: F401
 
 __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empty", "PfbError", "LIB_PATH",
            "Stft", "stft", "stft_axes", "spectrogram_from_iq_file",
            "analyze_dwell", "dwell_from_iq_file", "fit_event", "next_event", "EventPredictor", "DwellStats",
-           "PulseTrain", "pulse_train", "synth_params"]
+           "PulseTrain", "pulse_train", "synth_params",
+           "Trace", "Envelope", "envelope", "envelope_from_iq_file"]

@@ -106,6 +106,17 @@ class PfbSynthParams(C.Structure):
                 ("barker_offset", C.c_uint32), ("dcw", C.c_uint64), ("noise_gain", C.c_int64)]
 
 
+class PfbTraceConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sample_format", C.c_uint32), ("bit_width", C.c_uint32),
+                ("bin_samples", C.c_uint32), ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbTraceBin(C.Structure):
+    _fields_ = [("peak_sample", C.c_uint64), ("power_min", C.c_double), ("power_max", C.c_double),
+                ("power_mean", C.c_double), ("peak_i", C.c_float), ("peak_q", C.c_float), ("count", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -190,6 +201,9 @@ EXPORTS = (
     "pfb_synth_describe", "pfb_synth_create", "pfb_synth_destroy", "pfb_synth_set_stream", "pfb_synth_generate",
     "pfb_synth_generate_async", "pfb_synth_sync", "pfb_synth_get_device", "pfb_synth_write_iq_file",
     "pfb_iq_serialize_header",
+    "pfb_trace_create", "pfb_trace_destroy", "pfb_trace_reset", "pfb_trace_set_stream", "pfb_trace_sync",
+    "pfb_trace_get_device", "pfb_trace_bins_for", "pfb_trace_envelope", "pfb_trace_envelope_async", "pfb_trace_flush",
+    "pfb_trace_samples", "pfb_trace_choose_bin", "pfb_trace_envelope_from_iq_file",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -316,6 +330,20 @@ def load() -> C.CDLL:
     lib.pfb_synth_get_device.argtypes = [vp, C.POINTER(C.c_int)]
     lib.pfb_synth_write_iq_file.argtypes = [vp, C.c_char_p, C.c_int, u64, u32, C.POINTER(PfbIqPacket)]
     lib.pfb_iq_serialize_header.argtypes = [C.POINTER(PfbIqPacket), C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.pfb_trace_create.argtypes = [C.POINTER(PfbTraceConfig), C.POINTER(vp)]
+    lib.pfb_trace_destroy.argtypes = [vp]
+    lib.pfb_trace_reset.argtypes = [vp]
+    lib.pfb_trace_set_stream.argtypes = [vp, vp]
+    lib.pfb_trace_sync.argtypes = [vp]
+    lib.pfb_trace_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_trace_bins_for.argtypes = [vp, u64, C.POINTER(u64)]
+    lib.pfb_trace_envelope.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_trace_envelope_async.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    lib.pfb_trace_flush.argtypes = [vp, C.POINTER(PfbTraceBin), C.POINTER(i32)]
+    lib.pfb_trace_samples.argtypes = [vp, vp, u64, vp, vp, u32]
+    lib.pfb_trace_choose_bin.argtypes = [u64, u32, C.POINTER(u32)]
+    lib.pfb_trace_envelope_from_iq_file.argtypes = [C.c_char_p, u32, vp, u64, C.POINTER(u64), C.POINTER(u32),
+                                                    C.POINTER(PfbIqInfo), i32]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """isa_identical.py OLD_TREE NEW_TREE -- is the device code of two checkouts the same?
 
-Compiles the six kernel translation units of both trees to gfx950 assembly with the flags of
+Compiles the kernel translation units (FILES) of both trees to gfx950 assembly with the flags of
 sdr_channelizer_amd/build.py and compares them per kernel symbol: the instruction text with its
 .amdhsa_kernel block, and the kernel's entry in the code object's metadata.  Comments, .ident, .file, the
 per-compilation __hip_cuid_<hash> symbol and the file's .AMDGPU.* trailer sections (which follow whichever kernel was
 emitted last) are dropped; local labels lose the function's ordinal, so that the order
 in which kernels are emitted does not matter.  Exit status 0 = every kernel of every file exists in both trees and
-is identical.  A refactor that only moves device code between structs and headers must pass with no difference.
+is identical.  A refactor that only moves device code between structs and headers must pass with no difference.  A unit
+that one of the trees does not have yet counts as a difference and is reported by name.
 """
 import os
 import re
@@ -18,7 +19,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 FILES = ["pfb_kernels.hip", "pfb_kernels_mid.hip", "pfb_kernels_big.hip", "pfb_kernels_mixed.hip", "pfb_stft.hip",
-         "pfb_pdw.hip"]
+         "pfb_pdw.hip", "pfb_trace.hip"]
 CSRC = os.path.join("sdr_channelizer_amd", "csrc")
 FIELDS = [".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
           ".group_segment_fixed_size"]
@@ -81,11 +82,15 @@ def main():
         sys.exit(__doc__)
     trees = [os.path.abspath(t) for t in sys.argv[1:]]
     tmp = tempfile.mkdtemp(prefix="isa_identical_")
-    jobs = [(t, f, os.path.join(tmp, f"{i}_{f}.s")) for f in FILES for i, t in enumerate(trees)]
+    missing = [f for f in FILES if not all(os.path.exists(os.path.join(t, CSRC, f)) for t in trees)]
+    both = [f for f in FILES if f not in missing]
+    jobs = [(t, f, os.path.join(tmp, f"{i}_{f}.s")) for f in both for i, t in enumerate(trees)]
     with ThreadPoolExecutor(max_workers=min(5, os.cpu_count() or 1)) as pool:
         list(pool.map(assemble, jobs))
-    bad = 0
-    for f in FILES:
+    bad = len(missing)
+    for f in missing:
+        print(f"{f}: not in both trees")
+    for f in both:
         old, new = (kernels(os.path.join(tmp, f"{i}_{f}.s")) for i in (0, 1))
         print(f"{f}: {len(old)} kernels in OLD_TREE, {len(new)} in NEW_TREE")
         for sym in sorted(set(old) | set(new)):
