@@ -706,6 +706,97 @@ int pfb_trace_envelope_from_iq_file(const char* path, uint32_t max_bins, pfb_tra
                                     uint64_t* bins_out, uint32_t* bin_samples_out, pfb_iq_info* info_out,
                                     int32_t device_id);
 
+/* ---- matched filter (pulse compression) ---------------------------------------------------------------
+ * Finds a coded pulse by its replica instead of its envelope.  The pulses are the reference's own:
+ *   matlab/generate_pulsed_iq.m:17-19,43-59            LFM sweeps and Barker-13 chips (pfb_synth_* makes them)
+ *   tx_rx_pulses_usrp.cpp:24,141-142,212-242,284-291   a 13-chip burst transmitted and the dwell received, written as
+ *                                                      two .iq records, each with its own sampleStartTime
+ *   matlab/generate_training_iq.m:16-22                pulse widths up to 1000 us: 56 000 samples at 56 MS/s
+ * Arithmetic, with r[0..K-1] the caller's complex64 replica, 1 <= K <= 65536:
+ *   x[n] = (I[n] + jQ[n]) / 2^(bit_width-1)            (cf32: as given)
+ *   y[m] = g * sum_{n=0}^{K-1} conj(r[n]) * x[m+n]        m = 0, 1, ...  (stream-absolute)
+ * g = 1; with PFB_MF_NORMALIZE g = 1/sum|r|^2 (float64, at create): a copy of r with amplitude A gives y = A at the
+ * match.  Only complete windows are produced: N stream samples so far give max(0, N-K+1) outputs, and output m is the
+ * index of the sample at which a pulse equal to the replica starts.  PFB_MF_COMPLEX stores y (complex64, 8 bytes per
+ * output), PFB_MF_POWER |y|^2 (float32, 4 bytes).
+ * Method: overlap-save fast convolution in fp32 with FFTs of fft_length points.  PFB_MF_ROUTE_FUSED (K <= fft_length/2)
+ * is one kernel, fft_length - K + 1 outputs per block; PFB_MF_ROUTE_PARTITIONED (any K) cuts the replica into
+ * ceil(K / (fft_length/2)) partitions, fft_length/2 outputs per block, through a device workspace the handle owns
+ * (grow-only, at most 64 MiB, freed at destroy).  PFB_MF_ROUTE_AUTO: fused when K <= fft_length/2 (K <= 2048 for
+ * fft_length = 0), partitioned above.  fft_length = 0 is the library's choice, the faster length per K range as
+ * measured on the MI355X: fused, 1024 for K <= 64, 2048 for K <= 1024, 4096 above; partitioned,
+ * 2048 for K <= 1024, 4096 above.
+ * The handle is stateful like pfb_stft_*: it carries the last min(N, K-1) samples, so a stream may be cut into calls of
+ * any length, length 0 included.  The same sequence of calls gives the same bits every time.  Different cuttings of one
+ * stream agree to |y - y'| <= 2e-5 * g * ||r||_2 * max_m ||x[m..m+K-1]||_2 and are NOT bit-identical: the blocks start
+ * where a call (or a staging step of a host-pointer call) starts.  A cf32 sample that is not finite may make every
+ * output of the FFT block it falls in non-finite, not only the K outputs whose window holds it; it never causes a
+ * fault or an access outside the buffers.
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, K = 0, a replica value that is not finite, an all-zero replica with PFB_MF_NORMALIZE, a replica whose
+ * scaled spectrum does not fit float32, an unknown output, flag or route, fft_length outside {0, 1024, 2048, 4096}, an
+ * unknown mem, a device pointer not aligned to one sample (iq) or one output element (out).  PFB_ERR_BAD_FORMAT: an
+ * unknown sample format, bit_width outside 1..8 (int8) or 1..16 (int16; ignored for cf32).  PFB_ERR_UNSUPPORTED:
+ * K > 65536, or PFB_MF_ROUTE_FUSED with K > fft_length/2 (K > 2048 when fft_length = 0).  Then PFB_ERR_NO_DEVICE
+ * without a HIP device. */
+enum { PFB_MF_COMPLEX = 0, PFB_MF_POWER = 1 };
+enum { PFB_MF_NORMALIZE = 1u << 0 };
+enum { PFB_MF_ROUTE_AUTO = 0, PFB_MF_ROUTE_FUSED = 1, PFB_MF_ROUTE_PARTITIONED = 2 };
+
+typedef struct pfb_mf_config {
+  uint32_t struct_size;      /* = sizeof(pfb_mf_config)                                          */
+  uint32_t replica_length;   /* K                                                                */
+  const float* replica;      /* K interleaved re,im, finite, copied at create                    */
+  uint32_t sample_format;    /* pfb_sample_format                                                */
+  uint32_t bit_width;        /* full scale 2^(bit_width-1); ignored for CF32                     */
+  uint32_t output;           /* PFB_MF_COMPLEX / PFB_MF_POWER                                    */
+  uint32_t flags;            /* PFB_MF_NORMALIZE                                                 */
+  uint32_t fft_length;       /* 0 = the library's choice, else 1024 / 2048 / 4096                */
+  uint32_t route;            /* PFB_MF_ROUTE_*                                                   */
+  int32_t device_id;         /* HIP device ordinal, -1 = current device                          */
+} pfb_mf_config;
+
+typedef struct pfb_mf_plan { /* what pfb_mf_describe reports; host only                          */
+  uint32_t fft_length;       /* 1024 / 2048 / 4096                                               */
+  uint32_t route;            /* PFB_MF_ROUTE_FUSED or PFB_MF_ROUTE_PARTITIONED                   */
+  uint32_t partitions;       /* 1 (fused), ceil(K / (fft_length/2)) (partitioned)                */
+  uint32_t block_outputs;    /* outputs per workgroup: fft_length - K + 1, or fft_length/2       */
+  uint64_t workspace_bytes;  /* the most the handle's workspace grows to: 0 (fused), <= 64 MiB   */
+} pfb_mf_plan;
+
+typedef struct pfb_mf_handle pfb_mf_handle;
+
+/* Host only: validate cfg (everything pfb_mf_create checks before the device) and report the plan. */
+int pfb_mf_describe(const pfb_mf_config* cfg, pfb_mf_plan* plan_out);
+/* Lifecycle as pfb_stft_*.  The handle owns the replica's spectra, the carried samples and the workspace. */
+int pfb_mf_create(const pfb_mf_config* cfg, pfb_mf_handle** out);
+int pfb_mf_destroy(pfb_mf_handle* h);
+int pfb_mf_reset(pfb_mf_handle* h);   /* stream position back to 0, nothing carried */
+int pfb_mf_set_stream(pfb_mf_handle* h, void* hip_stream);
+int pfb_mf_sync(pfb_mf_handle* h);
+int pfb_mf_get_device(const pfb_mf_handle* h, int* device_id);
+/* The outputs the next call of num_samples samples completes. */
+int pfb_mf_outputs_for(const pfb_mf_handle* h, uint64_t num_samples, uint64_t* outputs_out);
+/* The stream index m of the next output to be produced: max(0, N-K+1) after N samples. */
+int pfb_mf_next_index(const pfb_mf_handle* h, uint64_t* index_out);
+/* Filter num_samples samples; the outputs they complete go to `out` (room for capacity_outputs), their number to
+ * *outputs_out.  PFB_ERR_CAPACITY sets *outputs_out to the number needed and changes no state.  mem: iq and out are
+ * both host pointers (PFB_MEM_HOST, staged as pfb_stft_process stages them, an output playing the role of a frame) or
+ * both device pointers (PFB_MEM_DEVICE).  Synchronous. */
+int pfb_mf_process(pfb_mf_handle* h, const void* iq, uint64_t num_samples, void* out, uint64_t capacity_outputs,
+                   uint64_t* outputs_out, uint32_t mem);
+/* Same, device pointers, enqueued on the handle's stream without a host sync (a partitioned call that grows the
+ * workspace waits for the device). */
+int pfb_mf_process_async(pfb_mf_handle* h, const void* d_iq, uint64_t num_samples, void* d_out,
+                         uint64_t capacity_outputs, uint64_t* outputs_out);
+/* One .iq record from disk (format and bit width checked against the handle), streamed as pfb_stft_process_iq_file
+ * streams it; `out` is host memory.  The handle's state carries on from earlier calls: reset first for a record on
+ * its own. */
+int pfb_mf_process_iq_file(pfb_mf_handle* h, const char* path, void* out, uint64_t capacity_outputs,
+                           uint64_t* outputs_out, pfb_iq_info* info_out);
+/* Name of the kernel the last process call launched ("" before the first). */
+const char* pfb_mf_last_kernel(const pfb_mf_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

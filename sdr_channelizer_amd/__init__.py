@@ -7,6 +7,8 @@ include/pfb_channelizer.h; this package is the thin host side.
 from ._lib import LIB_PATH, PfbError  # noqa: F401
 from .channelizer import Channelizer, center_frequencies, design_prototype, pinned_empty  # noqa: F401
 from .event import DwellStats, EventPredictor, analyze_dwell, dwell_from_iq_file, fit_event, next_event  # noqa: F401
+from .matched_filter import (MatchedFilter, compress, compress_iq_file, pulse_delay_from_iq_files,  # noqa: F401
+                             replica_from_pulse_train)
 from .pulse_source import PulseTrain, pulse_train, synth_params  # noqa: F401
 from .stft import Stft, spectrogram_from_iq_file, stft, stft_axes  # noqa: F401
 from .trace import Envelope, Trace, envelope, envelope_from_iq_file  # noqa: F401
@@ -15,4 +17,5 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "Stft", "stft", "stft_axes", "spectrogram_from_iq_file",
            "analyze_dwell", "dwell_from_iq_file", "fit_event", "next_event", "EventPredictor", "DwellStats",
            "PulseTrain", "pulse_train", "synth_params",
-           "Trace", "Envelope", "envelope", "envelope_from_iq_file"]
+           "Trace", "Envelope", "envelope", "envelope_from_iq_file",
+           "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files"]

@@ -39,6 +39,9 @@ PFB_STFT_KERNEL_AUTO, PFB_STFT_KERNEL_GENERIC, PFB_STFT_KERNEL_FUSED = 0, 1, 2
 PFB_DWELL_STAT_MEAN, PFB_DWELL_STAT_MEDIAN = 0, 1
 PFB_DWELL_SKIP_FREQ = 1
 PFB_SYNTH_BARKER13, PFB_SYNTH_BARKER_DEGREES, PFB_SYNTH_PHASE_FROM_ZERO, PFB_SYNTH_ROUND_MATLAB = 1, 2, 4, 8
+PFB_MF_COMPLEX, PFB_MF_POWER = 0, 1
+PFB_MF_NORMALIZE = 1
+PFB_MF_ROUTE_AUTO, PFB_MF_ROUTE_FUSED, PFB_MF_ROUTE_PARTITIONED = 0, 1, 2
 
 
 class PfbConfig(C.Structure):
@@ -115,6 +118,17 @@ class PfbTraceBin(C.Structure):
     _fields_ = [("peak_sample", C.c_uint64), ("power_min", C.c_double), ("power_max", C.c_double),
                 ("power_mean", C.c_double), ("peak_i", C.c_float), ("peak_q", C.c_float), ("count", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class PfbMfConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("replica_length", C.c_uint32), ("replica", C.POINTER(C.c_float)),
+                ("sample_format", C.c_uint32), ("bit_width", C.c_uint32), ("output", C.c_uint32), ("flags", C.c_uint32),
+                ("fft_length", C.c_uint32), ("route", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbMfPlan(C.Structure):
+    _fields_ = [("fft_length", C.c_uint32), ("route", C.c_uint32), ("partitions", C.c_uint32),
+                ("block_outputs", C.c_uint32), ("workspace_bytes", C.c_uint64)]
 
 
 class PfbFastPlanDesc(C.Structure):
@@ -204,6 +218,9 @@ EXPORTS = (
     "pfb_trace_create", "pfb_trace_destroy", "pfb_trace_reset", "pfb_trace_set_stream", "pfb_trace_sync",
     "pfb_trace_get_device", "pfb_trace_bins_for", "pfb_trace_envelope", "pfb_trace_envelope_async", "pfb_trace_flush",
     "pfb_trace_samples", "pfb_trace_choose_bin", "pfb_trace_envelope_from_iq_file",
+    "pfb_mf_describe", "pfb_mf_create", "pfb_mf_destroy", "pfb_mf_reset", "pfb_mf_set_stream", "pfb_mf_sync",
+    "pfb_mf_get_device", "pfb_mf_outputs_for", "pfb_mf_next_index", "pfb_mf_process", "pfb_mf_process_async",
+    "pfb_mf_process_iq_file", "pfb_mf_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -344,6 +361,20 @@ def load() -> C.CDLL:
     lib.pfb_trace_choose_bin.argtypes = [u64, u32, C.POINTER(u32)]
     lib.pfb_trace_envelope_from_iq_file.argtypes = [C.c_char_p, u32, vp, u64, C.POINTER(u64), C.POINTER(u32),
                                                     C.POINTER(PfbIqInfo), i32]
+    lib.pfb_mf_describe.argtypes = [C.POINTER(PfbMfConfig), C.POINTER(PfbMfPlan)]
+    lib.pfb_mf_create.argtypes = [C.POINTER(PfbMfConfig), C.POINTER(vp)]
+    lib.pfb_mf_destroy.argtypes = [vp]
+    lib.pfb_mf_reset.argtypes = [vp]
+    lib.pfb_mf_set_stream.argtypes = [vp, vp]
+    lib.pfb_mf_sync.argtypes = [vp]
+    lib.pfb_mf_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_mf_outputs_for.argtypes = [vp, u64, C.POINTER(u64)]
+    lib.pfb_mf_next_index.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_mf_process.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_mf_process_async.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    lib.pfb_mf_process_iq_file.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(u64), C.POINTER(PfbIqInfo)]
+    lib.pfb_mf_last_kernel.argtypes = [vp]
+    lib.pfb_mf_last_kernel.restype = C.c_char_p
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
