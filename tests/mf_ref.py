@@ -62,6 +62,45 @@ def tolerance(x, r, normalize=False):
     return TOL * gain(r, normalize) * bound(x, r)
 
 
+def span_tolerance(x, r, lo, hi, normalize=False):
+    """The local allowance of samples [lo, hi): e of that slice alone.  The device computes a block from the block's own
+    input span, so the outputs of blocks whose spans lie in [lo, hi) owe nothing to louder samples elsewhere."""
+    return tolerance(np.asarray(x)[lo:hi], r, normalize)
+
+
+def block_outputs(route, nfft, K):
+    """outputs per block: the plan's block_outputs"""
+    return nfft - K + 1 if route == "fused" else nfft // 2
+
+
+def block_span(route, nfft, K, b):
+    """The call-local samples [lo, hi) block b of a call is computed from (local sample 0 is the first carried one;
+    what lies past the call's end reads as zero).  Fused: the block's nfft samples.  Partitioned: output block b combines
+    the spectra of P half-overlapped nfft-point blocks, P + 1 half-blocks of B = nfft/2 samples."""
+    if route == "fused":
+        lo = b * (nfft - K + 1)
+        return lo, lo + nfft
+    B = nfft // 2
+    P = -(-K // B)
+    return b * B, (b + P + 1) * B
+
+
+def outputs_seeing(route, nfft, K, s, outputs):
+    """The call-local outputs [lo, hi) of the blocks whose input spans hold call-local sample s, of a call that completes
+    `outputs` outputs: those a sample that is not finite may spoil.  Empty: lo == hi."""
+    V = block_outputs(route, nfft, K)
+    blocks = -(-outputs // V)
+    if route == "fused":
+        first, last = -(-(s - nfft + 1) // V), s // V
+    else:
+        B = nfft // 2
+        first, last = s // B - -(-K // B), s // B
+    first, last = max(first, 0), min(last, blocks - 1)
+    if first > last:
+        return 0, 0
+    return first * V, min((last + 1) * V, outputs)
+
+
 def worst_ratio(y, ref, e, output):
     """The largest error over its allowance (<= 1 passes), and over the 1e-5 allowance's own unit: returns
     (ratio, error / (g Bnd)).  Power output: |p - |ref|^2| <= e (2|ref| + e), the same bound carried through the square."""

@@ -10,59 +10,20 @@ pytestmark = pytest.mark.gpu
 
 import mf_ref as R  # noqa: E402
 from gpu_support import cuda_torch  # noqa: E402
+from mf_support import WORST, check, on_device, reset_worst, run_guarded  # noqa: E402
 from sdr_channelizer_amd import (MatchedFilter, PulseTrain, compress, compress_iq_file, iqfile, pinned_empty,  # noqa: E402
                                  pulse_delay_from_iq_files, replica_from_pulse_train)
 from sdr_channelizer_amd import _lib as L  # noqa: E402
 from sdr_channelizer_amd.pdw import extract_pdws_raw  # noqa: E402
 
-WORST = {"ratio": 0.0, "of_bound": 0.0, "where": ""}
-
 
 @pytest.fixture(scope="module")
 def torch():
     t = cuda_torch()
+    reset_worst()
     yield t
     # the largest error the module saw, in units of g * Bnd (the allowance is 1e-5): DESIGN.md section 15 quotes it
     print(f"\nmf worst error / (g Bnd) = {WORST['of_bound']:.3e} ({WORST['ratio']:.3f} of the allowance) at {WORST['where']}")
-
-
-def check(y, ref, x, r, normalize, output, where):
-    y = np.asarray(y)
-    assert y.shape == ref.shape, (where, y.shape, ref.shape)
-    assert y.dtype == (np.complex64 if output == "complex" else np.float32)
-    if y.size == 0:
-        return
-    ratio, of_bound = R.worst_ratio(y, ref, R.tolerance(x, r, normalize), output)
-    if ratio > WORST["ratio"]:
-        WORST.update(ratio=ratio, of_bound=of_bound, where=str(where))
-    assert ratio <= 1.0, (where, ratio, of_bound)
-
-
-def on_device(torch, raw, misalign):
-    """the raw samples in device memory, 16-byte aligned or one sample past a 16-byte boundary"""
-    if not misalign:
-        return torch.from_numpy(raw).cuda()
-    buf = torch.empty(raw.size + 2, dtype=torch.from_numpy(raw[:0]).dtype, device="cuda")
-    assert buf.data_ptr() % 16 == 0
-    view = buf[2:]
-    view.copy_(torch.from_numpy(raw))
-    return view
-
-
-GUARD = 5   # output elements on either side: 40 or 20 bytes, so the guarded output starts off a 16-byte boundary
-
-
-def run_guarded(torch, mf, d_in, outputs, output, misalign):
-    """process into a caller's buffer with guard elements around it that must survive"""
-    dt = torch.complex64 if output == "complex" else torch.float32
-    lead = GUARD if misalign else GUARD + 3   # 8 elements: a multiple of 16 bytes for both kinds
-    buf = torch.full((lead + outputs + GUARD,), -77.0, dtype=dt, device="cuda")
-    out = buf[lead: lead + outputs]
-    got = mf.process(d_in, out=out)
-    assert got.numel() == outputs and (outputs == 0 or got.data_ptr() == out.data_ptr())
-    host = buf.cpu().numpy()
-    assert np.all(host[:lead] == -77.0) and np.all(host[lead + outputs:] == -77.0)
-    return host[lead: lead + outputs]
 
 
 @pytest.mark.parametrize("nfft", [1024, 2048, 4096])

@@ -1,5 +1,7 @@
 """The matched filter's contract without a GPU: the numpy restatement (mf_ref) against the definition, every argument
-check that comes before the device and their order, the plan pfb_mf_describe reports, the exports and the ABI guard."""
+check that comes before the device and their order, the plan pfb_mf_describe reports, the exports and the ABI guard,
+and the helpers the GPU tests derive local allowances and block sets from (mf_ref.span_tolerance, block_span,
+outputs_seeing) against the plan and a plain enumeration."""
 import ctypes as C
 import os
 import re
@@ -45,6 +47,46 @@ def test_bound_is_the_windowed_norm():
         max(np.sqrt(np.sum(np.abs(x[m:m + 17]) ** 2)) for m in range(300 - 17 + 1))
     assert abs(R.bound(x, r) - direct) <= 1e-12 * direct
     assert R.bound(x[:16], r) == 0.0 and R.tolerance(x, r) == 1e-5 * R.bound(x, r)
+
+
+def test_span_tolerance_is_the_slice_alone():
+    x = R.unpack(R.random_raw("cf32", 1, 400, 5), "cf32", 1)
+    x[150:250] *= 1e3   # a loud stretch
+    r = R.random_replica(17, 6)
+    for normalize in (False, True):
+        quiet = R.span_tolerance(x, r, 0, 150, normalize)
+        assert quiet == R.tolerance(x[:150], r, normalize) == R.TOL * R.gain(r, normalize) * R.bound(x[:150], r)
+        assert R.span_tolerance(x, r, 0, 151, normalize) > 10 * quiet   # one loud sample in the span
+        assert R.span_tolerance(x, r, 0, 400, normalize) == R.tolerance(x, r, normalize) > 100 * quiet
+    assert R.span_tolerance(x, r, 10, 26) == 0.0 and R.span_tolerance(x, r, 10, 27) > 0.0   # shorter than a window
+
+
+@pytest.mark.parametrize("route,nfft,K", [("fused", 1024, 1), ("fused", 1024, 300), ("fused", 1024, 512),
+                                          ("fused", 4096, 2048), ("partitioned", 1024, 1), ("partitioned", 1024, 512),
+                                          ("partitioned", 1024, 513), ("partitioned", 1024, 700),
+                                          ("partitioned", 4096, 5600)])
+def test_block_spans_and_the_outputs_that_see_a_sample(route, nfft, K):
+    plan = mf.describe(R.random_replica(K, 1), fft_length=nfft, route=route)
+    V = R.block_outputs(route, nfft, K)
+    assert V == plan.block_outputs
+    for outputs in (1, V - 1, V, V + 1, 5 * V + 3):
+        total = outputs + K - 1
+        blocks = -(-outputs // V)
+        spans = [R.block_span(route, nfft, K, b) for b in range(blocks)]
+        for b, (lo, hi) in enumerate(spans):
+            # a block's span holds the windows of all its outputs, and starts at its first output
+            assert lo == b * V and hi >= lo + V + K - 1
+            assert hi - lo == (nfft if route == "fused" else (plan.partitions + 1) * (nfft // 2))
+        for s in sorted({0, 1, K - 1, V - 1, V, nfft - 1, nfft, total // 2, total - 1} & set(range(total))):
+            seeing = [b for b, (lo, hi) in enumerate(spans) if lo <= s < hi]
+            lo, hi = R.outputs_seeing(route, nfft, K, s, outputs)
+            if not seeing:
+                assert lo == hi
+                continue
+            assert seeing == list(range(seeing[0], seeing[-1] + 1))
+            assert (lo, hi) == (seeing[0] * V, min((seeing[-1] + 1) * V, outputs))
+            # every output whose window holds s is among them
+            assert lo <= max(0, s - K + 1) and min(s, outputs - 1) < hi
 
 
 def config(K=13, replica=None, fmt=L.PFB_FMT_INT16_IQ, bw=12, output=0, flags=0, nfft=0, route=0, size=None, device=-1,
