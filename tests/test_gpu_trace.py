@@ -12,6 +12,7 @@ import trace_ref as R
 from gpu_support import cuda_torch
 from sdr_channelizer_amd import _lib as L
 from sdr_channelizer_amd import PulseTrain, Trace, envelope, envelope_from_iq_file, iqfile, synth, trace
+from trace_support import same, stream
 
 pytestmark = pytest.mark.gpu
 T = trace.TILE
@@ -22,25 +23,6 @@ INTEGER = [f for f in R.FORMATS if f[0] != "cf32"]
 @pytest.fixture(scope="module")
 def torch():
     return cuda_torch()
-
-
-def same(got, want, fmt):
-    got, want = trace.as_records(got), np.asarray(want)
-    if got.shape != want.shape:
-        return False
-    return R.mean_close(got, want) if fmt == "cf32" else np.array_equal(got.view(np.uint8), want.view(np.uint8))
-
-
-_streams = {}
-
-
-def stream(torch, fmt, bw, n=8 * 100003 + 4):
-    """One random stream per format, on the host and on the device; made once, never written."""
-    if (fmt, bw) not in _streams:
-        iq = R.random_iq(fmt, bw, n, seed=bw + len(fmt))
-        iq[5000:5040] = iq[5000]   # a run of equal powers
-        _streams[fmt, bw] = (iq, torch.from_numpy(iq).cuda())
-    return _streams[fmt, bw]
 
 
 @pytest.mark.parametrize("fmt,bw", R.FORMATS)

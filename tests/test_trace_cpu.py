@@ -187,3 +187,98 @@ def test_trace_entry_points_sit_under_the_abi_guard():
     for name, body in found.items():
         assert "abi_guard" in body.split("{", 1)[1][:80], name
     assert src.count('extern "C"') == len(found)
+
+
+# ---- what tests/test_gpu_trace_reach.py builds on: its helpers, and the conditions its bounds need, on the CPU ----
+
+def test_bins_holding():
+    assert R.bins_holding([], 5, 0, 41).size == 0
+    assert R.bins_holding([0, 4, 5, 5, 39, 40], 5, 0, 41).tolist() == [0, 1, 7, 8]
+    assert R.bins_holding([40, 41, -1], 5, 0, 41).tolist() == [8]                 # 41 and -1 are outside the stream
+    assert R.bins_holding([99, 100, 104, 105, 140], 5, 100, 41).tolist() == [0, 1, 8]
+    assert R.bins_holding(np.array([7, 3]), 1, 0, 8).tolist() == [3, 7]
+    got = R.bins_holding([2 ** 33 + 5], 2 ** 31, 0, 2 ** 34)
+    assert got.tolist() == [4] and got.dtype == np.int64
+
+
+def test_call_segments_counts_the_cuts():
+    """against a walk over every sample: a new segment at each bin start and each multiple of the tile inside a bin"""
+    tile = 8
+    for B in (8, 9, 16, 17, 30):
+        for open_ in range(B):
+            for n in (1, 2, 7, 8, 9, B - 1, B, B + 1, 3 * B + 5):
+                if n < 1:
+                    continue
+                g = np.arange(open_, open_ + n)
+                want = len(set(zip((g // B).tolist(), ((g % B) // tile).tolist())))
+                assert R.call_segments(n, B, open_, tile) == want, (B, open_, n)
+    assert R.call_segments(2 * 70001, 70001, 4) == 18 + 18 + 1 and R.call_segments(1, 5000, 4999) == 1
+
+
+@pytest.mark.parametrize("fmt,bw", R.FORMATS)
+def test_phase_bound_holds_over_several_grid_passes(fmt, bw):
+    """The inputs of the multi-pass full-rate test on a device of 256 compute units: numpy's float32 route stays below
+    half of PHASE_TOL_DEG on exactly these samples, so the bound taken on 200 003 samples needs no widening for 8.4
+    million.  Measured: 2.42e-5 (int8), 2.71e-5 (int16), 2.70e-5 (cf32) degrees."""
+    pass_, n = R.grid_pass(fmt, 256)
+    assert pass_ == 2048 * 256 * R.SAMPLES_PER_VECTOR[fmt] and n > 2 * pass_
+    assert (fmt != "int8" or n == 8389635) and (n - 3) % R.SAMPLES_PER_VECTOR[fmt] == 0
+    worst = R.float32_phase_error(R.phase_inputs(fmt, bw, n + 1, seed=21))
+    print(f"{fmt}/{bw}: {worst:.3e} degrees over {n + 1} samples")
+    assert worst < R.PHASE_TOL_DEG / 2, worst
+
+
+def test_phase_bound_holds_wide_and_scaled_inputs():
+    """The other full-rate inputs of the reach module: integers over the whole container (measured 2.4e-5 and 2.5e-5
+    degrees) and the cf32 inputs times 2^40 and 2^-40 (2.63e-5 at both: the scaling is exact)."""
+    for fmt in ("int8", "int16"):
+        iq = R.wide_iq(fmt, 5 * (trace.TILE + 1) + 3, seed=6)[:20003]
+        full = 128 if fmt == "int8" else 32768
+        assert iq.min() == -full and iq.max() == full - 1 and tuple(iq[3]) == (-full, -full)
+        assert R.float32_phase_error(iq) < R.PHASE_TOL_DEG / 2
+    base = R.phase_inputs("cf32", 12, 20003, seed=8)
+    for e in (40, -40):
+        iq = base * np.float32(2.0 ** e)
+        assert iq.dtype == np.float32 and np.array_equal(iq.astype(np.float64), base.astype(np.float64) * 2.0 ** e)
+        u, _ = R.powers(iq, "cf32", 12)
+        assert np.all((u == 0) | (u > 2.0 ** -1000)) and np.all(u < 2.0 ** 1000)     # normal doubles
+        assert np.all((iq == 0) | (np.abs(iq) >= np.finfo(np.float32).tiny))            # normal floats
+        assert R.float32_phase_error(iq) < R.PHASE_TOL_DEG / 2
+
+
+def test_reference_mean_against_a_sequential_sum():
+    """cf32: the restatement sums a bin pairwise (numpy); a plain sequential sum of the same doubles stays inside the
+    count * 2^-52 that mean_close allows, with room for the device's own order.  Measured at B = 70 001: 5.7e-14
+    against an allowance of 1.6e-11."""
+    iq = R.random_iq("cf32", 12, 8 * 100003 + 4, seed=16)[:200000]
+    for B in (3, 4096, 70001):
+        want = R.envelope_fast(iq, "cf32", 12, B, partial=False)
+        u, _ = R.powers(iq[:want.size * B], "cf32", 12)
+        seq = np.cumsum(u.reshape(want.size, B), axis=1)[:, -1] / float(B)
+        rel = np.abs(seq - want["power_mean"]) / want["power_mean"]
+        print(f"B = {B}: {rel.max():.2e} of an allowed {B * 2.0 ** -52:.2e}")
+        assert np.all(rel <= B * 2.0 ** -52)
+        if B == 70001:
+            assert rel.max() < 0.05 * B * 2.0 ** -52
+
+
+@pytest.mark.parametrize("fmt,bw", [("int8", 8), ("int16", 12), ("cf32", 12)])
+def test_planted_fold_stream(fmt, bw):
+    T = trace.TILE
+    B = 66 * T + 3
+    streams = R.planted_fold_stream(fmt, bw, B, seed=7)
+    assert len(streams) == 2 and -(-B // T) == 67
+    for iq, (first, second) in zip(streams, ((2, 66), (10, 50))):
+        assert iq.shape == (3 * B + 5000, 2) and iq.dtype == R.NP_DTYPE[fmt]
+        u, _ = R.powers(iq, fmt, bw)
+        in_bin = u[B:2 * B]
+        top = np.flatnonzero(in_bin == in_bin.max())
+        assert top.tolist() == [first * T + 17, second * T + 1]                  # the planted pair, and nowhere larger
+        assert np.flatnonzero(in_bin == 0).tolist() == [65 * T + 4000] and np.count_nonzero(u == 0) == 1
+        assert first % 64 == second % 64 or (first, second) == (10, 50)       # one lane of the fold in two rounds, or two
+        assert u.max() == in_bin.max() and np.sort(u)[-3] <= in_bin.max() / 4 + 1e-30   # half scale elsewhere
+        rec = R.envelope_fast(iq, fmt, bw, B)
+        assert rec.size == 4 and rec["count"].tolist() == [B, B, B, 5000]
+        assert rec["peak_sample"][1] == B + first * T + 17 and rec["power_min"][1] == 0 and np.all(rec["power_min"][[0, 2, 3]] > 0)
+        big = (1.0, -1.0) if fmt == "cf32" else (-1.0, -1.0)
+        assert (rec["peak_i"][1], rec["peak_q"][1]) == big

@@ -149,6 +149,65 @@ def phase_inputs(fmt, bw, n, seed):
     return iq
 
 
+SAMPLES_PER_VECTOR = {"int8": 8, "int16": 4, "cf32": 2}   # one 16-byte load of trace_samples_kernel
+
+
+def grid_pass(fmt, cus):
+    """(pass_, n): the samples one pass of pfb_trace_samples' grid covers on a device of `cus` compute units (8
+    workgroups per unit, 256 lanes, one vector per lane), and a call of two whole passes, half a workgroup of vectors
+    of a third, and a scalar tail of three samples."""
+    S = SAMPLES_PER_VECTOR[fmt]
+    pass_ = 8 * cus * 256 * S
+    return pass_, 2 * pass_ + 128 * S + 3
+
+
+def bins_holding(indices, B, origin, n):
+    """The bins (sorted, each once) that hold the samples with the given global indices, for a stream of n samples
+    whose first sample has global index `origin` and starts bin 0; indices outside the stream hold no bin."""
+    i = np.asarray(indices, dtype=np.int64).reshape(-1) - origin
+    return np.unique(i[(i >= 0) & (i < n)] // B)
+
+
+def call_segments(n, B, open_, tile=4096):
+    """The segments an envelope call of n > 0 samples is cut into when its first bin already holds open_ < B samples:
+    one per started tile of each bin (bins of 1024 samples and more; the partials a bin longer than a tile needs)."""
+    last = open_ + n - 1
+    return (last // B) * (-(-B // tile)) + (last % B) // tile + 1 - open_ // tile
+
+
+def wide_iq(fmt, n, seed):
+    """Integers over the whole range of the container, whatever the handle's bit width says, with the container's
+    largest power (-full, -full) at sample 3."""
+    bits = {"int8": 8, "int16": 16}[fmt]
+    iq = random_iq(fmt, bits, n, seed)
+    iq[3] = -(1 << (bits - 1))
+    return iq
+
+
+def planted_fold_stream(fmt, bw, B, seed, tile=4096):
+    """Two streams of 3 B + 5000 samples for a bin of 67 partials (B = 66 tiles + 3): random data at half scale without
+    a zero sample; in bin 1 the same full-scale sample twice -- in partials 2 and 66, which one lane of the fold takes
+    in two rounds, or (second stream) in partials 10 and 50, two lanes -- and the bin's only zero sample in partial 65."""
+    assert (B - 1) // tile == 66 and B % tile >= 2
+    n = 3 * B + 5000
+    rng = np.random.default_rng(seed)
+    if fmt == "cf32":
+        iq = rng.random((n, 2), dtype=np.float32) - np.float32(0.5)
+        big, floor = (1.0, -1.0), (2.0 ** -10, 0.0)
+    else:
+        full = 1 << (bw - 1)
+        iq = rng.integers(-(full // 2), full // 2, size=(n, 2)).astype(NP_DTYPE[fmt])
+        big, floor = (-full, -full), (1, 1)
+    iq[~iq.any(axis=1)] = floor
+    out = []
+    for first, second in ((2, 66), (10, 50)):
+        v = iq.copy()
+        v[B + first * tile + 17] = v[B + second * tile + 1] = big
+        v[B + 65 * tile + 4000] = 0
+        out.append(v)
+    return tuple(out)
+
+
 def phase_diff(a, b):
     """|a - b| modulo 360 degrees"""
     d = np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)) % 360.0
