@@ -797,6 +797,98 @@ int pfb_mf_process_iq_file(pfb_mf_handle* h, const char* path, void* out, uint64
 /* Name of the kernel the last process call launched ("" before the first). */
 const char* pfb_mf_last_kernel(const pfb_mf_handle* h);
 
+/* ---- time-binned waterfalls of channelizer and STFT output ---------------------------------------------
+ * Replaces the arithmetic of the reference's two-dimensional pictures (drawing stays with the caller):
+ *   matlab/channelizer_example.m:56-71                  surf of abs(channelizer(x)), one window after another
+ *   matlab/generate_channelized_training_iq.m:100-108   surf(f,t,abs(chan_iq))
+ *   matlab/spectrogram_my_iq.m:114-115                  mesh of abs(s).^2
+ * Input: a matrix of `rows` rows (frames) by W = width columns (channels, or STFT frequency rows), 1 <= W <= 65536.
+ * Per element, by pfb_wf_config.element:
+ *   PFB_WF_COMPLEX    complex64: p = (double)re*(double)re + (double)im*(double)im; the products are exact in double,
+ *                     so contraction cannot change the result
+ *   PFB_WF_MAGNITUDE  float32 a: p = (double)a*(double)a
+ *   PFB_WF_POWER      float32 v: p = (double)v
+ * Layout, ld in elements (a value smaller than the dense one is PFB_ERR_BAD_ARG):
+ *   PFB_WF_ROWS       x[m*ld + k]: the channelizer's frame-major output and the STFT's out[m*nfft + r]; ld = 0 means W
+ *   PFB_WF_COLUMNS    x[k*ld + m]: the channelizer's channel-major output; ld = 0 means this call's `rows`
+ * Bins and cells: the rows are cut into bins of bin_rows = B consecutive rows (1 .. 2^24), counted from the handle's
+ * origin (0 after create / reset; pfb_wf_flush starts a new grid at the next row).  Each completed bin gives W cells of
+ * 16 bytes, bin-major: out[b*W + k] is bin b of column k.
+ * Guarantees:
+ *   - power_max, power_min and peak_row are exact selections (taken on the double p, the first row winning among equal
+ *     powers): the same bits under any cutting of the rows into calls, either layout, any ld and any pointer alignment,
+ *     and whether the matrix is in device memory, in host memory or made from a file by pfb_wf_from_*_iq_file.
+ *   - power_mean is a double sum divided by the count, then rounded to float32.  The sum is taken without
+ *     floating-point atomics in an order fixed by the call's lengths and its pointer's alignment to 16 bytes: the same
+ *     call gives the same bits every time, another cutting may move the last bit.
+ *   - Inputs must be finite: a non-finite element may leave the cells of its own (bin, column) unspecified; it never
+ *     disturbs another cell, never faults and never causes an access outside the buffers.
+ *   - No sqrt and no log10 run on the device: magnitude and dB are the host's, one value per cell.
+ * Every argument is validated before the device is touched.  PFB_ERR_BAD_ARG: null pointers, a wrong struct_size, width
+ * outside 1 .. 65536, bin_rows outside 1 .. 2^24, an unknown element, layout or mem, any flag bit (none is defined),
+ * PFB_WF_COLUMNS with PFB_MEM_HOST, a device x not aligned to one element, out not aligned to 16 bytes.  Then
+ * PFB_ERR_NO_DEVICE without a HIP device. */
+enum { PFB_WF_COMPLEX = 0, PFB_WF_MAGNITUDE = 1, PFB_WF_POWER = 2 };
+enum { PFB_WF_ROWS = 0, PFB_WF_COLUMNS = 1 };
+
+typedef struct pfb_wf_cell {
+  float power_max, power_mean, power_min;  /* (float) of the double value, round to nearest even                  */
+  uint32_t peak_row;                       /* offset inside the bin (0 .. B-1) of the FIRST row holding the max   */
+} pfb_wf_cell;
+
+typedef struct pfb_wf_config {
+  uint32_t struct_size;  /* = sizeof(pfb_wf_config)                 */
+  uint32_t width;        /* W, 1 .. 65536                           */
+  uint32_t bin_rows;     /* B, 1 .. 2^24                            */
+  uint32_t element;      /* PFB_WF_COMPLEX / MAGNITUDE / POWER      */
+  uint32_t layout;       /* PFB_WF_ROWS / PFB_WF_COLUMNS            */
+  uint32_t flags;        /* 0                                       */
+  int32_t device_id;     /* HIP device ordinal, -1 = current device */
+} pfb_wf_config;
+
+typedef struct pfb_wf_handle pfb_wf_handle;
+
+/* Lifecycle as pfb_trace_*.  The handle holds the row position and, on the device, the bin a call left open. */
+int pfb_wf_create(const pfb_wf_config* cfg, pfb_wf_handle** out);
+int pfb_wf_destroy(pfb_wf_handle* h);
+int pfb_wf_reset(pfb_wf_handle* h);   /* origin back to 0, no open bin */
+int pfb_wf_set_stream(pfb_wf_handle* h, void* hip_stream);
+int pfb_wf_sync(pfb_wf_handle* h);
+int pfb_wf_get_device(const pfb_wf_handle* h, int* device_id);
+/* The bins the next call of `rows` rows completes. */
+int pfb_wf_bins_for(const pfb_wf_handle* h, uint64_t rows, uint64_t* bins_out);
+/* The cells of the bins these rows complete, to `out` (room for capacity_bins * W cells); *bins_out = their number.
+ * PFB_ERR_CAPACITY sets *bins_out to the number needed and changes no state.  mem: x and out are both device pointers
+ * (PFB_MEM_DEVICE) or both host pointers (PFB_MEM_HOST, PFB_WF_ROWS only, staged as pfb_stft_process stages them: a row
+ * playing the role of a sample, a bin of W cells that of a frame, steps of at most 64 MiB per side).  Synchronous. */
+int pfb_wf_process(pfb_wf_handle* h, const void* x, uint64_t rows, uint64_t ld, pfb_wf_cell* out,
+                   uint64_t capacity_bins, uint64_t* bins_out, uint32_t mem);
+/* Same, device pointers, enqueued on the handle's stream without a host sync (bins longer than the row tile use a
+ * device scratch that grows with the longest call so far: a call that grows it waits for the device). */
+int pfb_wf_process_async(pfb_wf_handle* h, const void* d_x, uint64_t rows, uint64_t ld, pfb_wf_cell* d_out,
+                         uint64_t capacity_bins, uint64_t* bins_out);
+/* The open bin's W cells to host memory (*rows_in_bin = the rows it holds, 0 when none is open: nothing is written);
+ * the mean is over the rows present.  A new bin grid starts at the next row. */
+int pfb_wf_flush(pfb_wf_handle* h, pfb_wf_cell* out_host, uint32_t* rows_in_bin);
+/* Host only: B = max(1, ceil(rows / max_bins)), the bin that shows `rows` rows in at most max_bins image rows.
+ * PFB_ERR_BAD_ARG when max_bins == 0 or B > 2^24. */
+int pfb_wf_choose_bin(uint64_t rows, uint32_t max_bins, uint32_t* bin_rows);
+/* One whole .iq record to an image without its channel matrix ever existing in full: the header is checked as in
+ * pfb_process_iq_file, the handle is reset, B = pfb_wf_choose_bin(the frames the record gives, max_bins), and the
+ * payload is streamed in chunks of chunk_samples samples (0 = 2^24): each is copied in, transformed by
+ * pfb_process_async into a device scratch sized for one chunk and reduced from there, all on the handle's stream.  The
+ * final partial bin is included.  Element kind and layout follow the handle (complex, PFB_FLAG_MAGNITUDE, + PFB_FLAG_POWER;
+ * frame-major or channel-major).  `out` is host memory with room for capacity_bins * M cells; *bins_out =
+ * ceil(frames / B), also on PFB_ERR_CAPACITY; *bin_rows_out = B. */
+int pfb_wf_from_channelizer_iq_file(pfb_handle* ch, const char* path, uint32_t max_bins, uint64_t chunk_samples,
+                                    pfb_wf_cell* out, uint64_t capacity_bins, uint64_t* bins_out,
+                                    uint32_t* bin_rows_out, pfb_iq_info* info_out);
+/* The same loop over pfb_stft_process_async: W = nfft, PFB_STFT_COMPLEX gives PFB_WF_COMPLEX and PFB_STFT_POWER gives
+ * PFB_WF_POWER; a PFB_STFT_DB handle is PFB_ERR_BAD_ARG (averaging dB is not averaging power). */
+int pfb_wf_from_stft_iq_file(pfb_stft_handle* st, const char* path, uint32_t max_bins, uint64_t chunk_samples,
+                             pfb_wf_cell* out, uint64_t capacity_bins, uint64_t* bins_out, uint32_t* bin_rows_out,
+                             pfb_iq_info* info_out);
+
 #ifdef __cplusplus
 }
 #endif

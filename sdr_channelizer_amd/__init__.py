@@ -12,10 +12,12 @@ from .matched_filter import (MatchedFilter, compress, compress_iq_file, pulse_de
 from .pulse_source import PulseTrain, pulse_train, synth_params  # noqa: F401
 from .stft import Stft, spectrogram_from_iq_file, stft, stft_axes  # noqa: F401
 from .trace import Envelope, Trace, envelope, envelope_from_iq_file  # noqa: F401
+from .waterfall import Waterfall, WaterfallImage, waterfall, waterfall_from_iq_file  # noqa: F401
 
 __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empty", "PfbError", "LIB_PATH",
            "Stft", "stft", "stft_axes", "spectrogram_from_iq_file",
            "analyze_dwell", "dwell_from_iq_file", "fit_event", "next_event", "EventPredictor", "DwellStats",
            "PulseTrain", "pulse_train", "synth_params",
            "Trace", "Envelope", "envelope", "envelope_from_iq_file",
-           "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files"]
+           "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
+           "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file"]

@@ -42,6 +42,8 @@ PFB_SYNTH_BARKER13, PFB_SYNTH_BARKER_DEGREES, PFB_SYNTH_PHASE_FROM_ZERO, PFB_SYN
 PFB_MF_COMPLEX, PFB_MF_POWER = 0, 1
 PFB_MF_NORMALIZE = 1
 PFB_MF_ROUTE_AUTO, PFB_MF_ROUTE_FUSED, PFB_MF_ROUTE_PARTITIONED = 0, 1, 2
+PFB_WF_COMPLEX, PFB_WF_MAGNITUDE, PFB_WF_POWER = 0, 1, 2
+PFB_WF_ROWS, PFB_WF_COLUMNS = 0, 1
 
 
 class PfbConfig(C.Structure):
@@ -129,6 +131,15 @@ class PfbMfConfig(C.Structure):
 class PfbMfPlan(C.Structure):
     _fields_ = [("fft_length", C.c_uint32), ("route", C.c_uint32), ("partitions", C.c_uint32),
                 ("block_outputs", C.c_uint32), ("workspace_bytes", C.c_uint64)]
+
+
+class PfbWfConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("bin_rows", C.c_uint32), ("element", C.c_uint32),
+                ("layout", C.c_uint32), ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbWfCell(C.Structure):
+    _fields_ = [("power_max", C.c_float), ("power_mean", C.c_float), ("power_min", C.c_float), ("peak_row", C.c_uint32)]
 
 
 class PfbFastPlanDesc(C.Structure):
@@ -221,6 +232,9 @@ EXPORTS = (
     "pfb_mf_describe", "pfb_mf_create", "pfb_mf_destroy", "pfb_mf_reset", "pfb_mf_set_stream", "pfb_mf_sync",
     "pfb_mf_get_device", "pfb_mf_outputs_for", "pfb_mf_next_index", "pfb_mf_process", "pfb_mf_process_async",
     "pfb_mf_process_iq_file", "pfb_mf_last_kernel",
+    "pfb_wf_create", "pfb_wf_destroy", "pfb_wf_reset", "pfb_wf_set_stream", "pfb_wf_sync", "pfb_wf_get_device",
+    "pfb_wf_bins_for", "pfb_wf_process", "pfb_wf_process_async", "pfb_wf_flush", "pfb_wf_choose_bin",
+    "pfb_wf_from_channelizer_iq_file", "pfb_wf_from_stft_iq_file",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -375,6 +389,21 @@ def load() -> C.CDLL:
     lib.pfb_mf_process_iq_file.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(u64), C.POINTER(PfbIqInfo)]
     lib.pfb_mf_last_kernel.argtypes = [vp]
     lib.pfb_mf_last_kernel.restype = C.c_char_p
+    lib.pfb_wf_create.argtypes = [C.POINTER(PfbWfConfig), C.POINTER(vp)]
+    lib.pfb_wf_destroy.argtypes = [vp]
+    lib.pfb_wf_reset.argtypes = [vp]
+    lib.pfb_wf_set_stream.argtypes = [vp, vp]
+    lib.pfb_wf_sync.argtypes = [vp]
+    lib.pfb_wf_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_wf_bins_for.argtypes = [vp, u64, C.POINTER(u64)]
+    lib.pfb_wf_process.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_wf_process_async.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
+    lib.pfb_wf_flush.argtypes = [vp, vp, C.POINTER(u32)]
+    lib.pfb_wf_choose_bin.argtypes = [u64, u32, C.POINTER(u32)]
+    lib.pfb_wf_from_channelizer_iq_file.argtypes = [vp, C.c_char_p, u32, u64, vp, u64, C.POINTER(u64), C.POINTER(u32),
+                                                    C.POINTER(PfbIqInfo)]
+    lib.pfb_wf_from_stft_iq_file.argtypes = [vp, C.c_char_p, u32, u64, vp, u64, C.POINTER(u64), C.POINTER(u32),
+                                             C.POINTER(PfbIqInfo)]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]

@@ -95,6 +95,20 @@ struct pfb_handle {
   hipEvent_t ev_switch = nullptr;    // pfb_set_stream: orders the old stream's work in front of the new stream's
 };
 
+pfb::OutputDesc pfb::describe_output(const pfb_handle* h) {
+  pfb::OutputDesc d;
+  d.device = h->device;
+  d.stream = h->stream;
+  d.fmt = h->fmt;
+  d.bit_width = h->bit_width;
+  d.bps = h->bps;
+  d.width = (uint32_t)h->M;
+  d.element = !(h->flags & PFB_FLAG_MAGNITUDE) ? PFB_WF_COMPLEX : ((h->flags & PFB_FLAG_POWER) ? PFB_WF_POWER : PFB_WF_MAGNITUDE);
+  d.layout = h->layout == PFB_LAYOUT_CHANNEL_MAJOR ? PFB_WF_COLUMNS : PFB_WF_ROWS;
+  d.carry_max = (uint64_t)h->D - 1;
+  return d;
+}
+
 namespace {
 
 void free_handle(pfb_handle* h) {

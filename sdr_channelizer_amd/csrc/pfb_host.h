@@ -87,6 +87,21 @@ struct StageOut {
 int stage_host(HostStage& st, hipStream_t stream, const StageSteps& steps, const void* in, uint64_t n,
                const StageOut& out);
 
+// What pfb_waterfall.hip reads of a channelizer or STFT handle whose output it reduces (pfb_wf_from_*_iq_file):
+// defined next to each handle, pfb_api.cpp and pfb_stft_api.cpp.
+struct OutputDesc {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int fmt = 0, bit_width = 0, bps = 0;  // of the input samples
+  uint32_t width = 0;                   // output values per frame: M, nfft
+  uint32_t element = 0;                 // PFB_WF_* of one output value
+  uint32_t layout = 0;                  // PFB_WF_ROWS / PFB_WF_COLUMNS
+  bool reducible = true;                // false: the output is not a power (PFB_STFT_DB)
+  uint64_t carry_max = 0;               // the most samples the handle carries from call to call
+};
+OutputDesc describe_output(const pfb_handle* h);
+OutputDesc describe_output(const pfb_stft_handle* h);
+
 struct Record {  // an open .iq record whose header has been parsed and checked
   int fd = -1;
   pfb_iq_info info{};  // zeroed: callers copy it out even when the record could not be opened

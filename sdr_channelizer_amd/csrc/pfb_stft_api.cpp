@@ -34,6 +34,21 @@ struct pfb_stft_handle {
   hipEvent_t ev_switch = nullptr;
 };
 
+pfb::OutputDesc pfb::describe_output(const pfb_stft_handle* h) {
+  pfb::OutputDesc d;
+  d.device = h->device;
+  d.stream = h->stream;
+  d.fmt = h->fmt;
+  d.bit_width = h->bit_width;
+  d.bps = h->bps;
+  d.width = (uint32_t)h->nfft;
+  d.element = h->output == PFB_STFT_COMPLEX ? PFB_WF_COMPLEX : PFB_WF_POWER;
+  d.layout = PFB_WF_ROWS;
+  d.reducible = h->output != PFB_STFT_DB;
+  d.carry_max = (uint64_t)h->L - 1;
+  return d;
+}
+
 namespace {
 
 void free_stft(pfb_stft_handle* h) {
