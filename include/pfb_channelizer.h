@@ -889,6 +889,112 @@ int pfb_wf_from_stft_iq_file(pfb_stft_handle* st, const char* path, uint32_t max
                              pfb_wf_cell* out, uint64_t capacity_bins, uint64_t* bins_out, uint32_t* bin_rows_out,
                              pfb_iq_info* info_out);
 
+/* ---- channel synthesizer: an I/Q stream rebuilt from channelizer output ---------------------------------
+ * The twin of pfb_process: it reads exactly what a frame-major channelizer handle writes and puts the channels back
+ * together at the full rate, all of them or the ones a weight mask keeps (the emitter pfb_pdw_from_iq_file reported in
+ * column `bin`, alone, as a time signal for pfb_mf_*, pfb_dwell_analyze or pfb_trace_*).
+ * Input: frame m = 0, 1, ... (stream-absolute) is M complex64 values at y[m*ld + c], ld >= M (ld = 0 means M).
+ * Column c holds channel k = c, or, with PFB_CHSYN_FFTSHIFT, k = (c + ceil(M/2)) mod M: the columns a handle made
+ * with PFB_FLAG_FFTSHIFT writes.  Per frame, with w an optional real float32 weight per COLUMN (NULL = all ones; a 0/1
+ * mask isolates a band):
+ *   v_m[p] = sum_k w[c(k)] * y[m, c(k)] * e^{+j 2 pi k p / M}          p = 0 .. M-1
+ * Per output sample s = b*D + d, 0 <= d < D, with g[0 .. L_g-1] the synthesis taps, L_g = M*P_g and Q = L_g / D:
+ *   x[s] = scale * sum_{q=0}^{Q-1} g[d + q*D] * v_{b-q}[(d + q*D) mod M]
+ * Frames before frame 0 are zero; the sum is always taken in ascending q.  With PFB_CHSYN_DEROTATE the input was made
+ * under PFB_FLAG_DEROTATE: v_m is then read at (p + m*D) mod M, an index change (the identity for D = M), which is why
+ * the handle keeps the absolute frame index (pfb_chsyn_set_frame_index for a stream that starts elsewhere).
+ * F frames in give exactly F*D samples out; a call of 0 frames is legal; feeding Q-1 zero frames drains the tail.
+ * scale = 0 means D, the unity-gain value when the analysis and the synthesis taps both have DC gain 1.
+ * Output: PFB_FMT_CF32, interleaved float I,Q, or PFB_FMT_INT16_IQ, round(x * 2^(bit_width-1)) with halves away from
+ * zero, saturated to -2^(bit_width-1) .. 2^(bit_width-1)-1 (a NaN stores 0) -- a result that can be written back as a
+ * record with pfb_iq_serialize_header.
+ * Reconstruction.  A channelizer with taps h (length L_h) and this synthesizer with taps g return the input delayed by
+ *   delta = L_h/2 + L_g/2 - input_offset   samples
+ * to the accuracy the pair of filters allows.  For the 2x oversampled bank, D = M/2, with h =
+ * pfb_design_prototype(M, 12) and g = pfb_design_prototype(D, 24) (length 12*M), the error is 3.6e-5 of the signal
+ * (-89 dB) and the gain 1.0000001 (float64, M = 16, 56, 64).  For the critically sampled bank, D = M, with g = h the
+ * Kaiser-windowed sinc is a Nyquist filter and not a root-Nyquist one: the sum above is computed all the same, but it
+ * reconstructs only to about 20 %.  Reconstruction quality at D = M is the business of the caller's taps.
+ * Domain: 2 <= M <= 4096; D = M (decimation = 0 or M) or D = M/2 for even M; 1 <= P_g <= 24; the taps finite float32,
+ * copied at create.  Channel-major input (pfb_chsyn_config.layout = PFB_LAYOUT_CHANNEL_MAJOR) is PFB_ERR_UNSUPPORTED.
+ * Method: packed fp32.  PFB_CHSYN_ROUTE_GENERIC (any M) is two launches: the M-point DFTs of a chunk of frames into a
+ * device workspace the handle owns (grow-only, at most 64 MiB, freed at destroy), then the Q-term sums out of it.
+ * PFB_CHSYN_ROUTE_FUSED (M = 56, 64, 128, 256, both D, both outputs, as long as tile_frames + Q - 1 rows fit 64 KiB of
+ * LDS) is one launch: a workgroup owns tile_frames consecutive output blocks and keeps the rows they need in LDS.
+ * PFB_CHSYN_ROUTE_AUTO takes the fused route where there is one.  The handle carries the last Q-1 rows v_m in device
+ * memory.  A frame's v_m does not depend on where the frame sits in a tile, a call, a chunk or a staging step, so
+ * within one route the output is THE SAME BITS under any cutting of the frame stream into calls.  The two routes
+ * differ by rounding only.
+ * Elements that are not finite poison only the Q*D output samples their frame reaches; they never cause a fault or an
+ * access outside the buffers.
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, M < 2, P_g = 0, a decimation other than 0, M or M/2 (M even), a tap or a scale that is not finite, an
+ * unknown flag, route or layout, an unknown mem, ld < M, a device pointer not aligned to 8 bytes (y) or to one output
+ * sample (out).  PFB_ERR_BAD_FORMAT: an output format other than PFB_FMT_CF32 / PFB_FMT_INT16_IQ, bit_width outside
+ * 2..16 (int16; ignored for cf32).  PFB_ERR_UNSUPPORTED: M > 4096, P_g > 24 (the taps of such a shape are not looked
+ * at), channel-major input, PFB_CHSYN_ROUTE_FUSED for a shape without a fused kernel.  Then PFB_ERR_NO_DEVICE without a
+ * HIP device. */
+enum { PFB_CHSYN_FFTSHIFT = 1u << 0, PFB_CHSYN_DEROTATE = 1u << 1 };
+enum { PFB_CHSYN_ROUTE_AUTO = 0, PFB_CHSYN_ROUTE_FUSED = 1, PFB_CHSYN_ROUTE_GENERIC = 2 };
+
+typedef struct pfb_chsyn_config {
+  uint32_t struct_size;       /* = sizeof(pfb_chsyn_config)                                       */
+  uint32_t num_channels;      /* M                                                                */
+  uint32_t taps_per_channel;  /* P_g: the synthesis taps have M*P_g values                        */
+  uint32_t decimation;        /* D: 0 or M = critically sampled, M/2 = 2x oversampled             */
+  const float* taps;          /* g[0 .. M*P_g-1], finite, copied at create                        */
+  double scale;               /* 0 = D                                                            */
+  uint32_t output_format;     /* PFB_FMT_CF32 / PFB_FMT_INT16_IQ                                  */
+  uint32_t bit_width;         /* int16 output: full scale 2^(bit_width-1), 2..16                  */
+  uint32_t layout;            /* pfb_output_layout of the INPUT; PFB_LAYOUT_FRAME_MAJOR only      */
+  uint32_t flags;             /* PFB_CHSYN_*                                                      */
+  uint32_t route;             /* PFB_CHSYN_ROUTE_*                                                */
+  int32_t device_id;          /* HIP device ordinal, -1 = current device                          */
+} pfb_chsyn_config;
+
+typedef struct pfb_chsyn_plan { /* what pfb_chsyn_describe reports; host only                     */
+  uint32_t route;             /* PFB_CHSYN_ROUTE_FUSED or PFB_CHSYN_ROUTE_GENERIC                 */
+  uint32_t decimation;        /* D                                                                */
+  uint32_t q;                 /* Q = M*P_g / D: the frames one output sample sums over            */
+  uint32_t tile_frames;       /* output blocks per workgroup (fused), frames per DFT tile (generic) */
+  uint64_t carried_bytes;     /* the Q-1 carried rows: (Q-1)*M*8                                  */
+  uint64_t workspace_bytes;   /* the most the workspace grows to: 0 (fused), <= 64 MiB            */
+} pfb_chsyn_plan;
+
+typedef struct pfb_chsyn_handle pfb_chsyn_handle;
+
+/* Host only: validate cfg (everything pfb_chsyn_create checks before the device) and report the plan. */
+int pfb_chsyn_describe(const pfb_chsyn_config* cfg, pfb_chsyn_plan* plan_out);
+/* Lifecycle as pfb_mf_*.  The handle owns the taps, the weights, the carried rows and the workspace. */
+int pfb_chsyn_create(const pfb_chsyn_config* cfg, pfb_chsyn_handle** out);
+int pfb_chsyn_destroy(pfb_chsyn_handle* h);
+int pfb_chsyn_reset(pfb_chsyn_handle* h);   /* nothing carried, frame index 0; the weights stay */
+int pfb_chsyn_set_stream(pfb_chsyn_handle* h, void* hip_stream);
+int pfb_chsyn_sync(pfb_chsyn_handle* h);
+int pfb_chsyn_get_device(const pfb_chsyn_handle* h, int* device_id);
+/* Absolute index m of the next frame (what PFB_CHSYN_DEROTATE reads its rows by); the carried rows stay and are the
+ * frames next_frame-1, next_frame-2, ... from then on. */
+int pfb_chsyn_set_frame_index(pfb_chsyn_handle* h, uint64_t next_frame);
+int pfb_chsyn_get_frame_index(const pfb_chsyn_handle* h, uint64_t* next_frame);
+/* The samples a call of num_frames frames writes: num_frames * D. */
+int pfb_chsyn_samples_for(const pfb_chsyn_handle* h, uint64_t num_frames, uint64_t* samples_out);
+/* M weights from host memory (NULL: all ones), in effect from the next frame on: frames already taken keep theirs.
+ * Waits for what the handle's stream has queued. */
+int pfb_chsyn_set_weights(pfb_chsyn_handle* h, const float* weights);
+/* Synthesize num_frames frames; their num_frames*D samples go to `out` (room for capacity_samples), their number to
+ * *samples_out.  PFB_ERR_CAPACITY sets *samples_out to the number needed and changes no state.  mem: y and out are
+ * both host pointers (PFB_MEM_HOST, staged as pfb_stft_process stages them, a frame of ld values playing the role of
+ * a sample and D output samples that of a frame, steps of at most 64 MiB per side) or both device pointers
+ * (PFB_MEM_DEVICE).  Synchronous. */
+int pfb_chsyn_process(pfb_chsyn_handle* h, const void* y, uint64_t num_frames, uint64_t ld, void* out,
+                      uint64_t capacity_samples, uint64_t* samples_out, uint32_t mem);
+/* Same, device pointers, enqueued on the handle's stream without a host sync (a generic call that grows the workspace
+ * waits for the device). */
+int pfb_chsyn_process_async(pfb_chsyn_handle* h, const void* d_y, uint64_t num_frames, uint64_t ld, void* d_out,
+                            uint64_t capacity_samples, uint64_t* samples_out);
+/* Name of the kernel the last process call launched ("" before the first). */
+const char* pfb_chsyn_last_kernel(const pfb_chsyn_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

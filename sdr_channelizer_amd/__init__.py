@@ -11,6 +11,8 @@ from .matched_filter import (MatchedFilter, compress, compress_iq_file, pulse_de
                              replica_from_pulse_train)
 from .pulse_source import PulseTrain, pulse_train, synth_params  # noqa: F401
 from .stft import Stft, spectrogram_from_iq_file, stft, stft_axes  # noqa: F401
+from .synthesizer import (ChannelSynthesizer, design_synthesis_taps, isolate_band, synthesis_delay,  # noqa: F401
+                          synthesize)
 from .trace import Envelope, Trace, envelope, envelope_from_iq_file  # noqa: F401
 from .waterfall import Waterfall, WaterfallImage, waterfall, waterfall_from_iq_file  # noqa: F401
 
@@ -20,4 +22,5 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "PulseTrain", "pulse_train", "synth_params",
            "Trace", "Envelope", "envelope", "envelope_from_iq_file",
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
-           "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file"]
+           "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
+           "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band"]

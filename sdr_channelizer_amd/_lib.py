@@ -44,6 +44,8 @@ PFB_MF_NORMALIZE = 1
 PFB_MF_ROUTE_AUTO, PFB_MF_ROUTE_FUSED, PFB_MF_ROUTE_PARTITIONED = 0, 1, 2
 PFB_WF_COMPLEX, PFB_WF_MAGNITUDE, PFB_WF_POWER = 0, 1, 2
 PFB_WF_ROWS, PFB_WF_COLUMNS = 0, 1
+PFB_CHSYN_FFTSHIFT, PFB_CHSYN_DEROTATE = 1, 2
+PFB_CHSYN_ROUTE_AUTO, PFB_CHSYN_ROUTE_FUSED, PFB_CHSYN_ROUTE_GENERIC = 0, 1, 2
 
 
 class PfbConfig(C.Structure):
@@ -142,6 +144,18 @@ class PfbWfCell(C.Structure):
     _fields_ = [("power_max", C.c_float), ("power_mean", C.c_float), ("power_min", C.c_float), ("peak_row", C.c_uint32)]
 
 
+class PfbChsynConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_channels", C.c_uint32), ("taps_per_channel", C.c_uint32),
+                ("decimation", C.c_uint32), ("taps", C.POINTER(C.c_float)), ("scale", C.c_double),
+                ("output_format", C.c_uint32), ("bit_width", C.c_uint32), ("layout", C.c_uint32), ("flags", C.c_uint32),
+                ("route", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbChsynPlan(C.Structure):
+    _fields_ = [("route", C.c_uint32), ("decimation", C.c_uint32), ("q", C.c_uint32), ("tile_frames", C.c_uint32),
+                ("carried_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -235,6 +249,10 @@ EXPORTS = (
     "pfb_wf_create", "pfb_wf_destroy", "pfb_wf_reset", "pfb_wf_set_stream", "pfb_wf_sync", "pfb_wf_get_device",
     "pfb_wf_bins_for", "pfb_wf_process", "pfb_wf_process_async", "pfb_wf_flush", "pfb_wf_choose_bin",
     "pfb_wf_from_channelizer_iq_file", "pfb_wf_from_stft_iq_file",
+    "pfb_chsyn_describe", "pfb_chsyn_create", "pfb_chsyn_destroy", "pfb_chsyn_reset", "pfb_chsyn_set_stream",
+    "pfb_chsyn_sync", "pfb_chsyn_get_device", "pfb_chsyn_set_frame_index", "pfb_chsyn_get_frame_index",
+    "pfb_chsyn_samples_for", "pfb_chsyn_set_weights", "pfb_chsyn_process", "pfb_chsyn_process_async",
+    "pfb_chsyn_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -404,6 +422,21 @@ def load() -> C.CDLL:
                                                     C.POINTER(PfbIqInfo)]
     lib.pfb_wf_from_stft_iq_file.argtypes = [vp, C.c_char_p, u32, u64, vp, u64, C.POINTER(u64), C.POINTER(u32),
                                              C.POINTER(PfbIqInfo)]
+    lib.pfb_chsyn_describe.argtypes = [C.POINTER(PfbChsynConfig), C.POINTER(PfbChsynPlan)]
+    lib.pfb_chsyn_create.argtypes = [C.POINTER(PfbChsynConfig), C.POINTER(vp)]
+    lib.pfb_chsyn_destroy.argtypes = [vp]
+    lib.pfb_chsyn_reset.argtypes = [vp]
+    lib.pfb_chsyn_set_stream.argtypes = [vp, vp]
+    lib.pfb_chsyn_sync.argtypes = [vp]
+    lib.pfb_chsyn_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_chsyn_set_frame_index.argtypes = [vp, u64]
+    lib.pfb_chsyn_get_frame_index.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_chsyn_samples_for.argtypes = [vp, u64, C.POINTER(u64)]
+    lib.pfb_chsyn_set_weights.argtypes = [vp, vp]
+    lib.pfb_chsyn_process.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_chsyn_process_async.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
+    lib.pfb_chsyn_last_kernel.argtypes = [vp]
+    lib.pfb_chsyn_last_kernel.restype = C.c_char_p
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
