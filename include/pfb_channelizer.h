@@ -995,6 +995,109 @@ int pfb_chsyn_process_async(pfb_chsyn_handle* h, const void* d_y, uint64_t num_f
 /* Name of the kernel the last process call launched ("" before the first). */
 const char* pfb_chsyn_last_kernel(const pfb_chsyn_handle* h);
 
+/* ---- matched-filter bank: delay and carrier of a coded pulse ---------------------------------------------
+ * pfb_mf_* finds a pulse only at the carrier its replica was made for, and the reference's signals do not give one:
+ *   matlab/generate_pulsed_iq.m:13, generate_training_iq.m:13   the carrier is drawn at random in +-fs/2
+ *   tx_rx_pulses_usrp.cpp                                       the TX / RX pair comes from two oscillators
+ * A Barker-13 pulse of 13 x 39 samples keeps 0.41 of its peak power one bin of a 1024-point FFT off its carrier and
+ * 0.0066, at a wrong sample, 37 bins off.  The bank correlates with H replicas, each the caller's modulated to one
+ * frequency offset, and shares the load and the forward FFT of a block among them.
+ * Arithmetic, with x, r, K and g as the matched filter defines them (g by PFB_MF_NORMALIZE in pfb_mfbank_config.flags):
+ *   q_h    = (first_bin + h) * bin_step                    h = 0 .. H-1, first_bin may be negative
+ *   f_h    = q_h * fs / fft_length                         the offset hypothesis h assumes (pfb_mfbank_frequencies)
+ *   y_h[m] = g * sum_{n=0}^{K-1} conj(r[n]) * e^{-j 2 pi q_h n / fft_length} * x[m+n]
+ *   p_h[m] = |y_h[m]|^2
+ * The modulation is anchored at the replica's first sample: y_h[m] does not depend on where a block or a call starts.
+ * Outputs are stream-absolute and only complete windows are produced: N samples so far give max(0, N-K+1) outputs,
+ * exactly as pfb_mf_*.  Steps of whole bins are enough: a pulse of K <= fft_length/2 samples that lies half a bin from
+ * the nearest hypothesis keeps sinc(K / (2 fft_length)) of its amplitude there, 0.900 (-0.91 dB) at K = fft_length/2
+ * and more for every shorter replica.
+ * Outputs, by pfb_mfbank_config.output:
+ *   PFB_MFBANK_BEST     one pfb_mfbank_cell per output m: the largest p_h[m] over h and the h that gave it.  The
+ *                       selection starts from h = 0 and replaces only on a strictly greater power: ties go to the
+ *                       lowest h and a power that is not a number never displaces anything (p_0[m] = NaN stays, h = 0).
+ *   PFB_MFBANK_SURFACE  float32 p_h[m] at out[h * row_pitch + m], the ambiguity picture; row_pitch, in elements, is
+ *                       given per call and must be >= the outputs the call completes; `out` holds
+ *                       (H-1) * row_pitch + outputs elements.  PFB_MFBANK_BEST ignores row_pitch.
+ * Method: pfb_mf_*'s fused route only, 1 <= K <= fft_length/2, fft_length 1024, 2048 or 4096; fft_length = 0 means
+ * 4096, so that the bins of first_bin and bin_step do not depend on K.  One workgroup per block of fft_length - K + 1
+ * outputs transforms the block once and runs the inverse transform H times on a rotated read of the one spectrum table.
+ * State, cutting and rounding as pfb_mf_*: the last min(N, K-1) samples are carried, the same sequence of calls gives the
+ * same bits, different cuttings agree to pfb_mf_*'s tolerance per hypothesis (blocks start where a call or a staging
+ * step starts); a sample that is not finite may spoil every output of the FFT blocks it falls in and nothing else.
+ * Every argument is validated before the device is touched, in pfb_mf_create's order and with its codes.
+ * PFB_ERR_BAD_ARG: null pointers, a wrong struct_size, K = 0, an unknown output or flag, fft_length outside {0, 1024,
+ * 2048, 4096}, bin_step = 0, H = 0, H * bin_step > fft_length (two hypotheses would coincide); then a replica value
+ * that is not finite, an all-zero replica with PFB_MF_NORMALIZE; an unknown mem, row_pitch below the call's outputs
+ * (surface), a device pointer not aligned to one sample (iq) or one output element (out: 8 bytes best, 4 surface).
+ * PFB_ERR_BAD_FORMAT: an unknown sample format, bit_width outside 1..8 (int8) or 1..16 (int16; ignored for cf32).
+ * PFB_ERR_UNSUPPORTED: K > fft_length/2, the code pfb_mf_create gives for PFB_MF_ROUTE_FUSED with such a replica.  Then
+ * PFB_ERR_BAD_ARG for a replica whose scaled spectrum does not fit float32, and PFB_ERR_NO_DEVICE without a HIP device,
+ * last. */
+enum { PFB_MFBANK_BEST = 0, PFB_MFBANK_SURFACE = 1 };
+
+typedef struct pfb_mfbank_config {
+  uint32_t struct_size;      /* = sizeof(pfb_mfbank_config)                                      */
+  uint32_t replica_length;   /* K                                                                */
+  const float* replica;      /* K interleaved re,im, finite, copied at create                    */
+  uint32_t sample_format;    /* pfb_sample_format                                                */
+  uint32_t bit_width;        /* full scale 2^(bit_width-1); ignored for CF32                     */
+  uint32_t output;           /* PFB_MFBANK_BEST / PFB_MFBANK_SURFACE                             */
+  uint32_t flags;            /* PFB_MF_NORMALIZE                                                 */
+  uint32_t fft_length;       /* 0 = 4096, else 1024 / 2048 / 4096                                */
+  int32_t first_bin;         /* q_0 = first_bin * bin_step                                       */
+  uint32_t num_hypotheses;   /* H >= 1, H * bin_step <= fft_length                               */
+  uint32_t bin_step;         /* >= 1                                                             */
+  int32_t device_id;         /* HIP device ordinal, -1 = current device                          */
+} pfb_mfbank_config;
+
+typedef struct pfb_mfbank_plan { /* what pfb_mfbank_describe reports; host only                  */
+  uint32_t fft_length;       /* 1024 / 2048 / 4096                                               */
+  uint32_t block_outputs;    /* outputs per workgroup: fft_length - K + 1                        */
+  uint32_t num_hypotheses;   /* H                                                                */
+  uint32_t lds_bytes;        /* LDS of one workgroup: two fft_length-point complex buffers       */
+} pfb_mfbank_plan;
+
+typedef struct pfb_mfbank_cell { /* one output of PFB_MFBANK_BEST                                */
+  float power;               /* max over h of p_h[m]                                             */
+  int32_t hypothesis;        /* the h that gave it                                               */
+} pfb_mfbank_cell;
+
+typedef struct pfb_mfbank_handle pfb_mfbank_handle;
+
+/* Host only: validate cfg (everything pfb_mfbank_create checks before the device) and report the plan. */
+int pfb_mfbank_describe(const pfb_mfbank_config* cfg, pfb_mfbank_plan* plan_out);
+/* Host only: out[h] = f_h = (first_bin + h) * bin_step * fs / fft_length for h = 0 .. H-1 (not wrapped into +-fs/2).
+ * Reads struct_size, fft_length, first_bin, num_hypotheses and bin_step of cfg and nothing else: the replica may be
+ * NULL.  PFB_ERR_BAD_ARG for null pointers, a wrong struct_size, a grid pfb_mfbank_create refuses or fs not finite. */
+int pfb_mfbank_frequencies(const pfb_mfbank_config* cfg, double fs, double* out);
+/* Lifecycle, stream, sync, device, outputs_for, next_index and last_kernel as pfb_mf_*. */
+int pfb_mfbank_create(const pfb_mfbank_config* cfg, pfb_mfbank_handle** out);
+int pfb_mfbank_destroy(pfb_mfbank_handle* h);
+int pfb_mfbank_reset(pfb_mfbank_handle* h);   /* stream position back to 0, nothing carried */
+int pfb_mfbank_set_stream(pfb_mfbank_handle* h, void* hip_stream);
+int pfb_mfbank_sync(pfb_mfbank_handle* h);
+int pfb_mfbank_get_device(const pfb_mfbank_handle* h, int* device_id);
+int pfb_mfbank_outputs_for(const pfb_mfbank_handle* h, uint64_t num_samples, uint64_t* outputs_out);
+int pfb_mfbank_next_index(const pfb_mfbank_handle* h, uint64_t* index_out);
+/* Process num_samples samples; the outputs they complete go to `out`, their number to *outputs_out.  capacity_outputs
+ * counts outputs: cells (best), elements of one row (surface).  PFB_ERR_CAPACITY sets *outputs_out to the number
+ * needed and changes no state.  mem: iq and out are both host pointers (PFB_MEM_HOST, staged as pfb_mf_process stages
+ * them; a surface walks in steps whose H rows fit the 64 MiB staging, 2^24 / H outputs each) or both device pointers
+ * (PFB_MEM_DEVICE).  Synchronous. */
+int pfb_mfbank_process(pfb_mfbank_handle* h, const void* iq, uint64_t num_samples, void* out, uint64_t capacity_outputs,
+                       uint64_t row_pitch, uint64_t* outputs_out, uint32_t mem);
+/* Same, device pointers, enqueued on the handle's stream without a host sync. */
+int pfb_mfbank_process_async(pfb_mfbank_handle* h, const void* d_iq, uint64_t num_samples, void* d_out,
+                             uint64_t capacity_outputs, uint64_t row_pitch, uint64_t* outputs_out);
+/* One .iq record from disk (format and bit width checked against the handle), streamed as pfb_mf_process_iq_file
+ * streams it; `out` is host memory.  The handle's state carries on from earlier calls: reset first for a record on
+ * its own. */
+int pfb_mfbank_process_iq_file(pfb_mfbank_handle* h, const char* path, void* out, uint64_t capacity_outputs,
+                               uint64_t row_pitch, uint64_t* outputs_out, pfb_iq_info* info_out);
+/* Name of the kernel the last process call launched ("" before the first). */
+const char* pfb_mfbank_last_kernel(const pfb_mfbank_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

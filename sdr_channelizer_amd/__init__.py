@@ -9,6 +9,8 @@ from .channelizer import Channelizer, center_frequencies, design_prototype, pinn
 from .event import DwellStats, EventPredictor, analyze_dwell, dwell_from_iq_file, fit_event, next_event  # noqa: F401
 from .matched_filter import (MatchedFilter, compress, compress_iq_file, pulse_delay_from_iq_files,  # noqa: F401
                              replica_from_pulse_train)
+from .mf_bank import (MatchedFilterBank, bank_frequencies, compress_bank,  # noqa: F401
+                      pulse_delay_and_offset_from_iq_files)
 from .pulse_source import PulseTrain, pulse_train, synth_params  # noqa: F401
 from .stft import Stft, spectrogram_from_iq_file, stft, stft_axes  # noqa: F401
 from .synthesizer import (ChannelSynthesizer, design_synthesis_taps, isolate_band, synthesis_delay,  # noqa: F401
@@ -23,4 +25,5 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "Trace", "Envelope", "envelope", "envelope_from_iq_file",
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
-           "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band"]
+           "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",
+           "MatchedFilterBank", "compress_bank", "bank_frequencies", "pulse_delay_and_offset_from_iq_files"]

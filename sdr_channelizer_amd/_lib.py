@@ -46,6 +46,7 @@ PFB_WF_COMPLEX, PFB_WF_MAGNITUDE, PFB_WF_POWER = 0, 1, 2
 PFB_WF_ROWS, PFB_WF_COLUMNS = 0, 1
 PFB_CHSYN_FFTSHIFT, PFB_CHSYN_DEROTATE = 1, 2
 PFB_CHSYN_ROUTE_AUTO, PFB_CHSYN_ROUTE_FUSED, PFB_CHSYN_ROUTE_GENERIC = 0, 1, 2
+PFB_MFBANK_BEST, PFB_MFBANK_SURFACE = 0, 1
 
 
 class PfbConfig(C.Structure):
@@ -156,6 +157,22 @@ class PfbChsynPlan(C.Structure):
                 ("carried_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64)]
 
 
+class PfbMfbankConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("replica_length", C.c_uint32), ("replica", C.POINTER(C.c_float)),
+                ("sample_format", C.c_uint32), ("bit_width", C.c_uint32), ("output", C.c_uint32), ("flags", C.c_uint32),
+                ("fft_length", C.c_uint32), ("first_bin", C.c_int32), ("num_hypotheses", C.c_uint32),
+                ("bin_step", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbMfbankPlan(C.Structure):
+    _fields_ = [("fft_length", C.c_uint32), ("block_outputs", C.c_uint32), ("num_hypotheses", C.c_uint32),
+                ("lds_bytes", C.c_uint32)]
+
+
+class PfbMfbankCell(C.Structure):
+    _fields_ = [("power", C.c_float), ("hypothesis", C.c_int32)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -253,6 +270,10 @@ EXPORTS = (
     "pfb_chsyn_sync", "pfb_chsyn_get_device", "pfb_chsyn_set_frame_index", "pfb_chsyn_get_frame_index",
     "pfb_chsyn_samples_for", "pfb_chsyn_set_weights", "pfb_chsyn_process", "pfb_chsyn_process_async",
     "pfb_chsyn_last_kernel",
+    "pfb_mfbank_describe", "pfb_mfbank_frequencies", "pfb_mfbank_create", "pfb_mfbank_destroy", "pfb_mfbank_reset",
+    "pfb_mfbank_set_stream", "pfb_mfbank_sync", "pfb_mfbank_get_device", "pfb_mfbank_outputs_for",
+    "pfb_mfbank_next_index", "pfb_mfbank_process", "pfb_mfbank_process_async", "pfb_mfbank_process_iq_file",
+    "pfb_mfbank_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -437,6 +458,21 @@ def load() -> C.CDLL:
     lib.pfb_chsyn_process_async.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
     lib.pfb_chsyn_last_kernel.argtypes = [vp]
     lib.pfb_chsyn_last_kernel.restype = C.c_char_p
+    lib.pfb_mfbank_describe.argtypes = [C.POINTER(PfbMfbankConfig), C.POINTER(PfbMfbankPlan)]
+    lib.pfb_mfbank_frequencies.argtypes = [C.POINTER(PfbMfbankConfig), C.c_double, C.POINTER(C.c_double)]
+    lib.pfb_mfbank_create.argtypes = [C.POINTER(PfbMfbankConfig), C.POINTER(vp)]
+    lib.pfb_mfbank_destroy.argtypes = [vp]
+    lib.pfb_mfbank_reset.argtypes = [vp]
+    lib.pfb_mfbank_set_stream.argtypes = [vp, vp]
+    lib.pfb_mfbank_sync.argtypes = [vp]
+    lib.pfb_mfbank_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_mfbank_outputs_for.argtypes = [vp, u64, C.POINTER(u64)]
+    lib.pfb_mfbank_next_index.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_mfbank_process.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), u32]
+    lib.pfb_mfbank_process_async.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64)]
+    lib.pfb_mfbank_process_iq_file.argtypes = [vp, C.c_char_p, vp, u64, u64, C.POINTER(u64), C.POINTER(PfbIqInfo)]
+    lib.pfb_mfbank_last_kernel.argtypes = [vp]
+    lib.pfb_mfbank_last_kernel.restype = C.c_char_p
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
