@@ -1,5 +1,7 @@
-// pfb_host.h -- host-only plumbing of pfb_api.cpp, pfb_stft_api.cpp and pfb_pdw.hip (defined in pfb_host.cpp): HIP
-// error mapping, device selection, the staged host-pointer pipeline and the .iq record reader.
+// pfb_host.h -- host-only plumbing of every unit that has a host side (pfb_api.cpp, pfb_stft_api.cpp, pfb_event.cpp and
+// the .hip units with entry points of their own; defined in pfb_host.cpp): HIP error mapping, device selection, stream
+// switch, twiddle upload, the staged host-pointer pipeline and the .iq record reader.  What only the matched filter and
+// its bank share is in pfb_ols_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

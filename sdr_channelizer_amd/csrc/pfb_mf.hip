@@ -12,10 +12,11 @@
 //
 //   pfb_mf_fused<NFFT, FMT>     NFFT in {1024, 2048, 4096} x {int8, int16, cf32}, K <= NFFT/2.  One short-lived
 //                               256-thread workgroup per block of V = NFFT - K + 1 outputs, in dispatch order:
-//     LOAD     the block's NFFT samples once, 16 bytes per lane where the span lies in this call's buffer, the carried
-//              samples from the carry buffer; samples past the call's end are zero
+//     LOAD     the block's NFFT samples once (iq_load_span, pfb_iq_span.hpp), 16 bytes per lane where the span lies in
+//              this call's buffer, the carried samples from the carry buffer; samples past the call's end are zero
 //     FORWARD  three Stockham passes of compile-time radix (16 x 8 x 8, 16 x 16 x 8, 16 x 16 x 16), each butterfly an
-//              in-register Dft<R> of pfb_cplx.hpp with one LDS exchange between passes
+//              in-register Dft<R> of pfb_cplx.hpp with one LDS exchange between passes (pfb_ols.hpp, shared with
+//              pfb_mfbank.hip)
 //     MULTIPLY by the spectrum (L2-resident) while the inverse's first pass reads its operands
 //     INVERSE  the same three passes: Dft<R> is the e^{+j} kernel, which is the FORWARD direction here (the spectrum is
 //              made for it); the e^{-j} transform back is DFT-(x) = swap(DFT+(swap(x))), re and im exchanged when the
@@ -33,33 +34,29 @@
 //
 // Blocks start where a call starts, so two cuttings of one stream round differently (they agree to the tolerance the
 // header states); the same sequence of calls gives the same bits.  No atomics anywhere.
+// Host side: the replica checks, the spectra and the stream state (carry, position, staging) are pfb_ols_host.h's,
+// shared with pfb_mfbank.hip; the route, the NFFT rule, mf_check's order, the workspace and the entry points are here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <complex>
 #include <new>
 #include <vector>
 
-#include "pfb_cplx.hpp"
-#include "pfb_host.h"
+#include "pfb_iq_span.hpp"
+#include "pfb_ols.hpp"
+#include "pfb_ols_host.h"
 
 namespace {
 
 using namespace pfb;
 
-constexpr int kThreads = 256;
-constexpr uint32_t kMaxReplica = 65536;
+constexpr int kThreads = kOlsThreads;
 constexpr uint64_t kWorkspaceCap = (uint64_t)64 << 20;  // partitioned route: bytes of spectra held at once
 constexpr uint64_t kStageBytes = (uint64_t)64 << 20;    // per side of the host staging
 
-template <int NFFT> struct MfCfg;
-template <> struct MfCfg<1024> { static constexpr int R0 = 16, R1 = 8, R2 = 8; };
-template <> struct MfCfg<2048> { static constexpr int R0 = 16, R1 = 16, R2 = 8; };
-template <> struct MfCfg<4096> { static constexpr int R0 = 16, R1 = 16, R2 = 16; };
-
 // Kernel-side view of one call.  "Stream sample s" counts from the first carried sample: s < carry_len is
-// carry[carry_cap - carry_len + s], the rest is in[s - carry_len]; local output m covers stream samples [m, m + K).
+// carry[carry_cap - carry_len + s], the rest is in[s - carry_len] (iq_load_span reads in, carry, carry_len and
+// carry_cap); local output m covers stream samples [m, m + K).
 struct MfParams {
   const void* in;       // this call's samples (device)
   const void* carry;    // carry_cap samples; the last carry_len precede in[0]
@@ -74,136 +71,27 @@ struct MfParams {
   int K, partitions, output;
 };
 
-template <int FMT>
-PFB_DEV float2 mf_fetch(const MfParams& p, long long s) {
-  const long long g = s - p.carry_len;
-  const void* b = g >= 0 ? p.in : p.carry;
-  const long long i = g >= 0 ? g : p.carry_cap + g;
-  if constexpr (FMT == PFB_FMT_INT16_IQ) {
-    const int16_t* q = static_cast<const int16_t*>(b) + 2 * i;
-    return make_float2((float)q[0], (float)q[1]);
-  } else if constexpr (FMT == PFB_FMT_INT8_IQ) {
-    const int8_t* q = static_cast<const int8_t*>(b) + 2 * i;
-    return make_float2((float)q[0], (float)q[1]);
-  } else {
-    const float* q = static_cast<const float*>(b) + 2 * i;
-    return make_float2(q[0], q[1]);
-  }
-}
-
-// blk[i] = stream sample s0 + i for i < S, zero for S <= i < NFFT (S <= 0: all zero)
-template <int NFFT, int FMT>
-PFB_DEV void mf_load_block(const MfParams& p, long long s0, int S, float2* blk) {
-  using ST = SampleT<FMT>;
-  constexpr int BPS = ST::kBytes, PER_VEC = 16 / BPS;
-  const int tid = threadIdx.x;
-  if (S < 0) S = 0;
-  for (int i = S + tid; i < NFFT; i += kThreads) blk[i] = make_float2(0.f, 0.f);
-  if (S == 0) return;
-  if (s0 < p.carry_len) {  // the block reaches into the carried samples
-    for (int i = tid; i < S; i += kThreads) blk[i] = mf_fetch<FMT>(p, s0 + i);
-    return;
-  }
-  // pfb_mf_process* admit sample-aligned pointers only: every 16-byte vector holds whole samples
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(p.in) + (uintptr_t)(s0 - p.carry_len) * BPS, a1 = a0 + (uintptr_t)S * BPS;
-  const uintptr_t v0 = (a0 + 15) & ~(uintptr_t)15, v1 = a1 & ~(uintptr_t)15;
-  int head = S, nvec = 0;  // samples before the first whole 16-byte vector, vectors
-  if (v1 > v0) { head = (int)((v0 - a0) / BPS); nvec = (int)((v1 - v0) / 16); }
-  const int tail0 = head + nvec * PER_VEC;
-  for (int i = tid; i < head; i += kThreads) blk[i] = mf_fetch<FMT>(p, s0 + i);
-  for (int i = tail0 + tid; i < S; i += kThreads) blk[i] = mf_fetch<FMT>(p, s0 + i);
-  const uint4* src = reinterpret_cast<const uint4*>(v0);
-  for (int i = tid; i < nvec; i += kThreads) {
-    const uint4 w = src[i];
-    float2* d = blk + head + i * PER_VEC;
-    float re, im;
-    if constexpr (FMT == PFB_FMT_INT16_IQ) {
-      const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { ST::cvt(u[e], re, im); d[e] = make_float2(re, im); }
-    } else if constexpr (FMT == PFB_FMT_INT8_IQ) {
-      const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        ST::cvt((uint16_t)(u[e] & 0xffffu), re, im); d[2 * e] = make_float2(re, im);
-        ST::cvt((uint16_t)(u[e] >> 16), re, im); d[2 * e + 1] = make_float2(re, im);
-      }
-    } else {
-      d[0] = make_float2(__uint_as_float(w.x), __uint_as_float(w.y));
-      d[1] = make_float2(__uint_as_float(w.z), __uint_as_float(w.w));
-    }
-  }
-}
-
-// first pass (sub-transforms of length 1, no twiddles).  MUL: the operands are src[n] * spec[n] with re and im exchanged,
-// the way into the e^{-j} transform
-template <int N, int R, bool MUL>
-PFB_DEV void mf_first_pass(const float2* src, float2* dst, const float2* __restrict__ spec) {
-  constexpr int NB = N / R;
-  for (int j = threadIdx.x; j < NB; j += kThreads) {
-    v2f x[R];
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-      const float2 v = src[j + q * NB];
-      if constexpr (MUL) {
-        const float2 h = spec[j + q * NB];
-        x[q] = swp(cmul((v2f){v.x, v.y}, h.x, h.y));
-      } else {
-        x[q] = (v2f){v.x, v.y};
-      }
-    }
-    Dft<R>::run(x);
-    float2* d = dst + j * R;
-#pragma unroll
-    for (int q = 0; q < R; ++q) d[q] = make_float2(x[q].x, x[q].y);
-  }
-}
-
-// Stockham pass of radix R after sub-transforms of length NS
-template <int N, int R, int NS>
-PFB_DEV void mf_pass(const float2* src, float2* dst, const float2* __restrict__ tw) {
-  constexpr int NB = N / R, TSTEP = N / (NS * R);
-  for (int j = threadIdx.x; j < NB; j += kThreads) {
-    const int k = j % NS;
-    v2f x[R];
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-      const float2 v = src[j + q * NB];
-      x[q] = (v2f){v.x, v.y};
-    }
-#pragma unroll
-    for (int q = 1; q < R; ++q) {
-      const float2 w = tw[q * k * TSTEP];
-      x[q] = cmul(x[q], w.x, w.y);
-    }
-    Dft<R>::run(x);
-    float2* d = dst + (j / NS) * NS * R + k;
-#pragma unroll
-    for (int q = 0; q < R; ++q) d[q * NS] = make_float2(x[q].x, x[q].y);
-  }
-}
-
 // DFT+ of a (natural order) into b; a is overwritten.  Ends behind a barrier.
 template <int NFFT>
 PFB_DEV void mf_forward(float2* a, float2* b, const float2* tw) {
-  using Cfg = MfCfg<NFFT>;
-  mf_first_pass<NFFT, Cfg::R0, false>(a, b, nullptr);
+  using Cfg = OlsPlan<NFFT>;
+  ols_first_pass<NFFT, Cfg::R0, false>(a, b, nullptr);
   __syncthreads();
-  mf_pass<NFFT, Cfg::R1, Cfg::R0>(b, a, tw);
+  ols_pass<NFFT, Cfg::R1, Cfg::R0>(b, a, tw);
   __syncthreads();
-  mf_pass<NFFT, Cfg::R2, Cfg::R0 * Cfg::R1>(a, b, tw);
+  ols_pass<NFFT, Cfg::R2, Cfg::R0 * Cfg::R1>(a, b, tw);
   __syncthreads();
 }
 
 // DFT+ of (MUL: b * spec exchanged, else b as it is) into a; b is overwritten.  Ends behind a barrier.
 template <int NFFT, bool MUL>
 PFB_DEV void mf_inverse(float2* b, float2* a, const float2* spec, const float2* tw) {
-  using Cfg = MfCfg<NFFT>;
-  mf_first_pass<NFFT, Cfg::R0, MUL>(b, a, spec);
+  using Cfg = OlsPlan<NFFT>;
+  ols_first_pass<NFFT, Cfg::R0, MUL>(b, a, spec);
   __syncthreads();
-  mf_pass<NFFT, Cfg::R1, Cfg::R0>(a, b, tw);
+  ols_pass<NFFT, Cfg::R1, Cfg::R0>(a, b, tw);
   __syncthreads();
-  mf_pass<NFFT, Cfg::R2, Cfg::R0 * Cfg::R1>(b, a, tw);
+  ols_pass<NFFT, Cfg::R2, Cfg::R0 * Cfg::R1>(b, a, tw);
   __syncthreads();
 }
 
@@ -211,10 +99,6 @@ PFB_DEV void mf_inverse(float2* b, float2* a, const float2* spec, const float2* 
 PFB_DEV float2 mf_value(const float2* y, int i) {
   const float2 v = y[i];
   return make_float2(v.y, v.x);
-}
-PFB_DEV float mf_power(const float2* y, int i) {
-  const float2 v = y[i];
-  return v.x * v.x + v.y * v.y;
 }
 
 // local outputs [m0, m0 + count) from y[0 .. count): a scalar head up to the first 16-byte boundary of the output, whole
@@ -233,15 +117,7 @@ PFB_DEV void mf_store(const MfParams& p, const float2* y, long long m0, int coun
     }
     if (tid < count - tail0) o[tail0 + tid] = mf_value(y, tail0 + tid);
   } else {
-    float* o = static_cast<float*>(p.out) + m0;
-    const int head = min((int)(((16 - reinterpret_cast<uintptr_t>(o) % 16) % 16) / 4), count);
-    const int nvec = (count - head) / 4, tail0 = head + 4 * nvec;
-    if (tid < head) o[tid] = mf_power(y, tid);
-    for (int v = tid; v < nvec; v += kThreads) {
-      const int i = head + 4 * v;
-      *reinterpret_cast<float4*>(o + i) = make_float4(mf_power(y, i), mf_power(y, i + 1), mf_power(y, i + 2), mf_power(y, i + 3));
-    }
-    if (tid < count - tail0) o[tail0 + tid] = mf_power(y, tail0 + tid);
+    ols_store_power(static_cast<float*>(p.out) + m0, y, count);
   }
 }
 
@@ -251,7 +127,7 @@ __global__ void __launch_bounds__(kThreads) pfb_mf_fused(const MfParams p) {
   __shared__ float2 buf_b[NFFT];
   const int V = NFFT - p.K + 1;
   const long long m0 = (long long)blockIdx.x * V;
-  mf_load_block<NFFT, FMT>(p, m0, (int)min((long long)NFFT, p.total - m0), buf_a);
+  iq_load_span<FMT, false, NFFT>(p, m0, (int)min((long long)NFFT, p.total - m0), buf_a);
   __syncthreads();
   mf_forward<NFFT>(buf_a, buf_b, p.tw);
   mf_inverse<NFFT, true>(buf_b, buf_a, p.spec, p.tw);
@@ -265,7 +141,7 @@ __global__ void __launch_bounds__(kThreads) pfb_mf_spectra(const MfParams p) {
   __shared__ float2 buf_a[NFFT];
   __shared__ float2 buf_b[NFFT];
   const long long s0 = (p.block0 + blockIdx.x) * (NFFT / 2);
-  mf_load_block<NFFT, FMT>(p, s0, (int)max(0ll, min((long long)NFFT, p.total - s0)), buf_a);
+  iq_load_span<FMT, false, NFFT>(p, s0, (int)max(0ll, min((long long)NFFT, p.total - s0)), buf_a);
   __syncthreads();
   mf_forward<NFFT>(buf_a, buf_b, p.tw);
   float4* dst = reinterpret_cast<float4*>(p.work + (size_t)blockIdx.x * NFFT);
@@ -348,29 +224,6 @@ const MfEntry* find_mf(int nfft, int fmt) {
 // ---------------------------------------------------------------------------------
 // host: checks, plan, spectra
 
-// in-place radix-2 DFT, kernel e^{-j 2 pi n k / n}, n a power of two; twiddles straight from cos / sin of the index
-void dft_minus(std::vector<std::complex<double>>& a) {
-  const size_t n = a.size();
-  for (size_t i = 1, j = 0; i < n; ++i) {
-    size_t bit = n >> 1;
-    for (; j & bit; bit >>= 1) j ^= bit;
-    j ^= bit;
-    if (i < j) std::swap(a[i], a[j]);
-  }
-  std::vector<std::complex<double>> w(n / 2);
-  for (size_t k = 0; k < n / 2; ++k) {
-    const double ang = -2.0 * M_PI * (double)k / (double)n;
-    w[k] = {std::cos(ang), std::sin(ang)};
-  }
-  for (size_t len = 2; len <= n; len <<= 1)
-    for (size_t i = 0; i < n; i += len)
-      for (size_t k = 0; k < len / 2; ++k) {
-        const std::complex<double> u = a[i + k], v = a[i + k + len / 2] * w[k * (n / len)];
-        a[i + k] = u + v;
-        a[i + k + len / 2] = u - v;
-      }
-}
-
 // Everything pfb_mf_describe and pfb_mf_create check before the device, in the order the header states; fills *plan,
 // and *spec (when asked for) with the float32 spectra
 int mf_check(const pfb_mf_config* cfg, pfb_mf_plan* plan, std::vector<float2>* spec) {
@@ -379,19 +232,13 @@ int mf_check(const pfb_mf_config* cfg, pfb_mf_plan* plan, std::vector<float2>* s
   if (K == 0 || cfg->output > PFB_MF_POWER || (cfg->flags & ~(uint32_t)PFB_MF_NORMALIZE) ||
       cfg->route > PFB_MF_ROUTE_PARTITIONED || !(nf == 0 || nf == 1024 || nf == 2048 || nf == 4096))
     return PFB_ERR_BAD_ARG;
-  double energy = 0.0;
-  for (uint64_t i = 0; i < 2 * (uint64_t)K; ++i) {
-    if (!std::isfinite(cfg->replica[i])) return PFB_ERR_BAD_ARG;
-    energy += (double)cfg->replica[i] * (double)cfg->replica[i];
-  }
-  const bool norm = (cfg->flags & PFB_MF_NORMALIZE) != 0;
-  if (norm && energy == 0.0) return PFB_ERR_BAD_ARG;
-  if (cfg->sample_format > PFB_FMT_CF32) return PFB_ERR_BAD_FORMAT;
-  uint32_t bw = cfg->bit_width;
-  if (cfg->sample_format == PFB_FMT_INT8_IQ && (bw < 1 || bw > 8)) return PFB_ERR_BAD_FORMAT;
-  if (cfg->sample_format == PFB_FMT_INT16_IQ && (bw < 1 || bw > 16)) return PFB_ERR_BAD_FORMAT;
-  if (cfg->sample_format == PFB_FMT_CF32) bw = 1;  // scale 1
-  if (K > kMaxReplica) return PFB_ERR_UNSUPPORTED;
+  double gain = 1.0;
+  int rc = replica_gain(cfg->replica, K, (cfg->flags & PFB_MF_NORMALIZE) != 0, &gain);
+  if (rc != PFB_OK) return rc;
+  uint32_t bw = 0;
+  rc = replica_format(cfg->sample_format, cfg->bit_width, &bw);
+  if (rc != PFB_OK) return rc;
+  if (K > kOlsMaxReplica) return PFB_ERR_UNSUPPORTED;
   const uint32_t fused_max = nf ? nf / 2 : 2048;  // the longest replica a fused kernel of the asked length takes
   if (cfg->route == PFB_MF_ROUTE_FUSED && K > fused_max) return PFB_ERR_UNSUPPORTED;
   const bool fused = cfg->route == PFB_MF_ROUTE_FUSED || (cfg->route == PFB_MF_ROUTE_AUTO && K <= fused_max);
@@ -408,47 +255,22 @@ int mf_check(const pfb_mf_config* cfg, pfb_mf_plan* plan, std::vector<float2>* s
   plan->block_outputs = fused ? N - K + 1 : B;
   plan->workspace_bytes = fused ? 0 : (kWorkspaceCap / ((uint64_t)N * sizeof(float2))) * (uint64_t)N * sizeof(float2);
   if (!spec) return PFB_OK;
-  // H_p[k] = scale * sum_{n < B} conj(r[p B + n]) e^{-j 2 pi n k / N}; fused: the one partition holds all K <= B samples
-  const double scale = (norm ? 1.0 / energy : 1.0) * std::ldexp(1.0, -((int)bw - 1)) / (double)N;
-  spec->assign((size_t)P * N, make_float2(0.f, 0.f));
-  std::vector<std::complex<double>> a(N);
-  for (uint32_t q = 0; q < P; ++q) {
-    std::fill(a.begin(), a.end(), std::complex<double>(0.0, 0.0));
-    for (uint32_t n = 0; n < B && (uint64_t)q * B + n < K; ++n) {
-      const float* r = cfg->replica + 2 * ((size_t)q * B + n);
-      a[n] = {(double)r[0], -(double)r[1]};
-    }
-    dft_minus(a);
-    for (uint32_t k = 0; k < N; ++k) {
-      const float re = (float)(a[k].real() * scale), im = (float)(a[k].imag() * scale);
-      if (!std::isfinite(re) || !std::isfinite(im)) return PFB_ERR_BAD_ARG;  // the spectrum must fit float32
-      (*spec)[(size_t)q * N + k] = make_float2(re, im);
-    }
-  }
-  return PFB_OK;
+  // H_p: partition p of B replica samples; fused: the one partition holds all K <= B samples
+  return replica_spectra(cfg->replica, K, N, B, P, gain, bw, spec);
 }
 
 }  // namespace
 
 struct pfb_mf_handle {
-  int K = 0, nfft = 0, partitions = 1, block_outputs = 0;
+  pfb::OlsStream st;  // out_elem: complex64, or float32 for power
+  int partitions = 1, block_outputs = 0;
   bool fused = true;
-  int fmt = 0, bit_width = 0, output = 0;
+  int output = 0;
   int device = 0;
-  int bps = 0;        // bytes per input sample
-  int out_elem = 8;   // complex64, or float32 for power
-  uint64_t pos = 0;   // samples since create / reset
-  float2* d_spec = nullptr;
-  float2* d_tw = nullptr;
-  void* d_carry[2] = {nullptr, nullptr};  // K - 1 raw samples each; the last min(pos, K - 1) precede the next call
-  int cur = 0;
   float2* d_work = nullptr;  // partitioned: spectra of the chunk in flight (grow-only)
   uint64_t work_slots = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_switch = nullptr;
   const MfEntry* kern = nullptr;
   const char* last_kernel = "";
-  pfb::HostStage stage;
 };
 
 namespace {
@@ -456,20 +278,9 @@ namespace {
 void free_mf(pfb_mf_handle* h) {
   if (!h) return;
   DeviceGuard g(h->device);
-  (void)hipFree(h->d_spec);
-  (void)hipFree(h->d_tw);
-  (void)hipFree(h->d_carry[0]);
-  (void)hipFree(h->d_carry[1]);
+  h->st.release();
   (void)hipFree(h->d_work);
-  h->stage.release();
-  if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
   delete h;
-}
-
-uint64_t carried(const pfb_mf_handle* h) { return std::min<uint64_t>(h->pos, (uint64_t)h->K - 1); }
-uint64_t outputs_for(const pfb_mf_handle* h, uint64_t n) {
-  const uint64_t total = carried(h) + n;
-  return total >= (uint64_t)h->K ? total - (uint64_t)h->K + 1 : 0;
 }
 
 int create_mf(const pfb_mf_config* cfg, pfb_mf_handle** out) {
@@ -481,27 +292,15 @@ int create_mf(const pfb_mf_config* cfg, pfb_mf_handle** out) {
   rc = pfb::resolve_device(cfg->device_id, &dev);
   if (rc != PFB_OK) return rc;
   pfb_mf_handle* h = new pfb_mf_handle();
-  h->K = (int)cfg->replica_length;
-  h->nfft = (int)plan.fft_length;
   h->partitions = (int)plan.partitions;
   h->block_outputs = (int)plan.block_outputs;
   h->fused = plan.route == PFB_MF_ROUTE_FUSED;
-  h->fmt = (int)cfg->sample_format;
-  h->bit_width = h->fmt == PFB_FMT_CF32 ? 1 : (int)cfg->bit_width;
   h->output = (int)cfg->output;
   h->device = dev;
-  h->bps = pfb::bytes_per_sample(h->fmt);
-  h->out_elem = h->output == PFB_MF_COMPLEX ? 8 : 4;
-  h->kern = find_mf(h->nfft, h->fmt);
+  h->st.out_elem = h->output == PFB_MF_COMPLEX ? 8 : 4;
+  h->kern = find_mf((int)plan.fft_length, (int)cfg->sample_format);
   DeviceGuard g(dev);
-  const size_t carry_bytes = (size_t)std::max(h->K - 1, 1) * h->bps, spec_bytes = spec.size() * sizeof(float2);
-  hipError_t e = hipMalloc((void**)&h->d_spec, spec_bytes);
-  if (e == hipSuccess) e = pfb::upload_twiddles((uint32_t)h->nfft, &h->d_tw);
-  if (e == hipSuccess) e = hipMalloc(&h->d_carry[0], carry_bytes);
-  if (e == hipSuccess) e = hipMalloc(&h->d_carry[1], carry_bytes);
-  if (e == hipSuccess) e = hipMemcpy(h->d_spec, spec.data(), spec_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(h->d_carry[0], 0, carry_bytes);
-  if (e == hipSuccess) e = hipMemset(h->d_carry[1], 0, carry_bytes);
+  const hipError_t e = h->st.allocate(cfg->replica_length, plan.fft_length, cfg->sample_format, cfg->bit_width, spec);
   if (e != hipSuccess) {
     rc = pfb::hip_fail(e, "pfb_mf_create allocation");
     free_mf(h);
@@ -514,69 +313,51 @@ int create_mf(const pfb_mf_config* cfg, pfb_mf_handle** out) {
 // the kernels of one call and the carry update for device-resident buffers; no host sync (a partitioned call that grows
 // the workspace waits for the device)
 int mf_enqueue(pfb_mf_handle* h, const void* d_iq, uint64_t n, void* d_out, uint64_t outputs) {
+  pfb::OlsStream& st = h->st;
   if (outputs > 0) {
     MfParams p{};
     p.in = d_iq;
-    p.carry = h->d_carry[h->cur];
+    p.carry = st.d_carry[st.cur];
     p.out = d_out;
-    p.spec = h->d_spec;
-    p.tw = h->d_tw;
-    p.carry_len = (int)carried(h);
-    p.carry_cap = h->K - 1;
-    p.total = (long long)(carried(h) + n);
+    p.spec = st.d_spec;
+    p.tw = st.d_tw;
+    p.carry_len = (int)st.carried();
+    p.carry_cap = st.K - 1;
+    p.total = (long long)(st.carried() + n);
     p.outputs = (long long)outputs;
-    p.K = h->K;
+    p.K = st.K;
     p.partitions = h->partitions;
     p.output = h->output;
     const uint64_t blocks = (outputs + (uint64_t)h->block_outputs - 1) / (uint64_t)h->block_outputs;
     if (blocks > 0x7fffffffull) return PFB_ERR_UNSUPPORTED;
     if (h->fused) {
-      h->kern->fused(p, (unsigned)blocks, h->stream);
+      h->kern->fused(p, (unsigned)blocks, st.stream);
       HIP_TRY(hipGetLastError());
       h->last_kernel = h->kern->fused_name;
     } else {
       const uint64_t extra = (uint64_t)h->partitions - 1;
-      const uint64_t max_slots = kWorkspaceCap / ((uint64_t)h->nfft * sizeof(float2));  // 2048 .. 8192, > extra
+      const uint64_t max_slots = kWorkspaceCap / ((uint64_t)st.nfft * sizeof(float2));  // 2048 .. 8192, > extra
       const uint64_t per_chunk = max_slots - extra, need = std::min(blocks, per_chunk) + extra;
       if (need > h->work_slots) {  // frees only after the device has drained: earlier calls are done with the old one
         (void)hipFree(h->d_work);
         h->d_work = nullptr;
         h->work_slots = 0;
-        HIP_TRY(hipMalloc((void**)&h->d_work, need * (uint64_t)h->nfft * sizeof(float2)));
+        HIP_TRY(hipMalloc((void**)&h->d_work, need * (uint64_t)st.nfft * sizeof(float2)));
         h->work_slots = need;
       }
       p.work = h->d_work;
       for (uint64_t i0 = 0; i0 < blocks; i0 += per_chunk) {  // stream order keeps one chunk's spectra from the next
         const uint64_t nb = std::min(per_chunk, blocks - i0);
         p.block0 = (long long)i0;
-        h->kern->spectra(p, (unsigned)(nb + extra), h->stream);
+        h->kern->spectra(p, (unsigned)(nb + extra), st.stream);
         HIP_TRY(hipGetLastError());
-        h->kern->combine(p, (unsigned)nb, h->stream);
+        h->kern->combine(p, (unsigned)nb, st.stream);
         HIP_TRY(hipGetLastError());
       }
       h->last_kernel = h->kern->partitioned_name;
     }
   }
-  if (n > 0 && h->K > 1) {  // the last K - 1 samples of [carry | in]
-    HIP_TRY(pfb::launch_update_history(h->d_carry[h->cur], d_iq, (long long)n, h->d_carry[h->cur ^ 1], h->K - 1, h->bps,
-                                       h->stream));
-    h->cur ^= 1;
-  }
-  h->pos += n;
-  return PFB_OK;
-}
-
-// what every process call checks before the device is touched; *f = the outputs it completes
-int mf_check_call(const pfb_mf_handle* h, const void* iq, uint64_t n, const void* out, uint64_t cap, uint64_t* outputs_out,
-                  bool device, uint64_t* f) {
-  if (!h || (n > 0 && !iq) || n > ((uint64_t)1 << 62) || h->pos + n < h->pos) return PFB_ERR_BAD_ARG;
-  *f = outputs_for(h, n);
-  if (outputs_out) *outputs_out = *f;
-  if (*f > cap) return PFB_ERR_CAPACITY;
-  if (*f > 0 && !out) return PFB_ERR_BAD_ARG;
-  if (device && (reinterpret_cast<uintptr_t>(iq) % (uintptr_t)h->bps || reinterpret_cast<uintptr_t>(out) % (uintptr_t)h->out_elem))
-    return PFB_ERR_BAD_ARG;
-  return PFB_OK;
+  return st.advance(d_iq, n);
 }
 
 // Host buffers (pageable or page-locked) through the staged pipeline: an output sample is a "frame", a step at most
@@ -584,12 +365,12 @@ int mf_check_call(const pfb_mf_handle* h, const void* iq, uint64_t n, const void
 int mf_host(pfb_mf_handle* h, const void* iq, uint64_t n, void* out, uint64_t limit = UINT64_MAX) {
   const uint64_t chunk = std::min<uint64_t>(limit, kStageBytes / 8);  // a step completes at most `chunk` outputs
   const pfb::StageSteps steps{
-      chunk, chunk, (size_t)h->bps, (size_t)h->out_elem,
-      [h](uint64_t m) { return outputs_for(h, m); },
+      chunk, chunk, (size_t)h->st.bps, (size_t)h->st.out_elem,
+      [h](uint64_t m) { return h->st.outputs_for(m); },
       [h](const void* d_in, uint64_t m, void* d_out, uint64_t f, int64_t, int64_t) {
         return mf_enqueue(h, d_in, m, d_out, f);
       }};
-  return pfb::stage_host(h->stage, h->stream, steps, iq, n, pfb::StageOut{out});
+  return pfb::stage_host(h->st.stage, h->st.stream, steps, iq, n, pfb::StageOut{out});
 }
 
 }  // namespace
@@ -623,7 +404,7 @@ extern "C" int pfb_mf_destroy(pfb_mf_handle* h) {
 extern "C" int pfb_mf_reset(pfb_mf_handle* h) {
   return pfb::abi_guard([&]() -> int {
     if (!h) return PFB_ERR_BAD_ARG;
-    h->pos = 0;  // nothing carried: the carry buffer is never read before it is written again
+    h->st.pos = 0;  // nothing carried: the carry buffer is never read before it is written again
     return PFB_OK;
   });
 }
@@ -631,7 +412,7 @@ extern "C" int pfb_mf_reset(pfb_mf_handle* h) {
 extern "C" int pfb_mf_set_stream(pfb_mf_handle* h, void* hip_stream) {
   return pfb::abi_guard([&]() -> int {
     if (!h) return PFB_ERR_BAD_ARG;
-    return pfb::switch_stream(h->device, &h->stream, &h->ev_switch, static_cast<hipStream_t>(hip_stream));
+    return pfb::switch_stream(h->device, &h->st.stream, &h->st.ev_switch, static_cast<hipStream_t>(hip_stream));
   });
 }
 
@@ -639,7 +420,7 @@ extern "C" int pfb_mf_sync(pfb_mf_handle* h) {
   return pfb::abi_guard([&]() -> int {
     if (!h) return PFB_ERR_BAD_ARG;
     DeviceGuard g(h->device);
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));
     return PFB_OK;
   });
 }
@@ -655,7 +436,7 @@ extern "C" int pfb_mf_get_device(const pfb_mf_handle* h, int* device_id) {
 extern "C" int pfb_mf_outputs_for(const pfb_mf_handle* h, uint64_t num_samples, uint64_t* outputs_out) {
   return pfb::abi_guard([&]() -> int {
     if (!h || !outputs_out || num_samples > ((uint64_t)1 << 62)) return PFB_ERR_BAD_ARG;
-    *outputs_out = outputs_for(h, num_samples);
+    *outputs_out = h->st.outputs_for(num_samples);
     return PFB_OK;
   });
 }
@@ -663,7 +444,7 @@ extern "C" int pfb_mf_outputs_for(const pfb_mf_handle* h, uint64_t num_samples, 
 extern "C" int pfb_mf_next_index(const pfb_mf_handle* h, uint64_t* index_out) {
   return pfb::abi_guard([&]() -> int {
     if (!h || !index_out) return PFB_ERR_BAD_ARG;
-    *index_out = h->pos - carried(h);  // = max(0, pos - K + 1): the outputs so far
+    *index_out = h->st.pos - h->st.carried();  // = max(0, pos - K + 1): the outputs so far
     return PFB_OK;
   });
 }
@@ -671,8 +452,9 @@ extern "C" int pfb_mf_next_index(const pfb_mf_handle* h, uint64_t* index_out) {
 extern "C" int pfb_mf_process_async(pfb_mf_handle* h, const void* d_iq, uint64_t num_samples, void* d_out,
                                     uint64_t capacity_outputs, uint64_t* outputs_out) {
   return pfb::abi_guard([&]() -> int {
+    if (!h) return PFB_ERR_BAD_ARG;
     uint64_t f = 0;
-    const int rc = mf_check_call(h, d_iq, num_samples, d_out, capacity_outputs, outputs_out, true, &f);
+    const int rc = h->st.check_call(d_iq, num_samples, d_out, capacity_outputs, outputs_out, true, &f);
     if (rc != PFB_OK) return rc;
     DeviceGuard g(h->device);
     return mf_enqueue(h, d_iq, num_samples, d_out, f);
@@ -682,15 +464,15 @@ extern "C" int pfb_mf_process_async(pfb_mf_handle* h, const void* d_iq, uint64_t
 extern "C" int pfb_mf_process(pfb_mf_handle* h, const void* iq, uint64_t num_samples, void* out, uint64_t capacity_outputs,
                               uint64_t* outputs_out, uint32_t mem) {
   return pfb::abi_guard([&]() -> int {
-    if (mem > PFB_MEM_DEVICE) return PFB_ERR_BAD_ARG;
+    if (mem > PFB_MEM_DEVICE || !h) return PFB_ERR_BAD_ARG;
     uint64_t f = 0;
-    int rc = mf_check_call(h, iq, num_samples, out, capacity_outputs, outputs_out, mem == PFB_MEM_DEVICE, &f);
+    int rc = h->st.check_call(iq, num_samples, out, capacity_outputs, outputs_out, mem == PFB_MEM_DEVICE, &f);
     if (rc != PFB_OK) return rc;
     DeviceGuard g(h->device);
     if (mem == PFB_MEM_HOST) return mf_host(h, iq, num_samples, out);
     rc = mf_enqueue(h, iq, num_samples, out, f);
     if (rc != PFB_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));
     return PFB_OK;
   });
 }
@@ -700,19 +482,19 @@ extern "C" int pfb_mf_process_iq_file(pfb_mf_handle* h, const char* path, void* 
   return pfb::abi_guard([&]() -> int {
     if (!h || !path) return PFB_ERR_BAD_ARG;
     pfb::Record rec;
-    const int rc = rec.open(path, h->fmt, h->bit_width);
+    const int rc = rec.open(path, h->st.fmt, h->st.bit_width);
     if (info_out) *info_out = rec.info;
     if (rc != PFB_OK) return rc;
-    const uint64_t need = outputs_for(h, rec.info.packet.numSamples);
+    const uint64_t need = h->st.outputs_for(rec.info.packet.numSamples);
     if (outputs_out) *outputs_out = need;
     if (need > capacity_outputs) return PFB_ERR_CAPACITY;
     if (need > 0 && !out) return PFB_ERR_BAD_ARG;
     // the payload in record chunks of 2^24 samples, each staged in steps of at most 2^22 (pfb_stft_process_iq_file)
     uint64_t done = 0;
     const int rc2 = rec.read((uint64_t)1 << 24, [&](const char* buf, uint64_t, uint64_t m) {
-      const uint64_t f = outputs_for(h, m);
+      const uint64_t f = h->st.outputs_for(m);
       DeviceGuard g(h->device);
-      const int r = mf_host(h, buf, m, static_cast<char*>(out) + done * (uint64_t)h->out_elem, (uint64_t)1 << 22);
+      const int r = mf_host(h, buf, m, static_cast<char*>(out) + done * (uint64_t)h->st.out_elem, (uint64_t)1 << 22);
       done += f;
       return r;
     });

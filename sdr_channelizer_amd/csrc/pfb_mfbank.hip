@@ -16,8 +16,8 @@
 //
 //   pfb_mfbank_fused<NFFT, FMT, OUT>   NFFT in {1024, 2048, 4096} x {int8, int16, cf32} x {best, surface}, K <= NFFT/2.
 //                                      One 256-thread workgroup per block of V = NFFT - K + 1 outputs:
-//     LOAD, FORWARD   as pfb_mf_fused: the block's NFFT samples once, three Stockham passes (restated here: pfb_mf.hip's
-//                     device code stays as it is)
+//     LOAD, FORWARD   as pfb_mf_fused, by the same functions (pfb_iq_span.hpp, pfb_ols.hpp): the block's NFFT samples
+//                     once, three Stockham passes
 //     KEEP      the block's spectrum X goes to registers in the operand layout of the inverse's first pass, 16 values per
 //               lane of the NFFT/16 lanes that run it: the LDS stays at two NFFT-point buffers (16 / 32 / 64 KiB), two
 //               workgroups of the 4096-point kernel share a CU where a third buffer (96 KiB) would leave one.  The
@@ -27,29 +27,28 @@
 //               exchanged, the two remaining passes, then
 //       BEST      each lane compares the powers of the cells it will store with its running (power, h) pairs: h = 0
 //                 starts them, a strictly greater power replaces, so ties keep the lowest h and a NaN displaces nothing
-//       SURFACE   row h of the block stored as pfb_mf.hip stores power
+//       SURFACE   row h of the block stored as pfb_mf.hip stores power (ols_store_power)
 //               The result alternates between the two buffers, so a hypothesis costs three barriers.
 //     STORE     BEST: the cells once, {float power; int32 h}, 16-byte vectors between a scalar head and tail
 // Blocks start where a call starts (the same sequence of calls gives the same bits); no atomics anywhere.
+// Host side: the replica checks, the spectrum and the stream state (carry, position, staging) are pfb_ols_host.h's,
+// shared with pfb_mf.hip; the hypothesis grid, bank_check's order and the entry points are here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <complex>
 #include <new>
-#include <utility>
 #include <vector>
 
-#include "pfb_cplx.hpp"
-#include "pfb_host.h"
+#include "pfb_iq_span.hpp"
+#include "pfb_ols.hpp"
+#include "pfb_ols_host.h"
 
 namespace {
 
 using namespace pfb;
 
-constexpr int kThreads = 256;
-constexpr int kR0 = 16;                                 // radix of the first pass at every length
-constexpr uint32_t kMaxReplica = 65536;                 // pfb_mf_create's limit: its code comes first for a longer one
+constexpr int kThreads = kOlsThreads;
 constexpr uint64_t kStageBytes = (uint64_t)64 << 20;    // per side of the host staging
 
 // KEEP: where a block's spectrum waits between two hypotheses, registers or a third LDS buffer (header comment).  The
@@ -60,12 +59,8 @@ constexpr uint64_t kStageBytes = (uint64_t)64 << 20;    // per side of the host 
 constexpr int kKeepInLdsLengths = PFB_MFBANK_KEEP_IN_LDS;  // the FFT lengths (powers of two) or-ed together
 template <int NFFT> constexpr bool kKeepInLds = (kKeepInLdsLengths & NFFT) != 0;
 
-template <int NFFT> struct BankCfg;
-template <> struct BankCfg<1024> { static constexpr int R1 = 8, R2 = 8; };
-template <> struct BankCfg<2048> { static constexpr int R1 = 16, R2 = 8; };
-template <> struct BankCfg<4096> { static constexpr int R1 = 16, R2 = 16; };
-
-// Kernel-side view of one call; stream samples and local outputs are counted as in pfb_mf.hip's MfParams
+// Kernel-side view of one call; stream samples and local outputs are counted as in pfb_mf.hip's MfParams, and
+// iq_load_span reads in, carry, carry_len and carry_cap
 struct BankParams {
   const void* in;        // this call's samples (device)
   const void* carry;     // carry_cap samples; the last carry_len precede in[0]
@@ -80,129 +75,6 @@ struct BankParams {
   int q0, qstep;         // q_h mod NFFT = (q0 + h * qstep) mod NFFT, both in [0, NFFT)
 };
 
-template <int FMT>
-PFB_DEV float2 bank_fetch(const BankParams& p, long long s) {
-  const long long g = s - p.carry_len;
-  const void* b = g >= 0 ? p.in : p.carry;
-  const long long i = g >= 0 ? g : p.carry_cap + g;
-  if constexpr (FMT == PFB_FMT_INT16_IQ) {
-    const int16_t* q = static_cast<const int16_t*>(b) + 2 * i;
-    return make_float2((float)q[0], (float)q[1]);
-  } else if constexpr (FMT == PFB_FMT_INT8_IQ) {
-    const int8_t* q = static_cast<const int8_t*>(b) + 2 * i;
-    return make_float2((float)q[0], (float)q[1]);
-  } else {
-    const float* q = static_cast<const float*>(b) + 2 * i;
-    return make_float2(q[0], q[1]);
-  }
-}
-
-// blk[i] = stream sample s0 + i for i < S, zero for S <= i < NFFT (S <= 0: all zero)
-template <int NFFT, int FMT>
-PFB_DEV void bank_load_block(const BankParams& p, long long s0, int S, float2* blk) {
-  using ST = SampleT<FMT>;
-  constexpr int BPS = ST::kBytes, PER_VEC = 16 / BPS;
-  const int tid = threadIdx.x;
-  if (S < 0) S = 0;
-  for (int i = S + tid; i < NFFT; i += kThreads) blk[i] = make_float2(0.f, 0.f);
-  if (S == 0) return;
-  if (s0 < p.carry_len) {  // the block reaches into the carried samples
-    for (int i = tid; i < S; i += kThreads) blk[i] = bank_fetch<FMT>(p, s0 + i);
-    return;
-  }
-  // pfb_mfbank_process* admit sample-aligned pointers only: every 16-byte vector holds whole samples
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(p.in) + (uintptr_t)(s0 - p.carry_len) * BPS, a1 = a0 + (uintptr_t)S * BPS;
-  const uintptr_t v0 = (a0 + 15) & ~(uintptr_t)15, v1 = a1 & ~(uintptr_t)15;
-  int head = S, nvec = 0;  // samples before the first whole 16-byte vector, vectors
-  if (v1 > v0) { head = (int)((v0 - a0) / BPS); nvec = (int)((v1 - v0) / 16); }
-  const int tail0 = head + nvec * PER_VEC;
-  for (int i = tid; i < head; i += kThreads) blk[i] = bank_fetch<FMT>(p, s0 + i);
-  for (int i = tail0 + tid; i < S; i += kThreads) blk[i] = bank_fetch<FMT>(p, s0 + i);
-  const uint4* src = reinterpret_cast<const uint4*>(v0);
-  for (int i = tid; i < nvec; i += kThreads) {
-    const uint4 w = src[i];
-    float2* d = blk + head + i * PER_VEC;
-    float re, im;
-    if constexpr (FMT == PFB_FMT_INT16_IQ) {
-      const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { ST::cvt(u[e], re, im); d[e] = make_float2(re, im); }
-    } else if constexpr (FMT == PFB_FMT_INT8_IQ) {
-      const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        ST::cvt((uint16_t)(u[e] & 0xffffu), re, im); d[2 * e] = make_float2(re, im);
-        ST::cvt((uint16_t)(u[e] >> 16), re, im); d[2 * e + 1] = make_float2(re, im);
-      }
-    } else {
-      d[0] = make_float2(__uint_as_float(w.x), __uint_as_float(w.y));
-      d[1] = make_float2(__uint_as_float(w.z), __uint_as_float(w.w));
-    }
-  }
-}
-
-// first pass of the forward transform (sub-transforms of length 1, no twiddles)
-template <int N>
-PFB_DEV void bank_first_pass(const float2* src, float2* dst) {
-  constexpr int NB = N / kR0;
-  for (int j = threadIdx.x; j < NB; j += kThreads) {
-    v2f x[kR0];
-#pragma unroll
-    for (int q = 0; q < kR0; ++q) {
-      const float2 v = src[j + q * NB];
-      x[q] = (v2f){v.x, v.y};
-    }
-    Dft<kR0>::run(x);
-    float2* d = dst + j * kR0;
-#pragma unroll
-    for (int q = 0; q < kR0; ++q) d[q] = make_float2(x[q].x, x[q].y);
-  }
-}
-
-// Stockham pass of radix R after sub-transforms of length NS
-template <int N, int R, int NS>
-PFB_DEV void bank_pass(const float2* src, float2* dst, const float2* __restrict__ tw) {
-  constexpr int NB = N / R, TSTEP = N / (NS * R);
-  for (int j = threadIdx.x; j < NB; j += kThreads) {
-    const int k = j % NS;
-    v2f x[R];
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-      const float2 v = src[j + q * NB];
-      x[q] = (v2f){v.x, v.y};
-    }
-#pragma unroll
-    for (int q = 1; q < R; ++q) {
-      const float2 w = tw[q * k * TSTEP];
-      x[q] = cmul(x[q], w.x, w.y);
-    }
-    Dft<R>::run(x);
-    float2* d = dst + (j / NS) * NS * R + k;
-#pragma unroll
-    for (int q = 0; q < R; ++q) d[q * NS] = make_float2(x[q].x, x[q].y);
-  }
-}
-
-// the inverse's result holds y with re and im exchanged: the power is the same
-PFB_DEV float bank_power(const float2* y, int i) {
-  const float2 v = y[i];
-  return v.x * v.x + v.y * v.y;
-}
-
-// SURFACE: o[0 .. count) = |y[0 .. count)|^2, a scalar head up to the first 16-byte boundary of o, whole 16-byte
-// vectors, a scalar tail
-PFB_DEV void bank_store_row(float* o, const float2* y, int count) {
-  const int tid = threadIdx.x;
-  const int head = min((int)(((16 - reinterpret_cast<uintptr_t>(o) % 16) % 16) / 4), count);
-  const int nvec = (count - head) / 4, tail0 = head + 4 * nvec;
-  if (tid < head) o[tid] = bank_power(y, tid);
-  for (int v = tid; v < nvec; v += kThreads) {
-    const int i = head + 4 * v;
-    *reinterpret_cast<float4*>(o + i) = make_float4(bank_power(y, i), bank_power(y, i + 1), bank_power(y, i + 2), bank_power(y, i + 3));
-  }
-  if (tid < count - tail0) o[tail0 + tid] = bank_power(y, tail0 + tid);
-}
-
 // BEST: the running (power, h) of one cell
 PFB_DEV void bank_pick(float& best, int& arg, float pw, int h) {
   if (h == 0 || pw > best) { best = pw; arg = h; }
@@ -210,7 +82,8 @@ PFB_DEV void bank_pick(float& best, int& arg, float pw, int h) {
 
 template <int NFFT, int FMT, int OUT>
 __global__ void __launch_bounds__(kThreads) pfb_mfbank_fused(const BankParams p) {
-  using Cfg = BankCfg<NFFT>;
+  using Cfg = OlsPlan<NFFT>;
+  constexpr int kR0 = Cfg::R0;              // radix of the first pass: 16 at every length
   constexpr int NB = NFFT / kR0;            // lanes of the inverse's first pass: 64 / 128 / 256
   constexpr int E = NFFT / (2 * kThreads);  // BEST: 16-byte vectors (two cells) per lane, at most
   __shared__ float2 buf_a[NFFT];
@@ -220,14 +93,14 @@ __global__ void __launch_bounds__(kThreads) pfb_mfbank_fused(const BankParams p)
   const int V = NFFT - p.K + 1;
   const long long m0 = (long long)blockIdx.x * V;
   const int count = (int)min((long long)V, p.outputs - m0);  // >= 1: the grid is ceil(outputs / V)
-  bank_load_block<NFFT, FMT>(p, m0, (int)min((long long)NFFT, p.total - m0), buf_a);
+  iq_load_span<FMT, false, NFFT>(p, m0, (int)min((long long)NFFT, p.total - m0), buf_a);
   __syncthreads();
-  bank_first_pass<NFFT>(buf_a, buf_b);
+  ols_first_pass<NFFT, kR0, false>(buf_a, buf_b, nullptr);
   __syncthreads();
-  bank_pass<NFFT, Cfg::R1, kR0>(buf_b, buf_a, p.tw);
+  ols_pass<NFFT, Cfg::R1, kR0>(buf_b, buf_a, p.tw);
   __syncthreads();
   float2* const spectrum = kKeepInLds<NFFT> ? buf_x : buf_b;
-  bank_pass<NFFT, Cfg::R2, kR0 * Cfg::R1>(buf_a, spectrum, p.tw);
+  ols_pass<NFFT, Cfg::R2, kR0 * Cfg::R1>(buf_a, spectrum, p.tw);
   __syncthreads();
   // KEEP in registers: X[tid + q NB].  No barrier before buf_a is written again: its last readers passed the one above;
   // buf_b is next written behind the first barrier of the loop
@@ -270,23 +143,23 @@ __global__ void __launch_bounds__(kThreads) pfb_mfbank_fused(const BankParams p)
       for (int k = 0; k < kR0; ++k) d[k] = make_float2(x[k].x, x[k].y);
     }
     __syncthreads();
-    bank_pass<NFFT, Cfg::R1, kR0>(ya, yb, p.tw);
+    ols_pass<NFFT, Cfg::R1, kR0>(ya, yb, p.tw);
     __syncthreads();
-    bank_pass<NFFT, Cfg::R2, kR0 * Cfg::R1>(yb, ya, p.tw);
+    ols_pass<NFFT, Cfg::R2, kR0 * Cfg::R1>(yb, ya, p.tw);
     __syncthreads();
     if constexpr (OUT == PFB_MFBANK_BEST) {
-      if (tid < head) bank_pick(best[2 * E], arg[2 * E], bank_power(ya, tid), h);
+      if (tid < head) bank_pick(best[2 * E], arg[2 * E], ols_power(ya, tid), h);
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int v = tid + e * kThreads;
         if (v < nvec) {
-          bank_pick(best[2 * e], arg[2 * e], bank_power(ya, head + 2 * v), h);
-          bank_pick(best[2 * e + 1], arg[2 * e + 1], bank_power(ya, head + 2 * v + 1), h);
+          bank_pick(best[2 * e], arg[2 * e], ols_power(ya, head + 2 * v), h);
+          bank_pick(best[2 * e + 1], arg[2 * e + 1], ols_power(ya, head + 2 * v + 1), h);
         }
       }
-      if (tid < count - tail0) bank_pick(best[2 * E + 1], arg[2 * E + 1], bank_power(ya, tail0 + tid), h);
+      if (tid < count - tail0) bank_pick(best[2 * E + 1], arg[2 * E + 1], ols_power(ya, tail0 + tid), h);
     } else {
-      bank_store_row(static_cast<float*>(p.out) + (long long)h * p.row_pitch + m0, ya, count);
+      ols_store_power(static_cast<float*>(p.out) + (long long)h * p.row_pitch + m0, ya, count);
     }
     // the next hypothesis ends in the other buffer: what is read above is written again only behind its first barrier
     float2* t = ya; ya = yb; yb = t;
@@ -334,29 +207,6 @@ const BankEntry* find_bank(int nfft, int fmt, int output) {
 // ---------------------------------------------------------------------------------
 // host: checks, plan, spectrum
 
-// in-place radix-2 DFT, kernel e^{-j 2 pi n k / n}, n a power of two; twiddles straight from cos / sin of the index
-void dft_minus(std::vector<std::complex<double>>& a) {
-  const size_t n = a.size();
-  for (size_t i = 1, j = 0; i < n; ++i) {
-    size_t bit = n >> 1;
-    for (; j & bit; bit >>= 1) j ^= bit;
-    j ^= bit;
-    if (i < j) std::swap(a[i], a[j]);
-  }
-  std::vector<std::complex<double>> w(n / 2);
-  for (size_t k = 0; k < n / 2; ++k) {
-    const double ang = -2.0 * M_PI * (double)k / (double)n;
-    w[k] = {std::cos(ang), std::sin(ang)};
-  }
-  for (size_t len = 2; len <= n; len <<= 1)
-    for (size_t i = 0; i < n; i += len)
-      for (size_t k = 0; k < len / 2; ++k) {
-        const std::complex<double> u = a[i + k], v = a[i + k + len / 2] * w[k * (n / len)];
-        a[i + k] = u + v;
-        a[i + k + len / 2] = u - v;
-      }
-}
-
 // the hypothesis grid alone: what pfb_mfbank_frequencies needs of a config; *nfft_out = the FFT length it counts bins of
 bool bank_grid_ok(const pfb_mfbank_config* cfg, uint32_t* nfft_out) {
   const uint32_t nf = cfg->fft_length;
@@ -375,58 +225,33 @@ int bank_check(const pfb_mfbank_config* cfg, pfb_mfbank_plan* plan, std::vector<
   uint32_t N = 0;
   if (K == 0 || cfg->output > PFB_MFBANK_SURFACE || (cfg->flags & ~(uint32_t)PFB_MF_NORMALIZE) || !bank_grid_ok(cfg, &N))
     return PFB_ERR_BAD_ARG;
-  double energy = 0.0;
-  for (uint64_t i = 0; i < 2 * (uint64_t)K; ++i) {
-    if (!std::isfinite(cfg->replica[i])) return PFB_ERR_BAD_ARG;
-    energy += (double)cfg->replica[i] * (double)cfg->replica[i];
-  }
-  const bool norm = (cfg->flags & PFB_MF_NORMALIZE) != 0;
-  if (norm && energy == 0.0) return PFB_ERR_BAD_ARG;
-  if (cfg->sample_format > PFB_FMT_CF32) return PFB_ERR_BAD_FORMAT;
-  uint32_t bw = cfg->bit_width;
-  if (cfg->sample_format == PFB_FMT_INT8_IQ && (bw < 1 || bw > 8)) return PFB_ERR_BAD_FORMAT;
-  if (cfg->sample_format == PFB_FMT_INT16_IQ && (bw < 1 || bw > 16)) return PFB_ERR_BAD_FORMAT;
-  if (cfg->sample_format == PFB_FMT_CF32) bw = 1;  // scale 1
-  if (K > kMaxReplica || K > N / 2) return PFB_ERR_UNSUPPORTED;  // the fused route only
+  double gain = 1.0;
+  int rc = replica_gain(cfg->replica, K, (cfg->flags & PFB_MF_NORMALIZE) != 0, &gain);
+  if (rc != PFB_OK) return rc;
+  uint32_t bw = 0;
+  rc = replica_format(cfg->sample_format, cfg->bit_width, &bw);
+  if (rc != PFB_OK) return rc;
+  if (K > kOlsMaxReplica || K > N / 2) return PFB_ERR_UNSUPPORTED;  // the fused route only
   plan->fft_length = N;
   plan->block_outputs = N - K + 1;
   plan->num_hypotheses = cfg->num_hypotheses;
   const bool keep_lds = N == 1024 ? kKeepInLds<1024> : N == 2048 ? kKeepInLds<2048> : kKeepInLds<4096>;
   plan->lds_bytes = (keep_lds ? 3 : 2) * N * (uint32_t)sizeof(float2);
   if (!spec) return PFB_OK;
-  // R[k] = scale * sum_{n < K} conj(r[n]) e^{-j 2 pi n k / N}: pfb_mf.hip's one partition
-  const double scale = (norm ? 1.0 / energy : 1.0) * std::ldexp(1.0, -((int)bw - 1)) / (double)N;
-  std::vector<std::complex<double>> a(N, std::complex<double>(0.0, 0.0));
-  for (uint32_t n = 0; n < K; ++n) a[n] = {(double)cfg->replica[2 * n], -(double)cfg->replica[2 * n + 1]};
-  dft_minus(a);
-  spec->assign(N, make_float2(0.f, 0.f));
-  for (uint32_t k = 0; k < N; ++k) {
-    const float re = (float)(a[k].real() * scale), im = (float)(a[k].imag() * scale);
-    if (!std::isfinite(re) || !std::isfinite(im)) return PFB_ERR_BAD_ARG;  // the spectrum must fit float32
-    (*spec)[k] = make_float2(re, im);
-  }
-  return PFB_OK;
+  // R[k] = scale * sum_{n < K} conj(r[n]) e^{-j 2 pi n k / N}: one partition of K samples
+  return replica_spectra(cfg->replica, K, N, K, 1, gain, bw, spec);
 }
 
 }  // namespace
 
 struct pfb_mfbank_handle {
-  int K = 0, nfft = 0, block_outputs = 0, H = 0;
+  pfb::OlsStream st;  // out_elem: a cell, or float32 for the surface
+  int block_outputs = 0, H = 0;
   int q0 = 0, qstep = 0;  // mod nfft
-  int fmt = 0, bit_width = 0, output = 0;
+  int output = 0;
   int device = 0;
-  int bps = 0;        // bytes per input sample
-  int out_elem = 8;   // a cell, or float32 for the surface
-  uint64_t pos = 0;   // samples since create / reset
-  float2* d_spec = nullptr;
-  float2* d_tw = nullptr;
-  void* d_carry[2] = {nullptr, nullptr};  // K - 1 raw samples each; the last min(pos, K - 1) precede the next call
-  int cur = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_switch = nullptr;
   const BankEntry* kern = nullptr;
   const char* last_kernel = "";
-  pfb::HostStage stage;
 };
 
 namespace {
@@ -434,19 +259,8 @@ namespace {
 void free_bank(pfb_mfbank_handle* h) {
   if (!h) return;
   DeviceGuard g(h->device);
-  (void)hipFree(h->d_spec);
-  (void)hipFree(h->d_tw);
-  (void)hipFree(h->d_carry[0]);
-  (void)hipFree(h->d_carry[1]);
-  h->stage.release();
-  if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
+  h->st.release();
   delete h;
-}
-
-uint64_t carried(const pfb_mfbank_handle* h) { return std::min<uint64_t>(h->pos, (uint64_t)h->K - 1); }
-uint64_t outputs_for(const pfb_mfbank_handle* h, uint64_t n) {
-  const uint64_t total = carried(h) + n;
-  return total >= (uint64_t)h->K ? total - (uint64_t)h->K + 1 : 0;
 }
 
 int create_bank(const pfb_mfbank_config* cfg, pfb_mfbank_handle** out) {
@@ -459,28 +273,16 @@ int create_bank(const pfb_mfbank_config* cfg, pfb_mfbank_handle** out) {
   if (rc != PFB_OK) return rc;
   pfb_mfbank_handle* h = new pfb_mfbank_handle();
   const long long N = (long long)plan.fft_length;
-  h->K = (int)cfg->replica_length;
-  h->nfft = (int)N;
   h->block_outputs = (int)plan.block_outputs;
   h->H = (int)cfg->num_hypotheses;
   h->q0 = (int)((((long long)cfg->first_bin * (long long)cfg->bin_step) % N + N) % N);
   h->qstep = (int)((long long)cfg->bin_step % N);
-  h->fmt = (int)cfg->sample_format;
-  h->bit_width = h->fmt == PFB_FMT_CF32 ? 1 : (int)cfg->bit_width;
   h->output = (int)cfg->output;
   h->device = dev;
-  h->bps = pfb::bytes_per_sample(h->fmt);
-  h->out_elem = h->output == PFB_MFBANK_BEST ? 8 : 4;
-  h->kern = find_bank(h->nfft, h->fmt, h->output);
+  h->st.out_elem = h->output == PFB_MFBANK_BEST ? 8 : 4;
+  h->kern = find_bank((int)N, (int)cfg->sample_format, h->output);
   DeviceGuard g(dev);
-  const size_t carry_bytes = (size_t)std::max(h->K - 1, 1) * h->bps, spec_bytes = spec.size() * sizeof(float2);
-  hipError_t e = hipMalloc((void**)&h->d_spec, spec_bytes);
-  if (e == hipSuccess) e = pfb::upload_twiddles((uint32_t)h->nfft, &h->d_tw);
-  if (e == hipSuccess) e = hipMalloc(&h->d_carry[0], carry_bytes);
-  if (e == hipSuccess) e = hipMalloc(&h->d_carry[1], carry_bytes);
-  if (e == hipSuccess) e = hipMemcpy(h->d_spec, spec.data(), spec_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(h->d_carry[0], 0, carry_bytes);
-  if (e == hipSuccess) e = hipMemset(h->d_carry[1], 0, carry_bytes);
+  const hipError_t e = h->st.allocate(cfg->replica_length, plan.fft_length, cfg->sample_format, cfg->bit_width, spec);
   if (e != hipSuccess) {
     rc = pfb::hip_fail(e, "pfb_mfbank_create allocation");
     free_bank(h);
@@ -492,48 +294,39 @@ int create_bank(const pfb_mfbank_config* cfg, pfb_mfbank_handle** out) {
 
 // the kernel of one call and the carry update for device-resident buffers; no host sync
 int bank_enqueue(pfb_mfbank_handle* h, const void* d_iq, uint64_t n, void* d_out, uint64_t outputs, uint64_t row_pitch) {
+  pfb::OlsStream& st = h->st;
   if (outputs > 0) {
     BankParams p{};
     p.in = d_iq;
-    p.carry = h->d_carry[h->cur];
+    p.carry = st.d_carry[st.cur];
     p.out = d_out;
-    p.spec = h->d_spec;
-    p.tw = h->d_tw;
-    p.total = (long long)(carried(h) + n);
+    p.spec = st.d_spec;
+    p.tw = st.d_tw;
+    p.total = (long long)(st.carried() + n);
     p.outputs = (long long)outputs;
     p.row_pitch = (long long)row_pitch;
-    p.carry_len = (int)carried(h);
-    p.carry_cap = h->K - 1;
-    p.K = h->K;
+    p.carry_len = (int)st.carried();
+    p.carry_cap = st.K - 1;
+    p.K = st.K;
     p.H = h->H;
     p.q0 = h->q0;
     p.qstep = h->qstep;
     const uint64_t blocks = (outputs + (uint64_t)h->block_outputs - 1) / (uint64_t)h->block_outputs;
     if (blocks > 0x7fffffffull) return PFB_ERR_UNSUPPORTED;
-    h->kern->launch(p, (unsigned)blocks, h->stream);
+    h->kern->launch(p, (unsigned)blocks, st.stream);
     HIP_TRY(hipGetLastError());
     h->last_kernel = h->kern->name;
   }
-  if (n > 0 && h->K > 1) {  // the last K - 1 samples of [carry | in]
-    HIP_TRY(pfb::launch_update_history(h->d_carry[h->cur], d_iq, (long long)n, h->d_carry[h->cur ^ 1], h->K - 1, h->bps,
-                                       h->stream));
-    h->cur ^= 1;
-  }
-  h->pos += n;
-  return PFB_OK;
+  return st.advance(d_iq, n);
 }
 
 // what every process call checks before the device is touched; *f = the outputs it completes
 int bank_check_call(const pfb_mfbank_handle* h, const void* iq, uint64_t n, const void* out, uint64_t cap, uint64_t row_pitch,
                     uint64_t* outputs_out, bool device, uint64_t* f) {
-  if (!h || (n > 0 && !iq) || n > ((uint64_t)1 << 62) || h->pos + n < h->pos) return PFB_ERR_BAD_ARG;
-  *f = outputs_for(h, n);
-  if (outputs_out) *outputs_out = *f;
-  if (*f > cap) return PFB_ERR_CAPACITY;
-  if (*f > 0 && !out) return PFB_ERR_BAD_ARG;
+  if (!h) return PFB_ERR_BAD_ARG;
+  const int rc = h->st.check_call(iq, n, out, cap, outputs_out, device, f);
+  if (rc != PFB_OK) return rc;
   if (h->output == PFB_MFBANK_SURFACE && (row_pitch < *f || row_pitch > ((uint64_t)1 << 40))) return PFB_ERR_BAD_ARG;
-  if (device && (reinterpret_cast<uintptr_t>(iq) % (uintptr_t)h->bps || reinterpret_cast<uintptr_t>(out) % (uintptr_t)h->out_elem))
-    return PFB_ERR_BAD_ARG;
   return PFB_OK;
 }
 
@@ -546,8 +339,8 @@ int bank_host(pfb_mfbank_handle* h, const void* iq, uint64_t n, void* out, uint6
   const size_t frame = surface ? (size_t)h->H * 4 : 8;
   const uint64_t chunk = std::min<uint64_t>(limit, kStageBytes / frame);  // a step completes at most `chunk` outputs
   const pfb::StageSteps steps{
-      chunk, chunk, (size_t)h->bps, frame,
-      [h](uint64_t m) { return outputs_for(h, m); },
+      chunk, chunk, (size_t)h->st.bps, frame,
+      [h](uint64_t m) { return h->st.outputs_for(m); },
       [h](const void* d_in, uint64_t m, void* d_out, uint64_t f, int64_t ld, int64_t) {
         return bank_enqueue(h, d_in, m, d_out, f, (uint64_t)ld);
       }};
@@ -559,7 +352,7 @@ int bank_host(pfb_mfbank_handle* h, const void* iq, uint64_t n, void* out, uint6
   } else {
     dst.row0 = row0;
   }
-  return pfb::stage_host(h->stage, h->stream, steps, iq, n, dst);
+  return pfb::stage_host(h->st.stage, h->st.stream, steps, iq, n, dst);
 }
 
 }  // namespace
@@ -604,7 +397,7 @@ extern "C" int pfb_mfbank_destroy(pfb_mfbank_handle* h) {
 extern "C" int pfb_mfbank_reset(pfb_mfbank_handle* h) {
   return pfb::abi_guard([&]() -> int {
     if (!h) return PFB_ERR_BAD_ARG;
-    h->pos = 0;  // nothing carried: the carry buffer is never read before it is written again
+    h->st.pos = 0;  // nothing carried: the carry buffer is never read before it is written again
     return PFB_OK;
   });
 }
@@ -612,7 +405,7 @@ extern "C" int pfb_mfbank_reset(pfb_mfbank_handle* h) {
 extern "C" int pfb_mfbank_set_stream(pfb_mfbank_handle* h, void* hip_stream) {
   return pfb::abi_guard([&]() -> int {
     if (!h) return PFB_ERR_BAD_ARG;
-    return pfb::switch_stream(h->device, &h->stream, &h->ev_switch, static_cast<hipStream_t>(hip_stream));
+    return pfb::switch_stream(h->device, &h->st.stream, &h->st.ev_switch, static_cast<hipStream_t>(hip_stream));
   });
 }
 
@@ -620,7 +413,7 @@ extern "C" int pfb_mfbank_sync(pfb_mfbank_handle* h) {
   return pfb::abi_guard([&]() -> int {
     if (!h) return PFB_ERR_BAD_ARG;
     DeviceGuard g(h->device);
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));
     return PFB_OK;
   });
 }
@@ -636,7 +429,7 @@ extern "C" int pfb_mfbank_get_device(const pfb_mfbank_handle* h, int* device_id)
 extern "C" int pfb_mfbank_outputs_for(const pfb_mfbank_handle* h, uint64_t num_samples, uint64_t* outputs_out) {
   return pfb::abi_guard([&]() -> int {
     if (!h || !outputs_out || num_samples > ((uint64_t)1 << 62)) return PFB_ERR_BAD_ARG;
-    *outputs_out = outputs_for(h, num_samples);
+    *outputs_out = h->st.outputs_for(num_samples);
     return PFB_OK;
   });
 }
@@ -644,7 +437,7 @@ extern "C" int pfb_mfbank_outputs_for(const pfb_mfbank_handle* h, uint64_t num_s
 extern "C" int pfb_mfbank_next_index(const pfb_mfbank_handle* h, uint64_t* index_out) {
   return pfb::abi_guard([&]() -> int {
     if (!h || !index_out) return PFB_ERR_BAD_ARG;
-    *index_out = h->pos - carried(h);  // = max(0, pos - K + 1): the outputs so far
+    *index_out = h->st.pos - h->st.carried();  // = max(0, pos - K + 1): the outputs so far
     return PFB_OK;
   });
 }
@@ -671,7 +464,7 @@ extern "C" int pfb_mfbank_process(pfb_mfbank_handle* h, const void* iq, uint64_t
     if (mem == PFB_MEM_HOST) return bank_host(h, iq, num_samples, out, row_pitch, 0);
     rc = bank_enqueue(h, iq, num_samples, out, f, row_pitch);
     if (rc != PFB_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->st.stream));
     return PFB_OK;
   });
 }
@@ -681,10 +474,10 @@ extern "C" int pfb_mfbank_process_iq_file(pfb_mfbank_handle* h, const char* path
   return pfb::abi_guard([&]() -> int {
     if (!h || !path) return PFB_ERR_BAD_ARG;
     pfb::Record rec;
-    const int rc = rec.open(path, h->fmt, h->bit_width);
+    const int rc = rec.open(path, h->st.fmt, h->st.bit_width);
     if (info_out) *info_out = rec.info;
     if (rc != PFB_OK) return rc;
-    const uint64_t need = outputs_for(h, rec.info.packet.numSamples);
+    const uint64_t need = h->st.outputs_for(rec.info.packet.numSamples);
     if (outputs_out) *outputs_out = need;
     if (need > capacity_outputs) return PFB_ERR_CAPACITY;
     if (need > 0 && !out) return PFB_ERR_BAD_ARG;
@@ -692,7 +485,7 @@ extern "C" int pfb_mfbank_process_iq_file(pfb_mfbank_handle* h, const char* path
     // the payload in record chunks of 2^24 samples, each staged in steps of at most 2^22 (pfb_mf_process_iq_file)
     uint64_t done = 0;
     const int rc2 = rec.read((uint64_t)1 << 24, [&](const char* buf, uint64_t, uint64_t m) {
-      const uint64_t f = outputs_for(h, m);
+      const uint64_t f = h->st.outputs_for(m);
       DeviceGuard g(h->device);
       const int r = bank_host(h, buf, m, out, row_pitch, done, (uint64_t)1 << 22);
       done += f;

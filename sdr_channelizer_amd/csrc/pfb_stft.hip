@@ -6,8 +6,8 @@
 //                               generic kernel uses (pfb_generic_fft.hpp), a plain DFT otherwise
 //
 // Fused kernel: short-lived 256-thread workgroups in dispatch order, workgroup b covering frames [b T, b T + T).
-//   LOAD   the tile's input span, (T-1) H + L samples, once: 16 bytes per lane where the span lies in this call's
-//          buffer, converted to float and kept in LDS -- overlapping frames read their shared samples from LDS, not
+//   LOAD   the tile's input span, (T-1) H + L samples, once (pfb_iq_span.hpp): 16 bytes per lane where the span lies in
+//          this call's buffer, converted to float and kept in LDS -- overlapping frames read their shared samples from LDS, not
 //          from HBM.
 //   FFT    Stockham passes of compile-time radix (R0 x R1 [x R2]), each butterfly an in-register Dft<R> of
 //          pfb_cplx.hpp with one LDS exchange between passes.  The first pass reads the span, multiplies by the window
@@ -19,6 +19,7 @@
 // LDS: two T x nfft complex buffers (the span, at most T L <= T nfft samples, lives in the first), 32-36 KiB.
 #include "pfb_cplx.hpp"
 #include "pfb_generic_fft.hpp"
+#include "pfb_iq_span.hpp"
 
 namespace pfb {
 
@@ -33,78 +34,7 @@ template <> struct StftCfg<768> { static constexpr int R0 = 12, R1 = 8, R2 = 8, 
 template <> struct StftCfg<1024> { static constexpr int R0 = 16, R1 = 8, R2 = 8, T = 2; };
 template <> struct StftCfg<2048> { static constexpr int R0 = 16, R1 = 16, R2 = 8, T = 1; };
 
-constexpr int kStftThreads = 256;
-
-// stream sample s, components read one by one
-template <int FMT>
-PFB_DEV float2 stft_fetch(const StftParams& p, long long s) {
-  const long long g = s - p.carry_len;
-  const void* b = g >= 0 ? p.in : p.carry;
-  const long long i = g >= 0 ? g : p.carry_cap + g;
-  if constexpr (FMT == PFB_FMT_INT16_IQ) {
-    const int16_t* q = static_cast<const int16_t*>(b) + 2 * i;
-    return make_float2((float)q[0], (float)q[1]);
-  } else if constexpr (FMT == PFB_FMT_INT8_IQ) {
-    const int8_t* q = static_cast<const int8_t*>(b) + 2 * i;
-    return make_float2((float)q[0], (float)q[1]);
-  } else {
-    const float* q = static_cast<const float*>(b) + 2 * i;
-    return make_float2(q[0], q[1]);
-  }
-}
-
-PFB_DEV float2 swapped(float re, float im) { return make_float2(im, re); }
-
-// span[i] = swap(stream sample s0 + i), i < S
-template <int FMT>
-PFB_DEV void stft_load_span(const StftParams& p, long long s0, int S, float2* span) {
-  using ST = SampleT<FMT>;
-  constexpr int BPS = ST::kBytes, PER_VEC = 16 / BPS;
-  const int tid = threadIdx.x;
-  // pfb_stft_process* admit sample-aligned pointers only: every 16-byte vector holds whole samples
-  const uintptr_t base = reinterpret_cast<uintptr_t>(p.in);
-  if (s0 < p.carry_len) {  // the span reaches into the carried samples
-    for (int i = tid; i < S; i += kStftThreads) {
-      const float2 v = stft_fetch<FMT>(p, s0 + i);
-      span[i] = swapped(v.x, v.y);
-    }
-    return;
-  }
-  const uintptr_t a0 = base + (uintptr_t)(s0 - p.carry_len) * BPS, a1 = a0 + (uintptr_t)S * BPS;
-  const uintptr_t v0 = (a0 + 15) & ~(uintptr_t)15, v1 = a1 & ~(uintptr_t)15;
-  int head = S, nvec = 0;  // samples before the first whole 16-byte vector, vectors
-  if (v1 > v0) { head = (int)((v0 - a0) / BPS); nvec = (int)((v1 - v0) / 16); }
-  const int tail0 = head + nvec * PER_VEC;
-  for (int i = tid; i < head; i += kStftThreads) {
-    const float2 v = stft_fetch<FMT>(p, s0 + i);
-    span[i] = swapped(v.x, v.y);
-  }
-  for (int i = tail0 + tid; i < S; i += kStftThreads) {
-    const float2 v = stft_fetch<FMT>(p, s0 + i);
-    span[i] = swapped(v.x, v.y);
-  }
-  const uint4* src = reinterpret_cast<const uint4*>(v0);
-  for (int i = tid; i < nvec; i += kStftThreads) {
-    const uint4 w = src[i];
-    float2* d = span + head + i * PER_VEC;
-    float re, im;
-    if constexpr (FMT == PFB_FMT_INT16_IQ) {
-      const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { ST::cvt(u[e], re, im); d[e] = swapped(re, im); }
-    } else if constexpr (FMT == PFB_FMT_INT8_IQ) {
-      const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        ST::cvt((uint16_t)(u[e] & 0xffffu), re, im); d[2 * e] = swapped(re, im);
-        ST::cvt((uint16_t)(u[e] >> 16), re, im); d[2 * e + 1] = swapped(re, im);
-      }
-    } else {
-      d[0] = swapped(__uint_as_float(w.x), __uint_as_float(w.y));
-      d[1] = swapped(__uint_as_float(w.z), __uint_as_float(w.w));
-    }
-  }
-}
+constexpr int kStftThreads = kSpanThreads;
 
 // first pass (sub-transforms of length 1, no twiddles): windowed, zero-padded frame t read from the span
 template <int N, int R>
@@ -213,7 +143,7 @@ __global__ void __launch_bounds__(kStftThreads) pfb_stft_fused(const StftParams 
   __shared__ float2 buf_b[T * NFFT];
   const long long f0 = (long long)blockIdx.x * T;
   const int frames = (int)min((long long)T, p.frames - f0);
-  stft_load_span<FMT>(p, f0 * p.H, (frames - 1) * p.H + p.L, buf_a);
+  iq_load_span<FMT, true>(p, f0 * p.H, (frames - 1) * p.H + p.L, buf_a);  // re and im exchanged
   __syncthreads();
   if constexpr (LOADSTORE) {
     stft_store<NFFT>(p, buf_a, f0, frames);
@@ -245,9 +175,9 @@ hipError_t launch_stft_fused(const StftParams& p, hipStream_t s) {
 // generic kernel: tile frames per workgroup, sm holds 2 x tile x nfft complex
 
 PFB_DEV float2 stft_fetch_rt(const StftParams& p, long long s) {
-  if (p.fmt == PFB_FMT_INT16_IQ) return stft_fetch<PFB_FMT_INT16_IQ>(p, s);
-  if (p.fmt == PFB_FMT_INT8_IQ) return stft_fetch<PFB_FMT_INT8_IQ>(p, s);
-  return stft_fetch<PFB_FMT_CF32>(p, s);
+  if (p.fmt == PFB_FMT_INT16_IQ) return iq_fetch<PFB_FMT_INT16_IQ>(p, s);
+  if (p.fmt == PFB_FMT_INT8_IQ) return iq_fetch<PFB_FMT_INT8_IQ>(p, s);
+  return iq_fetch<PFB_FMT_CF32>(p, s);
 }
 
 __global__ void __launch_bounds__(256) pfb_stft_generic_kernel(const StftParams p, int tile, GenericPlan plan) {

@@ -255,3 +255,10 @@ def test_mf_entry_points_sit_under_the_abi_guard():
     assert src.count('extern "C"') == len(found) + 1
     from sdr_channelizer_amd import build
     assert "pfb_mf.hip" in build.SOURCES
+    # the device is resolved after every argument check: NO_DEVICE comes last; the allocations are the shared ones
+    create = src[src.index("int create_mf("):]
+    create = create[: create.index("\n}\n")]
+    assert create.index("mf_check(cfg") < create.index("resolve_device") < create.index("st.allocate(")
+    shared = open(os.path.join(ROOT, "sdr_channelizer_amd", "csrc", "pfb_ols_host.cpp")).read()
+    allocate = shared[shared.index("hipError_t OlsStream::allocate("):]
+    assert "hipMalloc" in allocate[: allocate.index("\n}\n")] and "hipMalloc" not in create

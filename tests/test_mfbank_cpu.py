@@ -253,7 +253,11 @@ def test_mfbank_entry_points_sit_under_the_abi_guard():
     assert src.count('extern "C"') == len(found) + 1
     from sdr_channelizer_amd import build
     assert "pfb_mfbank.hip" in build.SOURCES
-    # the device is resolved after every argument check: NO_DEVICE comes last
+    # the device is resolved after every argument check: NO_DEVICE comes last; the allocations are the shared ones
     create = src[src.index("int create_bank("):]
-    assert create.index("bank_check(cfg") < create.index("resolve_device") < create.index("hipMalloc")
+    create = create[: create.index("\n}\n")]
+    assert create.index("bank_check(cfg") < create.index("resolve_device") < create.index("st.allocate(")
+    shared = open(os.path.join(ROOT, "sdr_channelizer_amd", "csrc", "pfb_ols_host.cpp")).read()
+    allocate = shared[shared.index("hipError_t OlsStream::allocate("):]
+    assert "hipMalloc" in allocate[: allocate.index("\n}\n")] and "hipMalloc" not in create
     assert "atomic" not in src.split("#include", 1)[1]
