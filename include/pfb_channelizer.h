@@ -1098,6 +1098,150 @@ int pfb_mfbank_process_iq_file(pfb_mfbank_handle* h, const char* path, void* out
 /* Name of the kernel the last process call launched ("" before the first). */
 const char* pfb_mfbank_last_kernel(const pfb_mfbank_handle* h);
 
+
+/* ---- CFAR detector: pulse lists from a compressed stream --------------------------------------
+ * The matched filter and its bank leave a stream of powers on the device; this unit turns it into one record per
+ * pulse.  A constant-false-alarm-rate detector estimates the noise around each cell from training cells on both sides,
+ * scales it by a factor chosen for a false-alarm probability, joins the crossings into runs and reports each run's peak.
+ * This comment is the definition: the device code (csrc/pfb_cfar.hip) and the tests' restatement (tests/cfar_ref.py)
+ * are each written from it.
+ *
+ * Input: cells with the global index i = 0, 1, ... since create or reset, of one of two kinds
+ *   PFB_CFAR_POWER      float32 p[i], what PFB_MF_POWER writes; hyp[i] = -1
+ *   PFB_CFAR_BANK_CELL  pfb_mfbank_cell, what PFB_MFBANK_BEST writes: p[i] = cell.power, hyp[i] = cell.hypothesis
+ * Parameters: block length C (a power of two, 4 .. 1024), guard blocks G (0 .. 64), training blocks per side T
+ * (1 .. 32), method (CA, GO, SO), factor alpha (float32, finite, > 0), min_power (float32, >= 0), merge_gap g
+ * (0 .. 2^20 cells).
+ *
+ * Blocks are aligned to the global index: block b holds cells bC .. bC+C-1.  That alignment makes every figure below
+ * independent of how the stream is cut into calls.
+ *
+ * Block sum S[b], float32: the balanced binary tree over the block's C cells in index order -- level 0 adds cells 2j
+ * and 2j+1, level 1 adds those sums pairwise, and so on; every node is one float32 addition.  (A lane's
+ * (a0+a1)+(a2+a3) followed by xor-butterfly shuffles 1, 2, 4, ... is this sum: float addition is commutative, so
+ * butterfly and tree agree bit for bit, and with additions only no FMA can arise.)  A block takes part in training
+ * only when all its C cells exist ("complete").
+ *
+ * Noise of block b: the lead set is the blocks b-G-T .. b-G-1 that are >= 0 (nL of them), the lag set the blocks
+ * b+G+1 .. b+G+T that are complete (nR).  sumL and sumR are float64 sums of the float32 S[.], sequential in ascending
+ * block index.
+ *   CA  noise = (float)((sumL + sumR) / ((nL + nR) * C))
+ *   GO  noise = (float)max(sumL / (nL * C), sumR / (nR * C))       SO: the same with min
+ * In GO and SO an empty side is left out, and a NaN on either side gives NaN.  All divisions are float64, with one
+ * rounding to float32 at the end.  With both sets empty the block has no noise: none of its cells is ever over, and
+ * they are counted in pfb_cfar_stats.cells_without_noise.
+ *
+ * Decision: over[i] = (p[i] > alpha * noise) && (p[i] > min_power), the product one float32 multiply.  A NaN on either
+ * side of a comparison therefore never detects; an Inf cell is over (against a finite threshold) and blinds the blocks
+ * that train on it.  That is IEEE behaviour, nothing is special-cased.
+ *
+ * When a block is decided: while streaming, block b is decided once block b+G+T is complete (blocks near the stream
+ * start have a short or empty lead set).  pfb_cfar_flush ends the stream: every remaining block, a final partial one
+ * included, is decided with the complete training blocks that exist; after it the handle takes cells only after
+ * pfb_cfar_reset (PFB_ERR_BAD_ARG before).  Block b's decision depends only on the number of complete blocks at that
+ * time, so without a flush it is a function of the total cell count alone.
+ *
+ * Detections: over cells whose gaps are <= g cells of not-over form one run.  A run whose last over cell is e closes
+ * when g+1 decided cells follow e, or at flush.  A closed run yields one pfb_cfar_det, in ascending first_index.
+ *
+ * Invariance: the detections of any cutting of the stream into calls, concatenated and followed by flush, are the
+ * same bytes as those of one call and flush.  Every figure is a fixed-order function of global indices: no float
+ * atomics, no arrival-order sums, no running sums.
+ *
+ * Limits: training by whole blocks is a deliberate trade for that invariance and for side data of 1/C of the stream;
+ * the guards must cover the replica's range sidelobes (G * C >= K) whatever the granularity.  C = 1 and 2 (the
+ * cell-sliding window), OS-CFAR and a detector fused into the matched filter's store are not built.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, an unknown element or method, a block_cells that is no power of two in 4 .. 1024, guard_blocks > 64,
+ * train_blocks outside 1 .. 32, merge_gap > 2^20, an alpha that is not finite or <= 0, a min_power that is negative or
+ * NaN, flags != 0.  Then PFB_ERR_NO_DEVICE without a HIP device. */
+enum { PFB_CFAR_POWER = 0, PFB_CFAR_BANK_CELL = 1 };
+enum { PFB_CFAR_CA = 0, PFB_CFAR_GO = 1, PFB_CFAR_SO = 2 };
+#define PFB_CFAR_DET_ONE_SIDED 1u /* pfb_cfar_det.flags: the peak's block trained on fewer than 2T blocks */
+
+typedef struct pfb_cfar_config {
+  uint32_t struct_size;   /* = sizeof(pfb_cfar_config)                                        */
+  uint32_t element;       /* PFB_CFAR_POWER / PFB_CFAR_BANK_CELL                              */
+  uint32_t method;        /* PFB_CFAR_CA / GO / SO                                            */
+  uint32_t block_cells;   /* C                                                                */
+  uint32_t guard_blocks;  /* G                                                                */
+  uint32_t train_blocks;  /* T, per side                                                      */
+  uint32_t merge_gap;     /* g, cells                                                         */
+  float alpha;
+  float min_power;
+  uint32_t flags;         /* 0                                                                */
+  int32_t device_id;      /* -1 = the current device                                          */
+} pfb_cfar_config;
+
+typedef struct pfb_cfar_plan { /* what pfb_cfar_describe reports; host only                    */
+  uint64_t latency_cells;  /* (G+T+1) * C: the most a cell waits for its decision              */
+  uint64_t training_cells; /* 2 * T * C                                                        */
+  uint64_t carry_bytes;    /* device bytes that hold the undecided cells and their block sums  */
+  char sum_kernel[32];     /* the sum pass's tier for this C                                   */
+} pfb_cfar_plan;
+
+typedef struct pfb_cfar_det {        /* 48 bytes */
+  uint64_t first_index, last_index;  /* first and last over cell of the run                                   */
+  uint64_t peak_index;               /* the over cell of largest p, ties to the lowest index                  */
+  float peak_power, noise;           /* p there; the noise of that cell's block                               */
+  int32_t hypothesis;                /* hyp[peak_index]; -1 for PFB_CFAR_POWER                                */
+  uint32_t cells_over;               /* over cells in the run, saturating at 2^32-1                           */
+  uint32_t flags;                    /* PFB_CFAR_DET_ONE_SIDED: the peak's block trained on fewer than 2T blocks */
+  uint32_t reserved;                 /* 0 */
+} pfb_cfar_det;
+
+typedef struct pfb_cfar_stats {
+  uint64_t cells_in;            /* cells taken since create or reset                                          */
+  uint64_t cells_decided;
+  uint64_t cells_over;
+  uint64_t cells_without_noise; /* decided cells of blocks with both training sets empty                      */
+  uint64_t detections;          /* runs closed, the dropped ones included                                     */
+  uint64_t dropped;             /* closed runs pfb_cfar_process_async had no room to write                    */
+  uint64_t open_run;            /* 0 or 1: a run waits for its g+1 decided cells                              */
+} pfb_cfar_stats;
+
+typedef struct pfb_cfar_handle pfb_cfar_handle;
+
+/* Host only: validate cfg (everything pfb_cfar_create checks before the device) and report the plan. */
+int pfb_cfar_describe(const pfb_cfar_config* cfg, pfb_cfar_plan* plan_out);
+/* Host only, float64: *alpha_out = N * (pfa^(-1/N) - 1), N = training_cells: the factor of CA-CFAR for square-law
+ * detected (exponentially distributed) noise.  GO and SO have other factors; a caller that uses them passes its own
+ * alpha.  PFB_ERR_BAD_ARG unless 0 < pfa < 1, N >= 1 and alpha_out is not null. */
+int pfb_cfar_alpha(double pfa, uint64_t training_cells, double* alpha_out);
+int pfb_cfar_create(const pfb_cfar_config* cfg, pfb_cfar_handle** out);
+int pfb_cfar_destroy(pfb_cfar_handle* h);
+int pfb_cfar_reset(pfb_cfar_handle* h);   /* stream index back to 0, nothing carried, stats zeroed */
+int pfb_cfar_set_stream(pfb_cfar_handle* h, void* hip_stream);
+int pfb_cfar_sync(pfb_cfar_handle* h);
+int pfb_cfar_get_device(const pfb_cfar_handle* h, int* device_id);
+int pfb_cfar_next_index(const pfb_cfar_handle* h, uint64_t* index_out);  /* global index of the next cell taken */
+/* Synchronises the handle's stream: the device keeps the counts that depend on the data. */
+int pfb_cfar_get_stats(pfb_cfar_handle* h, pfb_cfar_stats* stats_out);
+/* Take num_cells cells and write the detections that close, in order, to det_out (room for `capacity`); their number
+ * goes to *count_out.  PFB_ERR_CAPACITY sets *count_out to the number needed and changes no state (what det_out holds
+ * is then unspecified).  mem: cells and det_out are both host pointers (PFB_MEM_HOST, the cells staged in steps of
+ * 2^24) or both device pointers (PFB_MEM_DEVICE, cells aligned to one element, det_out to 8 bytes).  Synchronous. */
+int pfb_cfar_process(pfb_cfar_handle* h, const void* cells, uint64_t num_cells, pfb_cfar_det* det_out, uint64_t capacity,
+                     uint64_t* count_out, uint32_t mem);
+/* End the stream: decide what is left and close the open run.  Capacity contract and mem (of det_out) as above. */
+int pfb_cfar_flush(pfb_cfar_handle* h, pfb_cfar_det* det_out, uint64_t capacity, uint64_t* count_out, uint32_t mem);
+/* Device pointers, enqueued on the handle's stream without a host sync.  *d_count_out (a uint64 in device memory) is
+ * the number of runs the call closed.  Records beyond `capacity` are not written: they are counted in
+ * pfb_cfar_stats.dropped, and the state advances. */
+int pfb_cfar_process_async(pfb_cfar_handle* h, const void* d_cells, uint64_t num_cells, pfb_cfar_det* d_det_out,
+                           uint64_t capacity, uint64_t* d_count_out);
+/* Host only: detections as pulse descriptor words, so that pfb_event_fit takes them as it takes PDWs.
+ *   toa = (peak_index + 1) / fs + sample_start_time (the extractors' 1-based convention)
+ *   pw = (last_index - first_index + 1) / fs      snr = 10 log10(peak_power / noise)      mag = sqrt(peak_power)
+ *   freq = fc + (first_bin + hypothesis) * bin_step * bin_hz when hypothesis >= 0 (bank input), fc otherwise
+ *   sat = 0, bin = hypothesis
+ * PFB_ERR_BAD_ARG for null pointers (with n > 0) or an fs that is not finite and > 0. */
+int pfb_cfar_to_pdw(const pfb_cfar_det* dets, uint64_t n, double fs, double fc, double sample_start_time, double bin_hz,
+                    int32_t first_bin, uint32_t bin_step, pfb_pdw* pdw_out);
+/* Name of the sum kernel the last call launched ("" before the first). */
+const char* pfb_cfar_last_kernel(const pfb_cfar_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@ The arithmetic lives in libpfb_channelizer.so (HIP, gfx950) behind the C ABI of
 include/pfb_channelizer.h; this package is the thin host side.
 """
 from ._lib import LIB_PATH, PfbError  # noqa: F401
+from .cfar import (Cfar, cfar_alpha, detect, detect_pulses, detections_to_pdws,  # noqa: F401
+                   pulse_detections_from_iq_file)
 from .channelizer import Channelizer, center_frequencies, design_prototype, pinned_empty  # noqa: F401
 from .event import DwellStats, EventPredictor, analyze_dwell, dwell_from_iq_file, fit_event, next_event  # noqa: F401
 from .matched_filter import (MatchedFilter, compress, compress_iq_file, pulse_delay_from_iq_files,  # noqa: F401
@@ -26,4 +28,5 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
            "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",
+           "Cfar", "cfar_alpha", "detect", "detect_pulses", "pulse_detections_from_iq_file", "detections_to_pdws",
            "MatchedFilterBank", "compress_bank", "bank_frequencies", "pulse_delay_and_offset_from_iq_files"]

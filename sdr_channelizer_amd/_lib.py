@@ -47,6 +47,9 @@ PFB_WF_ROWS, PFB_WF_COLUMNS = 0, 1
 PFB_CHSYN_FFTSHIFT, PFB_CHSYN_DEROTATE = 1, 2
 PFB_CHSYN_ROUTE_AUTO, PFB_CHSYN_ROUTE_FUSED, PFB_CHSYN_ROUTE_GENERIC = 0, 1, 2
 PFB_MFBANK_BEST, PFB_MFBANK_SURFACE = 0, 1
+PFB_CFAR_POWER, PFB_CFAR_BANK_CELL = 0, 1
+PFB_CFAR_CA, PFB_CFAR_GO, PFB_CFAR_SO = 0, 1, 2
+PFB_CFAR_DET_ONE_SIDED = 1
 
 
 class PfbConfig(C.Structure):
@@ -173,6 +176,29 @@ class PfbMfbankCell(C.Structure):
     _fields_ = [("power", C.c_float), ("hypothesis", C.c_int32)]
 
 
+class PfbCfarConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("element", C.c_uint32), ("method", C.c_uint32), ("block_cells", C.c_uint32),
+                ("guard_blocks", C.c_uint32), ("train_blocks", C.c_uint32), ("merge_gap", C.c_uint32),
+                ("alpha", C.c_float), ("min_power", C.c_float), ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbCfarPlan(C.Structure):
+    _fields_ = [("latency_cells", C.c_uint64), ("training_cells", C.c_uint64), ("carry_bytes", C.c_uint64),
+                ("sum_kernel", C.c_char * 32)]
+
+
+class PfbCfarDet(C.Structure):
+    _fields_ = [("first_index", C.c_uint64), ("last_index", C.c_uint64), ("peak_index", C.c_uint64),
+                ("peak_power", C.c_float), ("noise", C.c_float), ("hypothesis", C.c_int32), ("cells_over", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PfbCfarStats(C.Structure):
+    _fields_ = [("cells_in", C.c_uint64), ("cells_decided", C.c_uint64), ("cells_over", C.c_uint64),
+                ("cells_without_noise", C.c_uint64), ("detections", C.c_uint64), ("dropped", C.c_uint64),
+                ("open_run", C.c_uint64)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -274,6 +300,9 @@ EXPORTS = (
     "pfb_mfbank_set_stream", "pfb_mfbank_sync", "pfb_mfbank_get_device", "pfb_mfbank_outputs_for",
     "pfb_mfbank_next_index", "pfb_mfbank_process", "pfb_mfbank_process_async", "pfb_mfbank_process_iq_file",
     "pfb_mfbank_last_kernel",
+    "pfb_cfar_describe", "pfb_cfar_alpha", "pfb_cfar_create", "pfb_cfar_destroy", "pfb_cfar_reset", "pfb_cfar_set_stream",
+    "pfb_cfar_sync", "pfb_cfar_get_device", "pfb_cfar_next_index", "pfb_cfar_get_stats", "pfb_cfar_process",
+    "pfb_cfar_flush", "pfb_cfar_process_async", "pfb_cfar_to_pdw", "pfb_cfar_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -473,6 +502,22 @@ def load() -> C.CDLL:
     lib.pfb_mfbank_process_iq_file.argtypes = [vp, C.c_char_p, vp, u64, u64, C.POINTER(u64), C.POINTER(PfbIqInfo)]
     lib.pfb_mfbank_last_kernel.argtypes = [vp]
     lib.pfb_mfbank_last_kernel.restype = C.c_char_p
+    lib.pfb_cfar_describe.argtypes = [C.POINTER(PfbCfarConfig), C.POINTER(PfbCfarPlan)]
+    lib.pfb_cfar_alpha.argtypes = [C.c_double, u64, C.POINTER(C.c_double)]
+    lib.pfb_cfar_create.argtypes = [C.POINTER(PfbCfarConfig), C.POINTER(vp)]
+    lib.pfb_cfar_destroy.argtypes = [vp]
+    lib.pfb_cfar_reset.argtypes = [vp]
+    lib.pfb_cfar_set_stream.argtypes = [vp, vp]
+    lib.pfb_cfar_sync.argtypes = [vp]
+    lib.pfb_cfar_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_cfar_next_index.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_cfar_get_stats.argtypes = [vp, C.POINTER(PfbCfarStats)]
+    lib.pfb_cfar_process.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_cfar_flush.argtypes = [vp, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_cfar_process_async.argtypes = [vp, vp, u64, vp, u64, vp]
+    lib.pfb_cfar_to_pdw.argtypes = [vp, u64, C.c_double, C.c_double, C.c_double, C.c_double, i32, u32, C.POINTER(PfbPdw)]
+    lib.pfb_cfar_last_kernel.argtypes = [vp]
+    lib.pfb_cfar_last_kernel.restype = C.c_char_p
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
