@@ -1242,6 +1242,118 @@ int pfb_cfar_to_pdw(const pfb_cfar_det* dets, uint64_t n, double fs, double fc, 
 /* Name of the sum kernel the last call launched ("" before the first). */
 const char* pfb_cfar_last_kernel(const pfb_cfar_handle* h);
 
+/* ---- pulse-Doppler integration: range-Doppler maps of a pulse train ---------------------------
+ * Every unit above decides on one pulse at a time, yet the reference's signals are trains of identical pulses
+ * (matlab/generate_pulsed_iq.m and generate_training_iq.m emit a pulse of PW every PRI, tx_rx_pulses_usrp.cpp:71 takes
+ * the PRI as an argument, the training records carry PW and PRI in their names).  K compressed pulses folded at the PRI
+ * add coherently, 10 log10 K dB over one pulse, and a phase step from pulse to pulse -- a carrier offset far finer than
+ * one bin of the bank -- shows as a Doppler bin.  This comment is the definition: the device code (csrc/pfb_pd.hip)
+ * and the tests' restatement (tests/pd_ref.py) are each written from it.
+ *
+ * Input: a complex64 stream x[n], n the stream-absolute index since create, reset or pfb_pd_set_index: what
+ * PFB_MF_COMPLEX writes, or any cf32 stream.
+ * Parameters: pri L samples (1 .. 2^24), origin o (the stream index of gate 0 of pulse 0, <= 2^62), num_gates R
+ * (1 .. L), num_pulses K per coherent interval (CPI), doppler_length ND in {8, 16, 32, 64, 128, 256, 512, 1024}
+ * (0: the smallest of these >= K), 1 <= K <= ND, a float32 window w[K] (NULL: all ones; finite, copied at create).
+ *
+ *   A_c[k][r] = x[o + (c K + k) L + r]       CPI c = 0, 1, ..., pulse k = 0 .. K-1, gate r = 0 .. R-1
+ * CPIs do not overlap; samples before o and between the gates are ignored.  Rows K .. ND-1 of the transform are zero.
+ * Outputs, by pfb_pd_config.output; c' counts the CPIs the call completes:
+ *   PFB_PD_COMPLEX      Z_c[d][r] = sum_{k<K} w[k] A_c[k][r] e^{-j 2 pi d k / ND}, complex64 at out[(c' ND + d) R + r]
+ *   PFB_PD_POWER        |Z_c[d][r]|^2, float32, same layout
+ *   PFB_PD_BEST         one pfb_mfbank_cell per gate at out[c' R + r]: the largest power over d and the d that gave it.
+ *                       The selection walks d = 0, 1, ... and replaces only on a strictly greater power: ties go to
+ *                       the lowest d and a power that is not a number never displaces anything (NaN at d = 0 stays):
+ *                       the rule of PFB_MFBANK_BEST, and what PFB_CFAR_BANK_CELL reads.
+ *   PFB_PD_NONCOHERENT  N_c[r] = sum_k w[k]^2 |A_c[k][r]|^2, float32 at out[c' R + r]: per pulse the windowed sample
+ *                       (w re, w im), its squared magnitude, added in float32 for k ascending.
+ * PFB_PD_CENTERED (flags): rows are written for d = -ND/2 .. ND/2-1 in that order (row d + ND/2), the hypothesis of a
+ * BEST cell is that signed d, and the tie rule walks the signed order.  Row d stands for the pulse-to-pulse frequency
+ * d fs / (ND L) (pfb_pd_doppler_frequencies).
+ *
+ * State: CPI c completes with sample o + ((c+1) K - 1) L + R - 1; cpi_samples = (K-1) L + R is its extent.  A stream
+ * may be cut into calls of any length, 0 included.  A CPI that lies wholly inside one call is read where it lies (row
+ * stride L, 8-byte alignment).  A CPI that spans calls has its gate samples copied into a device-side K x R carry as
+ * they arrive (zeroed when the CPI opens) and is transformed from the carry when it completes; each staging step of a
+ * host-pointer call counts as a call here.  Both sources run the same kernel on the same values in the same order, so
+ * THE SAME BITS COME OUT UNDER ANY CUTTING of the stream (unlike pfb_mf_*, whose blocks start where calls start).
+ * A CPI is taken only if its first sample o + c K L is not before the index the stream (re)started at: create and
+ * pfb_pd_reset start at 0, pfb_pd_set_index at its argument.  The carry is K R 8 bytes; more than 64 MiB is
+ * PFB_ERR_UNSUPPORTED.  pfb_pd_flush transforms the open CPI with its missing samples as zeros (a no-op when none is
+ * open); what the stream brings of that CPI afterwards is ignored.  Lengths outside the set, overlapping CPIs,
+ * staggered or non-integer PRIs, clutter cancellers and integer I/Q input are not built.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, L, R or K of 0, R > L, K > ND, ND outside the set, L > 2^24, origin > 2^62, an unknown output or flag,
+ * a window value that is not finite; per call an unknown mem, a stream index that would pass 2^62, a device pointer
+ * not aligned to its element (8 bytes for samples, complex rows, cells and the async count; 4 for float rows).
+ * PFB_ERR_UNSUPPORTED: a carry over 64 MiB.  Then PFB_ERR_NO_DEVICE without a HIP device. */
+enum { PFB_PD_COMPLEX = 0, PFB_PD_POWER = 1, PFB_PD_BEST = 2, PFB_PD_NONCOHERENT = 3 };
+enum { PFB_PD_CENTERED = 1u << 0 };
+
+typedef struct pfb_pd_config {
+  uint32_t struct_size;     /* = sizeof(pfb_pd_config)                                          */
+  uint32_t pri;             /* L, samples                                                       */
+  uint64_t origin;          /* o: stream index of gate 0 of pulse 0                             */
+  uint32_t num_gates;       /* R <= L                                                           */
+  uint32_t num_pulses;      /* K per CPI                                                        */
+  uint32_t doppler_length;  /* ND; 0 = the smallest of the set >= K                             */
+  uint32_t output;          /* PFB_PD_*                                                         */
+  const float* window;      /* w[0 .. K-1], finite, copied at create; NULL = all ones           */
+  uint32_t flags;           /* PFB_PD_CENTERED                                                  */
+  int32_t device_id;        /* HIP device ordinal, -1 = current device                          */
+} pfb_pd_config;
+
+typedef struct pfb_pd_plan { /* what pfb_pd_describe reports; host only                          */
+  uint32_t doppler_length;  /* ND                                                               */
+  uint32_t tile_gates;      /* adjacent gates one workgroup takes                               */
+  uint64_t carry_bytes;     /* K R 8                                                            */
+  uint64_t cpi_samples;     /* (K-1) L + R: from a CPI's first sample to the one completing it  */
+  uint64_t cpi_outputs;     /* output elements per CPI: ND R (complex, power), R (best, noncoherent) */
+  char kernel[32];          /* the kernel that transforms a CPI                                 */
+} pfb_pd_plan;
+
+typedef struct pfb_pd_handle pfb_pd_handle;
+
+/* Host only: validate cfg (everything pfb_pd_create checks before the device) and report the plan. */
+int pfb_pd_describe(const pfb_pd_config* cfg, pfb_pd_plan* plan_out);
+/* Host only: out[i] = d fs / (ND L) for the ND rows in the order they are written (d = 0 .. ND-1, or -ND/2 .. ND/2-1
+ * with PFB_PD_CENTERED).  Reads struct_size, pri, num_pulses, doppler_length and flags of cfg and nothing else.
+ * PFB_ERR_BAD_ARG for null pointers, a wrong struct_size, a pri, K or ND pfb_pd_create refuses, or fs not finite. */
+int pfb_pd_doppler_frequencies(const pfb_pd_config* cfg, double fs, double* out);
+/* Lifecycle as pfb_cfar_*.  The handle owns the window, the twiddles and the carry. */
+int pfb_pd_create(const pfb_pd_config* cfg, pfb_pd_handle** out);
+int pfb_pd_destroy(pfb_pd_handle* h);
+int pfb_pd_reset(pfb_pd_handle* h);   /* drops the open CPI; stream index back to 0 */
+int pfb_pd_set_stream(pfb_pd_handle* h, void* hip_stream);
+int pfb_pd_sync(pfb_pd_handle* h);
+int pfb_pd_get_device(const pfb_pd_handle* h, int* device_id);
+/* The CPIs the next num_samples samples complete, given the handle's state now. */
+int pfb_pd_cpis_for(const pfb_pd_handle* h, uint64_t num_samples, uint64_t* cpis_out);
+int pfb_pd_next_index(const pfb_pd_handle* h, uint64_t* index_out);  /* stream index of the next sample taken */
+/* Drops the open CPI and makes next_sample (<= 2^62) the index of the next sample taken (pfb_chsyn_set_frame_index
+ * is the precedent). */
+int pfb_pd_set_index(pfb_pd_handle* h, uint64_t next_sample);
+/* Take num_samples samples; the CPIs they complete go to `out` (room for capacity_cpis CPIs of plan.cpi_outputs
+ * elements each) in ascending order, their number to *cpis_out.  PFB_ERR_CAPACITY sets *cpis_out to the number needed
+ * and changes no state.  mem: y and out are both host pointers (PFB_MEM_HOST, staged in steps of 2^22 samples; the
+ * outputs of one step are held on the device until the step ends) or both device pointers (PFB_MEM_DEVICE).
+ * Synchronous.  After PFB_ERR_HIP the stream index is as before the call and the call may be repeated; an open CPI is
+ * kept unless the failed call had already closed it and begun another in the carry: then it is dropped, as
+ * pfb_pd_set_index(pfb_pd_next_index) would drop it.  What `out` holds after a failure is undefined. */
+int pfb_pd_process(pfb_pd_handle* h, const void* y, uint64_t num_samples, void* out, uint64_t capacity_cpis,
+                   uint64_t* cpis_out, uint32_t mem);
+/* Same, device pointers, enqueued on the handle's stream without a host sync; the number of CPIs the call closed is
+ * written to *d_cpis_out, a uint64 in device memory, in stream order.  PFB_ERR_CAPACITY queues nothing. */
+int pfb_pd_process_async(pfb_pd_handle* h, const void* d_y, uint64_t num_samples, void* d_out, uint64_t capacity_cpis,
+                         uint64_t* d_cpis_out);
+/* Transform the open CPI with its missing samples as zeros: *cpis_out is 1, or 0 when none is open.  Capacity
+ * contract and mem (of out) as pfb_pd_process. */
+int pfb_pd_flush(pfb_pd_handle* h, void* out, uint64_t capacity_cpis, uint64_t* cpis_out, uint32_t mem);
+/* The kernel and the source of the last CPI transformed: plan.kernel followed by "[stream]" (read where it lay) or
+ * "[carry]"; "" before the first. */
+const char* pfb_pd_last_kernel(const pfb_pd_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

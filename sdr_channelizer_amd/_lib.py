@@ -50,6 +50,8 @@ PFB_MFBANK_BEST, PFB_MFBANK_SURFACE = 0, 1
 PFB_CFAR_POWER, PFB_CFAR_BANK_CELL = 0, 1
 PFB_CFAR_CA, PFB_CFAR_GO, PFB_CFAR_SO = 0, 1, 2
 PFB_CFAR_DET_ONE_SIDED = 1
+PFB_PD_COMPLEX, PFB_PD_POWER, PFB_PD_BEST, PFB_PD_NONCOHERENT = 0, 1, 2, 3
+PFB_PD_CENTERED = 1
 
 
 class PfbConfig(C.Structure):
@@ -199,6 +201,17 @@ class PfbCfarStats(C.Structure):
                 ("open_run", C.c_uint64)]
 
 
+class PfbPdConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pri", C.c_uint32), ("origin", C.c_uint64), ("num_gates", C.c_uint32),
+                ("num_pulses", C.c_uint32), ("doppler_length", C.c_uint32), ("output", C.c_uint32),
+                ("window", C.POINTER(C.c_float)), ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbPdPlan(C.Structure):
+    _fields_ = [("doppler_length", C.c_uint32), ("tile_gates", C.c_uint32), ("carry_bytes", C.c_uint64),
+                ("cpi_samples", C.c_uint64), ("cpi_outputs", C.c_uint64), ("kernel", C.c_char * 32)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -303,6 +316,9 @@ EXPORTS = (
     "pfb_cfar_describe", "pfb_cfar_alpha", "pfb_cfar_create", "pfb_cfar_destroy", "pfb_cfar_reset", "pfb_cfar_set_stream",
     "pfb_cfar_sync", "pfb_cfar_get_device", "pfb_cfar_next_index", "pfb_cfar_get_stats", "pfb_cfar_process",
     "pfb_cfar_flush", "pfb_cfar_process_async", "pfb_cfar_to_pdw", "pfb_cfar_last_kernel",
+    "pfb_pd_describe", "pfb_pd_doppler_frequencies", "pfb_pd_create", "pfb_pd_destroy", "pfb_pd_reset",
+    "pfb_pd_set_stream", "pfb_pd_sync", "pfb_pd_get_device", "pfb_pd_cpis_for", "pfb_pd_next_index", "pfb_pd_set_index",
+    "pfb_pd_process", "pfb_pd_process_async", "pfb_pd_flush", "pfb_pd_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -518,6 +534,22 @@ def load() -> C.CDLL:
     lib.pfb_cfar_to_pdw.argtypes = [vp, u64, C.c_double, C.c_double, C.c_double, C.c_double, i32, u32, C.POINTER(PfbPdw)]
     lib.pfb_cfar_last_kernel.argtypes = [vp]
     lib.pfb_cfar_last_kernel.restype = C.c_char_p
+    lib.pfb_pd_describe.argtypes = [C.POINTER(PfbPdConfig), C.POINTER(PfbPdPlan)]
+    lib.pfb_pd_doppler_frequencies.argtypes = [C.POINTER(PfbPdConfig), C.c_double, C.POINTER(C.c_double)]
+    lib.pfb_pd_create.argtypes = [C.POINTER(PfbPdConfig), C.POINTER(vp)]
+    lib.pfb_pd_destroy.argtypes = [vp]
+    lib.pfb_pd_reset.argtypes = [vp]
+    lib.pfb_pd_set_stream.argtypes = [vp, vp]
+    lib.pfb_pd_sync.argtypes = [vp]
+    lib.pfb_pd_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_pd_cpis_for.argtypes = [vp, u64, C.POINTER(u64)]
+    lib.pfb_pd_next_index.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_pd_set_index.argtypes = [vp, u64]
+    lib.pfb_pd_process.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_pd_process_async.argtypes = [vp, vp, u64, vp, u64, vp]
+    lib.pfb_pd_flush.argtypes = [vp, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_pd_last_kernel.argtypes = [vp]
+    lib.pfb_pd_last_kernel.restype = C.c_char_p
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
