@@ -1354,6 +1354,113 @@ int pfb_pd_flush(pfb_pd_handle* h, void* out, uint64_t capacity_cpis, uint64_t* 
  * "[carry]"; "" before the first. */
 const char* pfb_pd_last_kernel(const pfb_pd_handle* h);
 
+/* ---- PRI search by epoch folding: where pfb_pd_config.pri comes from ----------------------------
+ * pfb_pd_* integrates a train whose single pulses are under the detector's threshold, for a caller who knows the PRI to
+ * the sample.  The reference carries that number in a script constant (matlab/generate_pulsed_iq.m:16) or on a command
+ * line (tx_rx_pulses_usrp.cpp:71); a record off the air carries it nowhere, and a train under the single-pulse threshold
+ * leaves pfb_cfar_* no arrival times to difference.  Epoch folding finds it: for each candidate period L the power
+ * stream is added into a profile of L / C phase bins.  At the true period every pulse lands in the same bin, which then
+ * stands out; at L +- 1 the train walks through the bins and averages away.  This comment is the definition: the device
+ * code (csrc/pfb_fold.hip) and the tests' restatement (tests/fold_ref.py) are each written from it.
+ *
+ * Input: float32 cells p[i] with the global index i = 0, 1, ... since create or reset: what PFB_MF_POWER writes, or any
+ * float32 stream.
+ * Parameters: bin_cells C (1 .. 64) and a list of NC candidate periods L_c (uint32, copied at create), 1 <= NC <= 4096,
+ * each with C <= L <= 2^24 and NB = floor(L / C) <= 65536 bins.  Duplicates are allowed and are separate candidates.
+ * The profiles take sum_c NB_c * 4 bytes on the device (plan.profile_bytes); more than 64 MiB is PFB_ERR_UNSUPPORTED.
+ *
+ * Bin of cell i under period L:  j = min(floor((i mod L) / C), NB - 1).  The L mod C cells left over at the end of a
+ * period go into the last bin, which is then C .. 2C-1 cells wide, never narrower (a narrow last bin has few cells
+ * behind its mean and wins the maximum on noise alone).
+ *
+ * Profile: F_L[j] is the float32 sum of the p[i] of bin j, added ONE AT A TIME IN ASCENDING i, starting from +0.0f.
+ * No tree, no atomics, no partial sums combined afterwards; only additions occur, so no FMA can arise.  The profile is
+ * therefore a function of the cells taken so far: THE SAME BITS COME OUT UNDER ANY CUTTING OF THE STREAM into calls; a
+ * call may be empty or end in the middle of a bin of a period.  NaN and Inf go where IEEE addition takes them.
+ *
+ * Counts, all integers, after N cells:  n_L[j](N) = floor(N / L) (b - a) + clamp((N mod L) - a, 0, b - a)  with a = j C
+ * and b = (j + 1) C, or b = L for the last bin (pfb_fold_counts; host only).
+ *
+ * Score of a candidate after N cells: one pfb_fold_score, in list order (pfb_fold_scores).
+ *   m_j = (double)F[j] / (double)n_j, the correctly rounded float64 quotient, for the bins with n_j > 0: the leading
+ *   bins_used ones.
+ *   The peak walks j ascending and replaces only on a strictly greater m_j: ties go to the lowest j, a NaN never
+ *   displaces anything, and a NaN in the first used bin stays -- the rule of PFB_MFBANK_BEST and PFB_PD_BEST.
+ *   peak_sum = F[peak_bin], peak_cells = n[peak_bin], peak_mean = (float)m_peak.
+ *   sum_means = sum_j m_j and sum_sq_means = sum_j m_j^2 over the used bins, in float64.  THEIR ORDER IS NOT FIXED (a
+ *   workgroup reduces them): they are good to (bins_used + 1) 2^-53 sum |terms|, the bound of any-order float64
+ *   summation plus the square's rounding.  Every other field is a fixed function of the cells.
+ *   With N = 0 every field but period, num_bins and cells is 0.
+ * A caller's statistic from these: mu = sum_means / bins_used, z = (peak_mean - mu) / sqrt(sum_sq_means / bins_used -
+ * mu^2).  The true period, its multiples and its divisors (if listed) score high; origin = peak_bin * C is, modulo the
+ * period, where the train's compressed peak lies (to one bin), and is what pfb_pd_config.origin takes.
+ *
+ * Not built: splitting one candidate's time axis over workgroups (the order above forbids it), non-integer and
+ * staggered periods, a fast-folding tree that shares additions between candidates, PFB_CFAR_BANK_CELL input, folding
+ * fused into the matched filter's store.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers (the list
+ * included), a wrong struct_size, C outside 1 .. 64, NC outside 1 .. 4096, a period < C or > 2^24 or with more than
+ * 65536 bins, flags != 0; per call an unknown mem, a device pointer not aligned to its element (4 bytes for cells and
+ * profiles, 8 for score records), an index that would pass 2^62, a candidate >= NC.  Then PFB_ERR_UNSUPPORTED: profiles
+ * over 64 MiB.  Then PFB_ERR_NO_DEVICE without a HIP device. */
+typedef struct pfb_fold_config {
+  uint32_t struct_size;     /* = sizeof(pfb_fold_config)                                        */
+  uint32_t bin_cells;       /* C                                                                */
+  uint32_t num_periods;     /* NC                                                               */
+  const uint32_t* periods;  /* L_c, c = 0 .. NC-1, copied at create                             */
+  uint32_t flags;           /* 0                                                                */
+  int32_t device_id;        /* HIP device ordinal, -1 = current device                          */
+} pfb_fold_config;
+
+typedef struct pfb_fold_plan { /* what pfb_fold_describe reports; host only                      */
+  uint64_t profile_bytes;   /* sum_c NB_c * 4 (the handle holds a second copy: pfb_fold_process)*/
+  uint64_t total_bins;      /* sum_c NB_c                                                       */
+  uint32_t max_bins;        /* max_c NB_c                                                       */
+  char kernel[32];          /* the kernel that folds a call                                     */
+} pfb_fold_plan;
+
+typedef struct pfb_fold_score {  /* 56 bytes */
+  uint32_t period, num_bins;     /* L, NB                                                            */
+  uint32_t bins_used;            /* bins with n_j > 0: min(NB, ceil(N / C))                          */
+  uint32_t peak_bin, peak_cells; /* the bin of largest mean, ties to the lowest; its n_j             */
+  uint32_t reserved;             /* 0 */
+  float peak_sum, peak_mean;     /* F[peak_bin]; (float)m_peak                                       */
+  double sum_means, sum_sq_means;
+  uint64_t cells;                /* N */
+} pfb_fold_score;
+
+typedef struct pfb_fold_handle pfb_fold_handle;
+
+/* Host only: validate cfg (everything pfb_fold_create checks before the device) and report the plan. */
+int pfb_fold_describe(const pfb_fold_config* cfg, pfb_fold_plan* plan_out);
+/* Host only: counts_out[j] = n_L[j](num_cells) for the NB bins of candidate `candidate` of cfg (the closed form above).
+ * PFB_ERR_BAD_ARG for a cfg pfb_fold_describe refuses with it, a null counts_out, candidate >= NC, num_cells > 2^62. */
+int pfb_fold_counts(const pfb_fold_config* cfg, uint32_t candidate, uint64_t num_cells, uint64_t* counts_out);
+/* Lifecycle as pfb_cfar_*.  The handle owns the period list and the profiles. */
+int pfb_fold_create(const pfb_fold_config* cfg, pfb_fold_handle** out);
+int pfb_fold_destroy(pfb_fold_handle* h);
+int pfb_fold_reset(pfb_fold_handle* h);   /* profiles to +0, index to 0 */
+int pfb_fold_set_stream(pfb_fold_handle* h, void* hip_stream);
+int pfb_fold_sync(pfb_fold_handle* h);
+int pfb_fold_get_device(const pfb_fold_handle* h, int* device_id);
+int pfb_fold_next_index(const pfb_fold_handle* h, uint64_t* index_out);  /* N: global index of the next cell taken */
+/* Fold num_cells cells into every profile.  mem: cells is a host pointer (PFB_MEM_HOST, staged in steps of 2^24 cells)
+ * or a device pointer (PFB_MEM_DEVICE, 4-byte aligned, nothing more).  Synchronous.  After PFB_ERR_HIP the profiles and
+ * the index are as before the call (the handle keeps the copy that makes this so). */
+int pfb_fold_process(pfb_fold_handle* h, const float* cells, uint64_t num_cells, uint32_t mem);
+/* Same, device pointer, enqueued on the handle's stream without a host sync. */
+int pfb_fold_process_async(pfb_fold_handle* h, const float* d_cells, uint64_t num_cells);
+/* Write the NC score records of the cells taken so far to `out` (room for `capacity` records; host memory, or device
+ * memory aligned to 8 bytes).  Changes no state and may be called any number of times mid-stream.  PFB_ERR_CAPACITY when
+ * capacity < NC: nothing is written.  Synchronous. */
+int pfb_fold_scores(pfb_fold_handle* h, pfb_fold_score* out, uint64_t capacity, uint32_t mem);
+/* Copy F_L of one candidate, NB floats, to `out` (room for capacity_bins): for plotting and for a caller's own
+ * statistics.  PFB_ERR_CAPACITY when capacity_bins < NB.  Changes no state.  Synchronous. */
+int pfb_fold_profile(pfb_fold_handle* h, uint32_t candidate, float* out, uint64_t capacity_bins, uint32_t mem);
+/* The kernel the last call that took cells launched: plan.kernel; "" before the first. */
+const char* pfb_fold_last_kernel(const pfb_fold_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,12 @@ int pfb_measure_mix_copy(int device_id, uint64_t bytes_in, uint32_t write_ratio,
  * on the generic kernel.  Registered nowhere: pfb_stft_last_kernel names it pfb_stft_loadstore<...>. */
 int pfb_stft_set_experiment(pfb_stft_handle* h, int experiment);
 
+/* Which kernel folds the next calls of a pfb_fold handle: 0 = the library's choice (pfb_fold_plan.kernel), 1 =
+ * fold_direct, 2 = fold_tile.  Both add every bin's cells in the definition's order and give the same bytes; the
+ * tests run one handle through both, the meter (tools/fold_rate.py --tier) times both.  PFB_ERR_UNSUPPORTED for 2 when
+ * bin_cells is not 8, 16, 32 or 64; PFB_ERR_BAD_ARG for any other value.  pfb_fold_last_kernel names what ran. */
+int pfb_fold_set_tier(pfb_fold_handle* h, int tier);
+
 /* The fused-kernel table, row by row in lookup order (host only, no device needed): what the tests walk, so that a
  * registered plan cannot go untested.  Rows of one (M, P, D, sample_format) are that shape's variants 0, 1, ... */
 typedef struct {

@@ -212,6 +212,22 @@ class PfbPdPlan(C.Structure):
                 ("cpi_samples", C.c_uint64), ("cpi_outputs", C.c_uint64), ("kernel", C.c_char * 32)]
 
 
+class PfbFoldConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("bin_cells", C.c_uint32), ("num_periods", C.c_uint32),
+                ("periods", C.POINTER(C.c_uint32)), ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbFoldPlan(C.Structure):
+    _fields_ = [("profile_bytes", C.c_uint64), ("total_bins", C.c_uint64), ("max_bins", C.c_uint32),
+                ("kernel", C.c_char * 32)]
+
+
+class PfbFoldScore(C.Structure):
+    _fields_ = [("period", C.c_uint32), ("num_bins", C.c_uint32), ("bins_used", C.c_uint32), ("peak_bin", C.c_uint32),
+                ("peak_cells", C.c_uint32), ("reserved", C.c_uint32), ("peak_sum", C.c_float), ("peak_mean", C.c_float),
+                ("sum_means", C.c_double), ("sum_sq_means", C.c_double), ("cells", C.c_uint64)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -319,9 +335,13 @@ EXPORTS = (
     "pfb_pd_describe", "pfb_pd_doppler_frequencies", "pfb_pd_create", "pfb_pd_destroy", "pfb_pd_reset",
     "pfb_pd_set_stream", "pfb_pd_sync", "pfb_pd_get_device", "pfb_pd_cpis_for", "pfb_pd_next_index", "pfb_pd_set_index",
     "pfb_pd_process", "pfb_pd_process_async", "pfb_pd_flush", "pfb_pd_last_kernel",
+    "pfb_fold_describe", "pfb_fold_counts", "pfb_fold_create", "pfb_fold_destroy", "pfb_fold_reset",
+    "pfb_fold_set_stream", "pfb_fold_sync", "pfb_fold_get_device", "pfb_fold_next_index", "pfb_fold_process",
+    "pfb_fold_process_async", "pfb_fold_scores", "pfb_fold_profile", "pfb_fold_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
+               "pfb_fold_set_tier",
                "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch", "pfb_last_entry", "pfb_plan_entry")
 
 _lib = None
@@ -550,6 +570,22 @@ def load() -> C.CDLL:
     lib.pfb_pd_flush.argtypes = [vp, vp, u64, C.POINTER(u64), u32]
     lib.pfb_pd_last_kernel.argtypes = [vp]
     lib.pfb_pd_last_kernel.restype = C.c_char_p
+    lib.pfb_fold_describe.argtypes = [C.POINTER(PfbFoldConfig), C.POINTER(PfbFoldPlan)]
+    lib.pfb_fold_counts.argtypes = [C.POINTER(PfbFoldConfig), u32, u64, C.POINTER(u64)]
+    lib.pfb_fold_create.argtypes = [C.POINTER(PfbFoldConfig), C.POINTER(vp)]
+    lib.pfb_fold_destroy.argtypes = [vp]
+    lib.pfb_fold_reset.argtypes = [vp]
+    lib.pfb_fold_set_stream.argtypes = [vp, vp]
+    lib.pfb_fold_sync.argtypes = [vp]
+    lib.pfb_fold_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_fold_next_index.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_fold_process.argtypes = [vp, vp, u64, u32]
+    lib.pfb_fold_process_async.argtypes = [vp, vp, u64]
+    lib.pfb_fold_scores.argtypes = [vp, vp, u64, u32]
+    lib.pfb_fold_profile.argtypes = [vp, u32, vp, u64, u32]
+    lib.pfb_fold_last_kernel.argtypes = [vp]
+    lib.pfb_fold_last_kernel.restype = C.c_char_p
+    lib.pfb_fold_set_tier.argtypes = [vp, C.c_int]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
