@@ -1461,6 +1461,148 @@ int pfb_fold_profile(pfb_fold_handle* h, uint32_t candidate, float* out, uint64_
 /* The kernel the last call that took cells launched: plan.kernel; "" before the first. */
 const char* pfb_fold_last_kernel(const pfb_fold_handle* h);
 
+/* ---- 2-D CFAR detector over range-Doppler maps -------------------------------------------------
+ * pfb_pd_* leaves power maps on the device; this unit turns them into one record per target.  It slides a window over
+ * the (Doppler row, gate) plane cell by cell: the noise of a cell is the mean of training cells before and after it in
+ * range, over a few Doppler rows around its own; a cell over its threshold is reported when it is the largest of its
+ * neighbourhood.  Two trains in one gate on different Doppler rows give two records, and the factor for a false-alarm
+ * rate is the plain CA factor for the training cells: with Wd = 0 whatever window pfb_pd_* applied, because training
+ * and test cell share a row's statistics; with Wd > 0 a taper correlates adjacent rows, the training cells count for
+ * fewer, and the rate rises (DESIGN.md section 22 has measured figures).  On the one-row maps of PFB_PD_NONCOHERENT it
+ * is the cell-sliding 1-D detector pfb_cfar_* leaves out.
+ * This comment is the definition: the device code (csrc/pfb_rdcfar.hip) and the tests' restatement
+ * (tests/rdcfar_ref.py) are each written from it.
+ *
+ * Input: maps P_m[d][r], float32, m = 0, 1, ... counting maps since create or reset, rows d = 0 .. ND-1 (ND any
+ * integer 1 .. 1024), gates r = 0 .. R-1 (R = 1 .. 2^20): the element lies at maps[(m' ND + d) pitch + r], m' the map's
+ * place in the call, pitch >= R (0 means R), ND pitch <= 2^26.  Rows are circular (Doppler wraps), gates are not.  The
+ * unit does not care in which order the rows stand (PFB_PD_CENTERED or not): it reports the row as stored.
+ * Parameters: Doppler half-width Wd (0 .. 16, 2 Wd + 1 <= ND), gate guard Gr (0 .. 1024), gate training per side Tr
+ * (1 .. 256), peak half-width in rows Pd (0 .. 16, 2 Pd + 1 <= ND), method (CA, GO, SO: the PFB_CFAR_* values), alpha
+ * (float32, finite, > 0), min_power (float32, >= 0).
+ *
+ * Column sum: A[d][r] is the float64 sum of (double)P[(d + j) mod ND][r] for j = -Wd .. Wd, added ONE AT A TIME IN
+ * ASCENDING j, starting from +0.0.
+ *
+ * Noise of cell (d, r): the lead gates are r-Gr-Tr .. r-Gr-1 that are >= 0 (nL of them), the lag gates r+Gr+1 ..
+ * r+Gr+Tr that are < R (nR).  sumL and sumR are float64 sums of A[d][.] over those gates, one at a time in ascending
+ * gate, each starting from +0.0.
+ *   CA  noise = (float)((sumL + sumR) / ((nL + nR) (2 Wd + 1)))
+ *   GO  noise = (float)max(sumL / (nL (2 Wd + 1)), sumR / (nR (2 Wd + 1)))       SO: the same with min
+ * In GO and SO an empty side is left out, and a NaN on either side gives NaN.  All divisions are float64, with one
+ * rounding to float32 at the end.  With nL = nR = 0 the cell has no noise: it is never over, and it is counted in
+ * pfb_rdcfar_stats.cells_without_noise.
+ *
+ * Decision: over = (p > alpha * noise) && (p > min_power), p = P[d][r], the product one float32 multiply, as in
+ * pfb_cfar_*.  A NaN on either side of a comparison never detects; nothing is special-cased.
+ *
+ * Detection: an over cell is reported iff no cell of its peak box beats it.  The box is the rows d-Pd .. d+Pd
+ * (circular) by the gates r-Gr .. r+Gr (clipped to 0 .. R-1).  q beats p iff P_q > P_p, or P_q == P_p and q's (row,
+ * gate), the row as stored, is lower in row-major order.  A NaN neighbour beats nothing.  One pfb_rdcfar_det per
+ * reported cell, written in ascending (map, row, gate).
+ *
+ * Invariance: every figure is a function of one map, so ANY CUTTING OF A SEQUENCE OF MAPS INTO CALLS GIVES THE SAME
+ * BYTES.  Only additions, one division and one multiply occur, in the order stated: no atomics, no running sums, no
+ * arrival-order compaction (the records are placed by counts and a scan).
+ *
+ * Cost: a cell walks its 2 Tr training sums itself, and an over cell walks its whole peak box, (2 Pd + 1)(2 Gr + 1)
+ * cells, in one lane: correct, and slow only for maps that are all detections.  A call is worked in steps of whole
+ * maps, of at most 2^24 cells and 2^18 words of 64 gates (at least one map); a host-pointer call stages its maps in
+ * those steps.
+ *
+ * Not built: OS-CFAR, guard rows in Doppler, joining adjacent reported cells into 2-D runs, a detector fused into
+ * pfb_pd_*'s store.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, rows outside 1 .. 1024, gates outside 1 .. 2^20, a pitch that is neither 0 nor >= gates or with
+ * rows pitch > 2^26, doppler_half_width > 16 or 2 Wd + 1 > rows, guard_gates > 1024, train_gates outside 1 .. 256,
+ * peak_half_width > 16 or 2 Pd + 1 > rows, an unknown method, an alpha that is not finite or <= 0, a min_power that is
+ * negative or NaN, flags != 0; per call an unknown mem, num_maps > 2^40, capacity > 2^56, a device pointer not aligned
+ * to its element (4 bytes for maps, 8 for records and the async count).  Then PFB_ERR_NO_DEVICE without a HIP device. */
+#define PFB_RDCFAR_DET_ONE_SIDED 1u /* pfb_rdcfar_det.flags: the cell trained on fewer than 2 Tr gates */
+
+typedef struct pfb_rdcfar_config {
+  uint32_t struct_size;         /* = sizeof(pfb_rdcfar_config)                                  */
+  uint32_t rows;                /* ND                                                           */
+  uint32_t gates;               /* R                                                            */
+  uint32_t pitch;               /* floats from one row to the next; 0 = gates                   */
+  uint32_t doppler_half_width;  /* Wd                                                           */
+  uint32_t guard_gates;         /* Gr                                                           */
+  uint32_t train_gates;         /* Tr, per side                                                 */
+  uint32_t peak_half_width;     /* Pd                                                           */
+  uint32_t method;              /* PFB_CFAR_CA / GO / SO                                        */
+  float alpha;
+  float min_power;
+  uint32_t flags;               /* 0                                                            */
+  int32_t device_id;            /* -1 = the current device                                      */
+} pfb_rdcfar_config;
+
+typedef struct pfb_rdcfar_plan { /* what pfb_rdcfar_describe reports; host only                  */
+  uint64_t training_cells;  /* 2 Tr (2 Wd + 1): what a cell away from the gate edges trains on  */
+  uint32_t tile_rows;       /* the band of rows and ...                                         */
+  uint32_t tile_gates;      /* ... the tile of gates one workgroup takes                        */
+  uint32_t lds_bytes;       /* of one workgroup                                                 */
+  uint32_t reserved;        /* 0 */
+  char kernel[32];          /* the kernel that decides the cells                                */
+} pfb_rdcfar_plan;
+
+typedef struct pfb_rdcfar_det {  /* 32 bytes */
+  uint64_t map;                  /* m, since create or reset                                     */
+  uint32_t row, gate;            /* d as stored, r                                               */
+  float power, noise;            /* P[d][r]; the cell's noise                                    */
+  uint32_t training_cells;       /* (nL + nR) (2 Wd + 1)                                         */
+  uint32_t flags;                /* PFB_RDCFAR_DET_ONE_SIDED: nL + nR < 2 Tr                     */
+} pfb_rdcfar_det;
+
+typedef struct pfb_rdcfar_stats {
+  uint64_t maps_in;             /* maps taken since create or reset                              */
+  uint64_t cells_over;
+  uint64_t cells_without_noise; /* cells with nL = nR = 0                                        */
+  uint64_t detections;          /* reported cells, the dropped ones included                     */
+  uint64_t dropped;             /* records pfb_rdcfar_process_async had no room to write         */
+} pfb_rdcfar_stats;
+
+typedef struct pfb_rdcfar_handle pfb_rdcfar_handle;
+
+/* Host only: validate cfg (everything pfb_rdcfar_create checks before the device) and report the plan. */
+int pfb_rdcfar_describe(const pfb_rdcfar_config* cfg, pfb_rdcfar_plan* plan_out);
+/* Lifecycle as pfb_cfar_*.  pfb_cfar_alpha(pfa, 2 Tr (2 Wd + 1)) is the CA factor for a false-alarm rate. */
+int pfb_rdcfar_create(const pfb_rdcfar_config* cfg, pfb_rdcfar_handle** out);
+int pfb_rdcfar_destroy(pfb_rdcfar_handle* h);
+int pfb_rdcfar_reset(pfb_rdcfar_handle* h);   /* map index back to 0, stats zeroed */
+int pfb_rdcfar_set_stream(pfb_rdcfar_handle* h, void* hip_stream);
+int pfb_rdcfar_sync(pfb_rdcfar_handle* h);
+int pfb_rdcfar_get_device(const pfb_rdcfar_handle* h, int* device_id);
+int pfb_rdcfar_next_map(const pfb_rdcfar_handle* h, uint64_t* map_out);  /* m of the next map taken */
+/* Synchronises the handle's stream: the device keeps the counts that depend on the data. */
+int pfb_rdcfar_get_stats(pfb_rdcfar_handle* h, pfb_rdcfar_stats* stats_out);
+/* Take num_maps maps and write their detections, in order, to det_out (room for `capacity`); their number goes to
+ * *count_out.  PFB_ERR_CAPACITY sets *count_out to the number needed and changes no state (what det_out holds is then
+ * unspecified).  mem: maps and det_out are both host pointers (PFB_MEM_HOST) or both device pointers
+ * (PFB_MEM_DEVICE).  Synchronous. */
+int pfb_rdcfar_process(pfb_rdcfar_handle* h, const float* maps, uint64_t num_maps, pfb_rdcfar_det* det_out,
+                       uint64_t capacity, uint64_t* count_out, uint32_t mem);
+/* Device pointers, enqueued on the handle's stream without a host sync.  *d_count_out (a uint64 in device memory) is
+ * the number of detections of the call.  The first `capacity` records in order are written; the rest are counted in
+ * pfb_rdcfar_stats.dropped, and the state advances. */
+int pfb_rdcfar_process_async(pfb_rdcfar_handle* h, const float* d_maps, uint64_t num_maps, pfb_rdcfar_det* d_det_out,
+                             uint64_t capacity, uint64_t* d_count_out);
+/* Host only: detections as pulse descriptor words, so that pfb_event_fit takes them as it takes PDWs.  The maps are
+ * those of a pfb_pd_* with these pri, num_pulses and origin; `rows` is its ND and `centered` whether it wrote its rows
+ * with PFB_PD_CENTERED.  The signed bin of row d is d - floor(ND / 2) when centered, else d for d < ceil(ND / 2) and
+ * d - ND above.
+ *   toa = (origin + map * num_pulses * pri + gate + 1) / fs + sample_start_time: the train's first pulse of that
+ *   interval (pulse 0), in the extractors' 1-based convention
+ *   freq = fc + signed_bin * fs / (rows * pri)      bin = signed_bin
+ *   pw = 1 / fs      snr = 10 log10(power / noise)      mag = sqrt(power)      sat = 0
+ * PFB_ERR_BAD_ARG for null pointers (with n > 0), an fs that is not finite and > 0, a pri, num_pulses or rows of 0, or
+ * a record whose row is >= rows. */
+int pfb_rdcfar_to_pdw(const pfb_rdcfar_det* dets, uint64_t n, double fs, double fc, double sample_start_time,
+                      uint32_t pri, uint32_t num_pulses, uint64_t origin, uint32_t rows, uint32_t centered,
+                      pfb_pdw* pdw_out);
+/* The kernel the last call that took maps launched: plan.kernel; "" before the first. */
+const char* pfb_rdcfar_last_kernel(const pfb_rdcfar_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

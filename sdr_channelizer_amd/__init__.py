@@ -16,6 +16,8 @@ from .mf_bank import (MatchedFilterBank, bank_frequencies, compress_bank,  # noq
 from .pri_search import PriFold, describe_fold, find_pri, fold_z  # noqa: F401
 from .pulse_doppler import PulseDoppler, detect_pulse_train, doppler_frequencies, range_doppler  # noqa: F401
 from .pulse_source import PulseTrain, pulse_train, synth_params  # noqa: F401
+from .rd_cfar import RangeDopplerCfar, detect_maps, detect_targets  # noqa: F401
+from .rd_cfar import detections_to_pdws as targets_to_pdws  # noqa: F401
 from .stft import Stft, spectrogram_from_iq_file, stft, stft_axes  # noqa: F401
 from .synthesizer import (ChannelSynthesizer, design_synthesis_taps, isolate_band, synthesis_delay,  # noqa: F401
                           synthesize)
@@ -30,6 +32,7 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
            "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",
+           "RangeDopplerCfar", "detect_maps", "detect_targets", "targets_to_pdws",
            "PriFold", "find_pri", "fold_z", "describe_fold",
            "PulseDoppler", "range_doppler", "doppler_frequencies", "detect_pulse_train",
            "Cfar", "cfar_alpha", "detect", "detect_pulses", "pulse_detections_from_iq_file", "detections_to_pdws",

@@ -52,6 +52,7 @@ PFB_CFAR_CA, PFB_CFAR_GO, PFB_CFAR_SO = 0, 1, 2
 PFB_CFAR_DET_ONE_SIDED = 1
 PFB_PD_COMPLEX, PFB_PD_POWER, PFB_PD_BEST, PFB_PD_NONCOHERENT = 0, 1, 2, 3
 PFB_PD_CENTERED = 1
+PFB_RDCFAR_DET_ONE_SIDED = 1
 
 
 class PfbConfig(C.Structure):
@@ -228,6 +229,28 @@ class PfbFoldScore(C.Structure):
                 ("sum_means", C.c_double), ("sum_sq_means", C.c_double), ("cells", C.c_uint64)]
 
 
+class PfbRdcfarConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("rows", C.c_uint32), ("gates", C.c_uint32), ("pitch", C.c_uint32),
+                ("doppler_half_width", C.c_uint32), ("guard_gates", C.c_uint32), ("train_gates", C.c_uint32),
+                ("peak_half_width", C.c_uint32), ("method", C.c_uint32), ("alpha", C.c_float), ("min_power", C.c_float),
+                ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbRdcfarPlan(C.Structure):
+    _fields_ = [("training_cells", C.c_uint64), ("tile_rows", C.c_uint32), ("tile_gates", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("reserved", C.c_uint32), ("kernel", C.c_char * 32)]
+
+
+class PfbRdcfarDet(C.Structure):
+    _fields_ = [("map", C.c_uint64), ("row", C.c_uint32), ("gate", C.c_uint32), ("power", C.c_float),
+                ("noise", C.c_float), ("training_cells", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PfbRdcfarStats(C.Structure):
+    _fields_ = [("maps_in", C.c_uint64), ("cells_over", C.c_uint64), ("cells_without_noise", C.c_uint64),
+                ("detections", C.c_uint64), ("dropped", C.c_uint64)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -338,6 +361,9 @@ EXPORTS = (
     "pfb_fold_describe", "pfb_fold_counts", "pfb_fold_create", "pfb_fold_destroy", "pfb_fold_reset",
     "pfb_fold_set_stream", "pfb_fold_sync", "pfb_fold_get_device", "pfb_fold_next_index", "pfb_fold_process",
     "pfb_fold_process_async", "pfb_fold_scores", "pfb_fold_profile", "pfb_fold_last_kernel",
+    "pfb_rdcfar_describe", "pfb_rdcfar_create", "pfb_rdcfar_destroy", "pfb_rdcfar_reset", "pfb_rdcfar_set_stream",
+    "pfb_rdcfar_sync", "pfb_rdcfar_get_device", "pfb_rdcfar_next_map", "pfb_rdcfar_get_stats", "pfb_rdcfar_process",
+    "pfb_rdcfar_process_async", "pfb_rdcfar_to_pdw", "pfb_rdcfar_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -585,6 +611,21 @@ def load() -> C.CDLL:
     lib.pfb_fold_profile.argtypes = [vp, u32, vp, u64, u32]
     lib.pfb_fold_last_kernel.argtypes = [vp]
     lib.pfb_fold_last_kernel.restype = C.c_char_p
+    lib.pfb_rdcfar_describe.argtypes = [C.POINTER(PfbRdcfarConfig), C.POINTER(PfbRdcfarPlan)]
+    lib.pfb_rdcfar_create.argtypes = [C.POINTER(PfbRdcfarConfig), C.POINTER(vp)]
+    lib.pfb_rdcfar_destroy.argtypes = [vp]
+    lib.pfb_rdcfar_reset.argtypes = [vp]
+    lib.pfb_rdcfar_set_stream.argtypes = [vp, vp]
+    lib.pfb_rdcfar_sync.argtypes = [vp]
+    lib.pfb_rdcfar_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_rdcfar_next_map.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_rdcfar_get_stats.argtypes = [vp, C.POINTER(PfbRdcfarStats)]
+    lib.pfb_rdcfar_process.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_rdcfar_process_async.argtypes = [vp, vp, u64, vp, u64, vp]
+    lib.pfb_rdcfar_to_pdw.argtypes = [vp, u64, C.c_double, C.c_double, C.c_double, u32, u32, u64, u32, u32,
+                                      C.POINTER(PfbPdw)]
+    lib.pfb_rdcfar_last_kernel.argtypes = [vp]
+    lib.pfb_rdcfar_last_kernel.restype = C.c_char_p
     lib.pfb_fold_set_tier.argtypes = [vp, C.c_int]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
