@@ -1510,8 +1510,8 @@ const char* pfb_fold_last_kernel(const pfb_fold_handle* h);
  * maps, of at most 2^24 cells and 2^18 words of 64 gates (at least one map); a host-pointer call stages its maps in
  * those steps.
  *
- * Not built: OS-CFAR, guard rows in Doppler, joining adjacent reported cells into 2-D runs, a detector fused into
- * pfb_pd_*'s store.
+ * Not built: guard rows in Doppler, joining adjacent reported cells into 2-D runs, a detector fused into
+ * pfb_pd_*'s store.  (OS-CFAR is the unit of its own below, pfb_oscfar_*: DESIGN.md section 23.)
  *
  * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
  * struct_size, rows outside 1 .. 1024, gates outside 1 .. 2^20, a pitch that is neither 0 nor >= gates or with
@@ -1602,6 +1602,117 @@ int pfb_rdcfar_to_pdw(const pfb_rdcfar_det* dets, uint64_t n, double fs, double 
                       pfb_pdw* pdw_out);
 /* The kernel the last call that took maps launched: plan.kernel; "" before the first. */
 const char* pfb_rdcfar_last_kernel(const pfb_rdcfar_handle* h);
+
+/* ---- ordered-statistic CFAR over range-Doppler maps --------------------------------------------
+ * Every other detector here estimates a cell's noise as a mean, and a mean breaks when a second target stands in the
+ * training window: the interferer raises it and the weaker target disappears.  This unit takes the k-th smallest of
+ * the training cells instead (OS-CFAR): up to N - k interferers in a window leave the estimate where it was.  Input,
+ * geometry, decision, peak box, records (pfb_rdcfar_det, PFB_RDCFAR_DET_ONE_SIDED), stats (pfb_rdcfar_stats),
+ * capacity and async semantics are pfb_rdcfar_*'s; pfb_rdcfar_to_pdw takes its records unchanged.
+ * This comment is the definition: the device code (csrc/pfb_oscfar.hip) and the tests' restatement
+ * (tests/oscfar_ref.py) are each written from it.
+ *
+ * Input: maps P_m[d][r], float32, exactly as pfb_rdcfar_*: rows d = 0 .. ND-1 (1 .. 1024) are circular, gates r = 0 ..
+ * R-1 (1 .. 2^20) are not; the element lies at maps[(m' ND + d) pitch + r], pitch >= R (0 means R), ND pitch <= 2^26.
+ * Parameters: Wd (0 .. 16, 2 Wd + 1 <= ND), Gr (0 .. 1024), Tr (1 .. 256), Pd (0 .. 16, 2 Pd + 1 <= ND), alpha (float32,
+ * finite, > 0), min_power (float32, >= 0), and the rank k = 1 .. N, where N = 2 Tr (2 Wd + 1) is what a cell away from
+ * the gate edges trains on.  N must be <= 4096.
+ *
+ * Training set of cell (d, r): the values P[(d + j) mod ND][g] for j = -Wd .. Wd and g over the lead gates r-Gr-Tr ..
+ * r-Gr-1 that are >= 0 (nL of them) and the lag gates r+Gr+1 .. r+Gr+Tr that are < R (nR): n = (nL + nR)(2 Wd + 1)
+ * values.  With n = 0 the cell has no noise: it is never over, and it is counted in
+ * pfb_rdcfar_stats.cells_without_noise.
+ *
+ * Rank at the gate edges: k' = ceil(k n / N), in integers (k n + N - 1) / N: k' = k for a fully trained cell and
+ * 1 <= k' <= n otherwise.  The record's training_cells = n and PFB_RDCFAR_DET_ONE_SIDED (nL + nR < 2 Tr) tell which.
+ *
+ * Noise of the cell: the k'-th smallest training value under float32 `<`, where a NaN ranks after every number and
+ * -0 and +0 are equal.  Equivalently the smallest training value v with #{x_i <= v} >= k'; when there is none (fewer
+ * than k' values are numbers), the noise is NaN.  A zero is reported as +0.0, so the bytes are unique.  A NaN noise
+ * never detects, and the cell is NOT counted in cells_without_noise.
+ *
+ * Decision: over = (p > alpha * noise) && (p > min_power), p = P[d][r], the product one float32 multiply.  Because
+ * alpha > 0 and a float32 multiply is monotone, p > alpha * noise holds exactly when at least k' training values
+ * satisfy alpha * x_i < p (a NaN compares false): an implementation may decide by counting and select the noise only
+ * for the cells that are over.
+ *
+ * Detection, peak box, ties and record order: pfb_rdcfar_*'s, word for word.  The box is the rows d-Pd .. d+Pd
+ * (circular) by the gates r-Gr .. r+Gr (clipped); q beats p iff P_q > P_p, or P_q == P_p and q's (row, gate) is lower
+ * in row-major order; a NaN neighbour beats nothing.  One pfb_rdcfar_det per reported cell (noise: the order
+ * statistic), in ascending (map, row, gate).
+ *
+ * Invariance: every figure is a function of one map, so ANY CUTTING OF A SEQUENCE OF MAPS INTO CALLS GIVES THE SAME
+ * BYTES.  The noise is a rank, not a sum: THE ORDER IN WHICH THE TRAINING CELLS ARE VISITED IS FREE, and a sliding or
+ * shared evaluation is allowed.  No atomics; the records are placed by counts and a scan.
+ *
+ * Cost: a cell reads at most its n training values once to decide; an over cell has them read 32 times more to select
+ * its noise (a bitwise search on an order-preserving integer key, shared out over its wave) and walks its peak box in
+ * one lane: slow only for maps that are all detections.  Steps and host staging as pfb_rdcfar_*.
+ *
+ * pfb_oscfar_alpha: for independent exponentially distributed cells (power of complex Gaussian noise) the k-th of N
+ * gives P(over) = prod_{i=0}^{k-1} (N - i) / (N - i + alpha); the factor is the root of that product = pfa.
+ *
+ * Not built: OS in the block detector pfb_cfar_*, trimmed or censored means, guard rows in Doppler, a detector fused
+ * into pfb_pd_*'s store.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, rows outside 1 .. 1024, gates outside 1 .. 2^20, a pitch that is neither 0 nor >= gates or with
+ * rows pitch > 2^26, doppler_half_width > 16 or 2 Wd + 1 > rows, guard_gates > 1024, train_gates outside 1 .. 256,
+ * peak_half_width > 16 or 2 Pd + 1 > rows, N = 2 Tr (2 Wd + 1) > 4096, a rank outside 1 .. N, an alpha that is not
+ * finite or <= 0, a min_power that is negative or NaN, flags != 0; per call an unknown mem, num_maps > 2^40,
+ * capacity > 2^56, a device pointer not aligned to its element (4 bytes for maps, 8 for records and the async count).
+ * Then PFB_ERR_NO_DEVICE without a HIP device. */
+typedef struct pfb_oscfar_config {
+  uint32_t struct_size;         /* = sizeof(pfb_oscfar_config)                                  */
+  uint32_t rows;                /* ND                                                           */
+  uint32_t gates;               /* R                                                            */
+  uint32_t pitch;               /* floats from one row to the next; 0 = gates                   */
+  uint32_t doppler_half_width;  /* Wd                                                           */
+  uint32_t guard_gates;         /* Gr                                                           */
+  uint32_t train_gates;         /* Tr, per side                                                 */
+  uint32_t peak_half_width;     /* Pd                                                           */
+  uint32_t rank;                /* k = 1 .. 2 Tr (2 Wd + 1)                                     */
+  float alpha;
+  float min_power;
+  uint32_t flags;               /* 0                                                            */
+  int32_t device_id;            /* -1 = the current device                                      */
+} pfb_oscfar_config;
+
+typedef struct pfb_oscfar_plan { /* what pfb_oscfar_describe reports; host only                  */
+  uint64_t training_cells;  /* N = 2 Tr (2 Wd + 1)                                              */
+  uint32_t tile_rows;       /* the band of rows and ...                                         */
+  uint32_t tile_gates;      /* ... the tile of gates one workgroup takes                        */
+  uint32_t lds_bytes;       /* of one workgroup; 0 when the maps are read through the caches    */
+  uint32_t reserved;        /* 0 */
+  char kernel[32];          /* the kernel that decides the cells                                */
+} pfb_oscfar_plan;
+
+typedef struct pfb_oscfar_handle pfb_oscfar_handle;
+
+/* Host only: validate cfg (everything pfb_oscfar_create checks before the device) and report the plan. */
+int pfb_oscfar_describe(const pfb_oscfar_config* cfg, pfb_oscfar_plan* plan_out);
+/* Host only: the factor alpha for a false-alarm rate pfa with rank k of N training cells, solved in float64 by
+ * bisection on the logarithm of the product above.  PFB_ERR_BAD_ARG for a null pointer, a pfa outside (0, 1),
+ * training_cells = 0 or > 2^20, or a rank outside 1 .. training_cells. */
+int pfb_oscfar_alpha(double pfa, uint64_t training_cells, uint64_t rank, double* alpha_out);
+/* Lifecycle, calls and stats as pfb_rdcfar_*. */
+int pfb_oscfar_create(const pfb_oscfar_config* cfg, pfb_oscfar_handle** out);
+int pfb_oscfar_destroy(pfb_oscfar_handle* h);
+int pfb_oscfar_reset(pfb_oscfar_handle* h);   /* map index back to 0, stats zeroed */
+int pfb_oscfar_set_stream(pfb_oscfar_handle* h, void* hip_stream);
+int pfb_oscfar_sync(pfb_oscfar_handle* h);
+int pfb_oscfar_get_device(const pfb_oscfar_handle* h, int* device_id);
+int pfb_oscfar_next_map(const pfb_oscfar_handle* h, uint64_t* map_out);  /* m of the next map taken */
+/* Synchronises the handle's stream: the device keeps the counts that depend on the data. */
+int pfb_oscfar_get_stats(pfb_oscfar_handle* h, pfb_rdcfar_stats* stats_out);
+/* As pfb_rdcfar_process: PFB_ERR_CAPACITY sets *count_out to the number needed and changes no state.  Synchronous. */
+int pfb_oscfar_process(pfb_oscfar_handle* h, const float* maps, uint64_t num_maps, pfb_rdcfar_det* det_out,
+                       uint64_t capacity, uint64_t* count_out, uint32_t mem);
+/* As pfb_rdcfar_process_async: device pointers, no host sync; what does not fit is counted in stats.dropped. */
+int pfb_oscfar_process_async(pfb_oscfar_handle* h, const float* d_maps, uint64_t num_maps, pfb_rdcfar_det* d_det_out,
+                             uint64_t capacity, uint64_t* d_count_out);
+/* The kernel the last call that took maps launched: plan.kernel; "" before the first. */
+const char* pfb_oscfar_last_kernel(const pfb_oscfar_handle* h);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@ from .matched_filter import (MatchedFilter, compress, compress_iq_file, pulse_de
                              replica_from_pulse_train)
 from .mf_bank import (MatchedFilterBank, bank_frequencies, compress_bank,  # noqa: F401
                       pulse_delay_and_offset_from_iq_files)
+from .os_cfar import OsCfar, detect_maps_os, os_cfar_alpha  # noqa: F401
 from .pri_search import PriFold, describe_fold, find_pri, fold_z  # noqa: F401
 from .pulse_doppler import PulseDoppler, detect_pulse_train, doppler_frequencies, range_doppler  # noqa: F401
 from .pulse_source import PulseTrain, pulse_train, synth_params  # noqa: F401
@@ -32,6 +33,7 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
            "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",
+           "OsCfar", "os_cfar_alpha", "detect_maps_os",
            "RangeDopplerCfar", "detect_maps", "detect_targets", "targets_to_pdws",
            "PriFold", "find_pri", "fold_z", "describe_fold",
            "PulseDoppler", "range_doppler", "doppler_frequencies", "detect_pulse_train",

@@ -251,6 +251,18 @@ class PfbRdcfarStats(C.Structure):
                 ("detections", C.c_uint64), ("dropped", C.c_uint64)]
 
 
+class PfbOscfarConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("rows", C.c_uint32), ("gates", C.c_uint32), ("pitch", C.c_uint32),
+                ("doppler_half_width", C.c_uint32), ("guard_gates", C.c_uint32), ("train_gates", C.c_uint32),
+                ("peak_half_width", C.c_uint32), ("rank", C.c_uint32), ("alpha", C.c_float), ("min_power", C.c_float),
+                ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbOscfarPlan(C.Structure):
+    _fields_ = [("training_cells", C.c_uint64), ("tile_rows", C.c_uint32), ("tile_gates", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("reserved", C.c_uint32), ("kernel", C.c_char * 32)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -364,6 +376,9 @@ EXPORTS = (
     "pfb_rdcfar_describe", "pfb_rdcfar_create", "pfb_rdcfar_destroy", "pfb_rdcfar_reset", "pfb_rdcfar_set_stream",
     "pfb_rdcfar_sync", "pfb_rdcfar_get_device", "pfb_rdcfar_next_map", "pfb_rdcfar_get_stats", "pfb_rdcfar_process",
     "pfb_rdcfar_process_async", "pfb_rdcfar_to_pdw", "pfb_rdcfar_last_kernel",
+    "pfb_oscfar_describe", "pfb_oscfar_alpha", "pfb_oscfar_create", "pfb_oscfar_destroy", "pfb_oscfar_reset",
+    "pfb_oscfar_set_stream", "pfb_oscfar_sync", "pfb_oscfar_get_device", "pfb_oscfar_next_map", "pfb_oscfar_get_stats",
+    "pfb_oscfar_process", "pfb_oscfar_process_async", "pfb_oscfar_last_kernel",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
@@ -626,6 +641,20 @@ def load() -> C.CDLL:
                                       C.POINTER(PfbPdw)]
     lib.pfb_rdcfar_last_kernel.argtypes = [vp]
     lib.pfb_rdcfar_last_kernel.restype = C.c_char_p
+    lib.pfb_oscfar_describe.argtypes = [C.POINTER(PfbOscfarConfig), C.POINTER(PfbOscfarPlan)]
+    lib.pfb_oscfar_alpha.argtypes = [C.c_double, u64, u64, C.POINTER(C.c_double)]
+    lib.pfb_oscfar_create.argtypes = [C.POINTER(PfbOscfarConfig), C.POINTER(vp)]
+    lib.pfb_oscfar_destroy.argtypes = [vp]
+    lib.pfb_oscfar_reset.argtypes = [vp]
+    lib.pfb_oscfar_set_stream.argtypes = [vp, vp]
+    lib.pfb_oscfar_sync.argtypes = [vp]
+    lib.pfb_oscfar_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_oscfar_next_map.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_oscfar_get_stats.argtypes = [vp, C.POINTER(PfbRdcfarStats)]
+    lib.pfb_oscfar_process.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_oscfar_process_async.argtypes = [vp, vp, u64, vp, u64, vp]
+    lib.pfb_oscfar_last_kernel.argtypes = [vp]
+    lib.pfb_oscfar_last_kernel.restype = C.c_char_p
     lib.pfb_fold_set_tier.argtypes = [vp, C.c_int]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []

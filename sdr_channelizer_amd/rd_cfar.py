@@ -63,6 +63,11 @@ class RangeDopplerCfar(Handle):
     they are a view of wider ones."""
 
     _kind, _destroy, _get_device = "range-Doppler CFAR detector", "pfb_rdcfar_destroy", "pfb_rdcfar_get_device"
+    _abi = "pfb_rdcfar_"   # the entry points a subclass with the same calls (OsCfar) goes through instead
+
+    def _run(self, name: str, *args) -> int:
+        """Call the handle's entry point ``name`` (without the unit's prefix) and return its status."""
+        return getattr(self._lib, self._abi + name)(self._h, *args)
 
     def __init__(self, rows: int, gates: int, doppler_half_width: int, guard_gates: int, train_gates: int,
                  alpha: float | None = None, *, pfa: float | None = None, peak_half_width: int = 0, method: str = "ca",
@@ -84,29 +89,29 @@ class RangeDopplerCfar(Handle):
         self._capacity = 1024
 
     def reset(self) -> None:
-        L.check(self._lib.pfb_rdcfar_reset(self._h), "pfb_rdcfar_reset")
+        L.check(self._run("reset"), self._abi + "reset")
 
     def set_stream(self, hip_stream: int) -> None:
-        L.check(self._lib.pfb_rdcfar_set_stream(self._h, C.c_void_p(hip_stream)), "pfb_rdcfar_set_stream")
+        L.check(self._run("set_stream", C.c_void_p(hip_stream)), self._abi + "set_stream")
 
     def sync(self) -> None:
-        L.check(self._lib.pfb_rdcfar_sync(self._h), "pfb_rdcfar_sync")
+        L.check(self._run("sync"), self._abi + "sync")
 
     @property
     def last_kernel(self) -> str:
-        return self._lib.pfb_rdcfar_last_kernel(self._h).decode()
+        return getattr(self._lib, self._abi + "last_kernel")(self._h).decode()
 
     @property
     def next_map(self) -> int:
         """Index of the next map to be taken, counted since construction or reset."""
         m = C.c_uint64()
-        L.check(self._lib.pfb_rdcfar_next_map(self._h, C.byref(m)), "pfb_rdcfar_next_map")
+        L.check(self._run("next_map", C.byref(m)), self._abi + "next_map")
         return int(m.value)
 
     @property
     def stats(self) -> dict:
         s = L.PfbRdcfarStats()
-        L.check(self._lib.pfb_rdcfar_get_stats(self._h, C.byref(s)), "pfb_rdcfar_get_stats")
+        L.check(self._run("get_stats", C.byref(s)), self._abi + "get_stats")
         return {name: int(getattr(s, name)) for name, _ in L.PfbRdcfarStats._fields_}
 
     # -- maps ----------------------------------------------------------------------
@@ -153,16 +158,16 @@ class RangeDopplerCfar(Handle):
         """Take maps of shape (maps, rows, gates) -- or one (rows, gates) map; returns their detections."""
         if is_torch(x) and x.is_cuda:
             n = self._device_maps(x)
-            rc, out = self._call(lambda p, cap, cnt: self._lib.pfb_rdcfar_process(
-                self._h, C.c_void_p(x.data_ptr()), n, p, cap, cnt, L.PFB_MEM_DEVICE), x.device)
+            rc, out = self._call(lambda p, cap, cnt: self._run(
+                "process", C.c_void_p(x.data_ptr()), n, p, cap, cnt, L.PFB_MEM_DEVICE), x.device)
         else:
             a = np.asarray(x)
             if a.dtype != np.float32:
                 raise TypeError(f"expected float32 maps for this {self._kind}, got {a.dtype}")
             n = self._maps(a.shape, tuple(s // 4 for s in a.strides))
-            rc, out = self._call(lambda p, cap, cnt: self._lib.pfb_rdcfar_process(
-                self._h, C.c_void_p(a.ctypes.data), n, p, cap, cnt, L.PFB_MEM_HOST), None)
-        L.check(rc, "pfb_rdcfar_process")
+            rc, out = self._call(lambda p, cap, cnt: self._run(
+                "process", C.c_void_p(a.ctypes.data), n, p, cap, cnt, L.PFB_MEM_HOST), None)
+        L.check(rc, self._abi + "process")
         return out
 
     __call__ = process
@@ -179,9 +184,8 @@ class RangeDopplerCfar(Handle):
                 raise ValueError(f"{what} must be a contiguous int64 tensor on cuda:{self.device_index}")
         if out.numel() % _WORDS or count.numel() < 1:
             raise ValueError(f"out holds records of {_WORDS} int64 words, count one element")
-        L.check(self._lib.pfb_rdcfar_process_async(self._h, C.c_void_p(x.data_ptr()), n, C.c_void_p(out.data_ptr()),
-                                                   out.numel() // _WORDS, C.c_void_p(count.data_ptr())),
-                "pfb_rdcfar_process_async")
+        L.check(self._run("process_async", C.c_void_p(x.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                          out.numel() // _WORDS, C.c_void_p(count.data_ptr())), self._abi + "process_async")
 
 
 def detect_maps(maps, doppler_half_width: int, guard_gates: int, train_gates: int, alpha: float | None = None, *,
@@ -208,7 +212,7 @@ def detect_targets(iq, replica, pri: int, num_pulses: int, *, pfa: float | None 
                    doppler_half_width: int = 1, guard_gates: int | None = None, train_gates: int = 64,
                    peak_half_width: int = 1, method: str = "ca", min_power: float = 0.0, fs: float = 1.0,
                    sample_format: str | None = None, bit_width: int = 12, normalize: bool = False,
-                   chunk_samples: int = 1 << 22, device: int = -1) -> np.ndarray:
+                   chunk_samples: int = 1 << 22, device: int = -1, rank: int | None = None) -> np.ndarray:
     """The targets of an I/Q stream that match ``replica`` and repeat every ``pri`` samples: a ``MatchedFilter``
     (complex output) feeds a ``PulseDoppler`` (power maps, centered), whose intervals go, all those of a chunk in one
     call, through a ``RangeDopplerCfar`` -- chunk by chunk on the device; neither the compressed stream nor the maps
@@ -220,6 +224,11 @@ def detect_targets(iq, replica, pri: int, num_pulses: int, *, pfa: float | None 
     correlates adjacent rows, so the training cells count for fewer than their number and the rate lies above ``pfa``
     (the header and DESIGN.md section 22).  Two trains in one gate on different Doppler rows give two records per
     interval.
+
+    ``rank``: with an integer k the chain's detector is an ``OsCfar`` that takes the k-th smallest of the 2 *
+    train_gates * (2 * doppler_half_width + 1) training cells as the noise (``method`` is then unused, and ``pfa`` means
+    the ordered-statistic factor os_cfar_alpha(pfa, cells, k)): a second train in the first one's training window no
+    longer hides the weaker one.  With None nothing changes.
 
     Returns TARGET_DTYPE records in ascending (cpi, row, gate): the interval, the gate (the train's first sample is
     origin + gate, modulo pri), the row as stored, the signed Doppler bin and its frequency bin * fs /
@@ -235,11 +244,18 @@ def detect_targets(iq, replica, pri: int, num_pulses: int, *, pfa: float | None 
     Gr = r.size if guard_gates is None else int(guard_gates)
     fmt = sample_format or _format_of(iq)
     found = []
+
+    def detector(rows, dev_index):
+        if rank is None:
+            return RangeDopplerCfar(rows, R, doppler_half_width, Gr, train_gates, alpha, pfa=pfa,
+                                    peak_half_width=peak_half_width, method=method, min_power=min_power, device=dev_index)
+        from .os_cfar import OsCfar
+        return OsCfar(rows, R, doppler_half_width, Gr, train_gates, int(rank), alpha, pfa=pfa,
+                      peak_half_width=peak_half_width, min_power=min_power, device=dev_index)
+
     with MatchedFilter(r, fmt, bit_width, "complex", normalize, device=device) as mf, \
             PulseDoppler(pri, num_pulses, R, origin, window, doppler_length, "power", True, device=mf.device_index) as pd, \
-            RangeDopplerCfar(pd.doppler_length, R, doppler_half_width, Gr, train_gates, alpha, pfa=pfa,
-                             peak_half_width=peak_half_width, method=method, min_power=min_power,
-                             device=mf.device_index) as det:
+            detector(pd.doppler_length, mf.device_index) as det:
         ND = pd.doppler_length
         dev = torch.device("cuda", mf.device_index)
         on_device = is_torch(iq) and iq.is_cuda
