@@ -18,14 +18,12 @@ import pd_cases  # noqa: E402
 import rdcfar_cases  # noqa: E402
 import rdcfar_ref as R  # noqa: E402
 from gpu_support import Busy, cuda_torch  # noqa: E402
+from rdmap_support import SENTINEL, place, run_async  # noqa: E402
 from sdr_channelizer_amd import (MatchedFilter, OsCfar, cfar_alpha, detect_maps, detect_maps_os, detect_targets,  # noqa: E402
                                  os_cfar_alpha, range_doppler, targets_to_pdws)
 from sdr_channelizer_amd import _lib as L  # noqa: E402
 from sdr_channelizer_amd import os_cfar, rd_cfar  # noqa: E402
 from sdr_channelizer_amd.rd_cfar import DET_DTYPE, TARGET_DTYPE, records  # noqa: E402
-
-SENTINEL = 0x5A5A5A5A5A5A5A5A
-
 
 @pytest.fixture(scope="module")
 def torch():
@@ -34,31 +32,6 @@ def torch():
 
 def cells(det):
     return [(int(d["row"]), int(d["gate"])) for d in det]
-
-
-def place(torch, maps, pitch=0, offset=0):
-    """the maps on the device as a view with `pitch` floats from row to row, its first cell `offset` cells off a
-    256-byte boundary; what lies between the rows is NaN"""
-    n, ND, Rg = maps.shape
-    pitch = pitch or Rg
-    flat = torch.full((offset + max(n, 1) * ND * pitch + 64,), float("nan"), dtype=torch.float32, device="cuda")
-    assert flat.data_ptr() % 256 == 0
-    view = flat[offset:].as_strided((n, ND, Rg), (ND * pitch, pitch, 1))
-    view.copy_(torch.from_numpy(maps))
-    return view
-
-
-def run_async(torch, det, x, capacity):
-    """(records, count) of one pfb_oscfar_process_async call, with guard words around the records and the count"""
-    out = torch.full((capacity + 2, 4), SENTINEL, dtype=torch.int64, device="cuda")
-    count = torch.full((3,), SENTINEL, dtype=torch.int64, device="cuda")
-    det.process_async(x, out[1:capacity + 1], count[1:2])
-    det.sync()
-    n = int(count[1].item())
-    assert int(count[0].item()) == int(count[2].item()) == SENTINEL
-    assert (out[0] == SENTINEL).all() and (out[capacity + 1] == SENTINEL).all()
-    assert (out[1 + min(n, capacity):] == SENTINEL).all()          # nothing behind the last record
-    return records(out[1:1 + min(n, capacity)]), n
 
 
 def check(torch, maps, Wd, Gr, Tr, Pd, ranks, alpha=4.0, min_power=0.0, pitch=0, offset=0, kernel=None):
