@@ -1714,6 +1714,156 @@ int pfb_oscfar_process_async(pfb_oscfar_handle* h, const float* d_maps, uint64_t
 /* The kernel the last call that took maps launched: plan.kernel; "" before the first. */
 const char* pfb_oscfar_last_kernel(const pfb_oscfar_handle* h);
 
+/* ---- PDW deinterleaver: emitters from arrival times ---------------------------------------------
+ * Every detector here ends in one time-ordered table of pulses; a record off the air holds several emitters whose
+ * pulses arrive interleaved.  This unit takes the table apart: a difference histogram of the arrival times proposes
+ * periods, a sequence search pulls the train of the best one out, and the rest goes round again until nothing is
+ * left.  pfb_fold_* finds the period of a train too weak to give arrival times; this unit is for pulses that have them.
+ * Every figure is an integer (one IEEE division apart), so the results are bytes, not tolerances.
+ * This comment is the definition: the device code (csrc/pfb_deint.hip) and the tests' restatement
+ * (tests/deint_ref.py) are each written from it.
+ *
+ * Input: t[0 .. N), uint64 arrival ticks in non-decreasing order (duplicates allowed), N <= 2^20, every tick < 2^62,
+ * in host or device memory by `mem` (a device pointer is 8-byte aligned).  A tick is the caller's clock: the
+ * peak_index of a pfb_cfar_det, a PDW's toa turned into frames (pfb_deint_ticks_from_toa).
+ *
+ * Parameters: pmin = min_period, pmax = max_period (1 <= pmin <= pmax <= 2^31), W = bin_ticks (>= 1, with NB =
+ * (pmax - pmin) / W + 1 <= 65536 bins), Lv = max_level (1 .. 256), detect_percent (1 .. 100), min_pulses (3 .. 2^20),
+ * X = max_missing (0 .. 8), e = tolerance (0 means W; e (2 X + 3) < pmin keeps the X + 1 search windows of one pulse
+ * apart), fill_percent (1 .. 100), max_emitters (1 .. 1024).
+ *
+ * A round works on the ALIVE pulses, those not yet assigned, in their order: a[0 .. n), a[q] = t[idx[q]].
+ *  1. Histogram: every pair (i, j) with 1 <= j - i <= Lv and d = a[j] - a[i] in [pmin, pmax] adds 1 to
+ *     C[(d - pmin) / W], C uint32.  A count of a set: the order is free.
+ *  2. Candidates, k ascending, a missing neighbour taken as 0: bin k is a candidate iff C[k] > C[k-1], C[k] >= C[k+1]
+ *     and S_k = C[k-1] + C[k] + C[k+1] >= max(min_pulses - 1, ceil(floor(span / tau_k) detect_percent / 100)), with
+ *     tau_k = pmin + k W + W / 2 (integer division) and span = a[n-1] - a[0].  Ascending order is the subharmonic
+ *     rule: the bin at 2 tau is reached only after tau has been tried and its train removed.
+ *  3. Successor of alive pulse i at period tau: for m = 0 .. X in turn the target is a[i] + (m + 1) tau and the window
+ *     target -+ (m + 1) e, inclusive.  Among the alive j > i inside the window the one with the smallest
+ *     |a[j] - target| is taken, ties to the lowest j.  The first m that finds one gives succ(i) = j, step(i) = m + 1;
+ *     if none does there is no successor.
+ *  4. Chains: len(i) = 1 + len(succ(i)), per(i) = step(i) + per(succ(i)), end(i) = end(succ(i)); without a successor
+ *     1, 0 and i.  The best start b is the i of largest len, ties to the lowest i.  The candidate is ACCEPTED iff
+ *     len(b) >= min_pulses and 100 (len(b) - 1) >= fill_percent per(b): the fill rule refuses the sparse chains that
+ *     a fraction of a real period strings together through the miss windows.  A refused candidate gives way to the
+ *     next one of the same histogram.
+ *  5. Extraction: the pulses of b's chain get label E, the index of the record, and leave the alive set; one
+ *     pfb_deint_emitter is written; the next round begins with a new histogram.
+ * The run ends when fewer than min_pulses pulses are alive (no histogram is built then), when no candidate of a
+ * round is accepted, or when max_emitters records exist.
+ *
+ * Output: labels, int32, one per input pulse, -1 for unassigned; records in extraction order.  Both are pure
+ * functions of the list and the config: THE SAME CALL TWICE, AND HOST AND DEVICE INPUT, GIVE THE SAME BYTES.  Integer
+ * adds commute, so the histogram may use integer atomics; there are no float atomics.
+ *
+ * Stats of the last run: rounds = histograms built, candidates_tried = successor searches made, candidates_refused =
+ * those not accepted, pulses_assigned = the sum of the records' pulses.
+ *
+ * Tiers.  Histogram: a workgroup stages tiles of 1024 consecutive alive ticks plus Lv more in LDS and its lanes take
+ * (i, level) pairs; for NB <= 8192 (pfb_deint_plan.lds_bins) it counts in a private LDS histogram that it adds to the
+ * global one once (pfb_deint_hist_lds), above that straight into the global one (pfb_deint_hist_global).  Successors:
+ * one lane per alive pulse (pfb_deint_succ).  Chains: pointer doubling over (succ, len, per), an argmax and a marking
+ * pass that reads the kept jump tables of the doubling rounds (pfb_deint_mark_tables) or, by pfb_deint_set_tier, walks
+ * b's chain in one lane (pfb_deint_mark_walk).  pfb_deint_last_kernel joins the names of what the last call launched with '+'.
+ *
+ * Not built: an async form (the decision of every round returns to the host), staggered, jittered-by-design or
+ * sliding PRIs, frequency or pulse-width clustering before the time search (split the table by `bin` first), a
+ * streaming form over PDW chunks, the PRI transform's phase weighting, a histogram fused into the detectors' emit.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, min_period = 0, max_period < min_period or > 2^31, bin_ticks = 0, NB > 65536, max_level outside
+ * 1 .. 256, detect_percent outside 1 .. 100, min_pulses outside 3 .. 2^20, max_missing > 8, e (2 X + 3) >= pmin,
+ * fill_percent outside 1 .. 100, max_emitters outside 1 .. 1024, flags != 0; per call a null handle, an unknown mem,
+ * n > 2^20, a null ticks with n > 0, a null output (labels_out may be null only with n = 0), a device pointer not
+ * aligned to its element (8 bytes for ticks and records, 4 for labels, counts and the successor arrays), and for
+ * pfb_deint_successors a period outside 1 .. 2^32 - 1 or with e (2 X + 3) >= period.  PFB_ERR_CAPACITY: capacity_bins
+ * < NB.  Then PFB_ERR_NO_DEVICE without a HIP device.  The order of the ticks and their bound 2^62 are checked on the
+ * device, in the first pass over the list: a list that fails returns PFB_ERR_BAD_ARG with nothing written. */
+typedef struct pfb_deint_config {
+  uint32_t struct_size;     /* = sizeof(pfb_deint_config)                                       */
+  uint32_t min_period;      /* pmin, ticks                                                      */
+  uint32_t max_period;      /* pmax                                                             */
+  uint32_t bin_ticks;       /* W                                                                */
+  uint32_t max_level;       /* Lv: differences up to the Lv-th neighbour                        */
+  uint32_t detect_percent;  /* of the span / tau pairs a full train would give                  */
+  uint32_t min_pulses;      /* of a train                                                       */
+  uint32_t max_missing;     /* X: pulses in a row a chain may step over                         */
+  uint32_t tolerance;       /* e, ticks per period stepped; 0 = W                               */
+  uint32_t fill_percent;    /* hits per period a chain must reach                               */
+  uint32_t max_emitters;    /* records after which the run ends                                 */
+  uint32_t flags;           /* 0                                                                */
+  int32_t device_id;        /* -1 = the current device                                          */
+} pfb_deint_config;
+
+typedef struct pfb_deint_plan { /* what pfb_deint_describe reports; host only                     */
+  uint64_t scratch_bytes;     /* device memory a handle holds after pfb_deint_run on n pulses     */
+  uint32_t num_bins;          /* NB                                                               */
+  uint32_t lds_bins;          /* the largest NB the LDS tier takes                                */
+  uint32_t tile_pulses;       /* alive pulses of one histogram tile (Lv more are staged)          */
+  uint32_t lds_bytes;         /* of one histogram workgroup                                       */
+  uint32_t successor_threads; /* lanes of one workgroup of the successor kernel                   */
+  uint32_t reserved;          /* 0 */
+  char histogram_kernel[32];
+  char successor_kernel[32];
+  char marking_kernel[32];
+} pfb_deint_plan;
+
+typedef struct pfb_deint_emitter {  /* 48 bytes */
+  uint64_t first_tick;        /* a[b]                                                             */
+  uint64_t last_tick;         /* a[end(b)]                                                        */
+  double period;              /* (double)(last_tick - first_tick) / (double)periods: one division */
+  uint32_t pulses;            /* len(b)                                                           */
+  uint32_t periods;           /* per(b): periods from the first pulse to the last                 */
+  uint32_t bin;               /* k of the candidate                                               */
+  uint32_t candidate_period;  /* tau_k                                                            */
+  uint32_t first_pulse;       /* index of the first pulse in the caller's list                    */
+  uint32_t hist_count;        /* S_k                                                              */
+} pfb_deint_emitter;
+
+typedef struct pfb_deint_stats {
+  uint64_t rounds;
+  uint64_t candidates_tried;
+  uint64_t candidates_refused;
+  uint64_t pulses_assigned;
+} pfb_deint_stats;
+
+typedef struct pfb_deint_handle pfb_deint_handle;
+
+/* Host only: validate cfg (everything pfb_deint_create checks before the device) and report the plan for a list of
+ * n pulses (n > 2^20: PFB_ERR_BAD_ARG). */
+int pfb_deint_describe(const pfb_deint_config* cfg, uint64_t n, pfb_deint_plan* plan_out);
+/* Lifecycle as pfb_fold_*.  The scratch grows with the longest list seen and is kept. */
+int pfb_deint_create(const pfb_deint_config* cfg, pfb_deint_handle** out);
+int pfb_deint_destroy(pfb_deint_handle* h);
+int pfb_deint_set_stream(pfb_deint_handle* h, void* hip_stream);
+int pfb_deint_sync(pfb_deint_handle* h);
+int pfb_deint_get_device(const pfb_deint_handle* h, int* device_id);
+/* The whole search.  emitters_out (capacity records) and labels_out (n int32) are host memory, or device memory with
+ * mem = PFB_MEM_DEVICE; *count_out (host) is the number of records found.  PFB_ERR_CAPACITY when that is more than
+ * capacity: *count_out holds the true count, neither array is written and the stats stay those of the run before.
+ * Synchronous. */
+int pfb_deint_run(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, pfb_deint_emitter* emitters_out,
+                  uint64_t capacity, uint64_t* count_out, int32_t* labels_out);
+/* Step 1 alone on the whole list: NB uint32 counts, for plots and for the tests.  Changes no stats. */
+int pfb_deint_histogram(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, uint32_t* counts_out,
+                        uint64_t capacity_bins);
+/* Steps 3 and 4 alone on the whole list at one period: succ(i) (-1 for none), step(i) (0 for none) and len(i), n
+ * int32 each.  Changes no stats. */
+int pfb_deint_successors(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, uint64_t period,
+                         int32_t* succ_out, int32_t* step_out, int32_t* len_out);
+/* The kernels the last call launched, joined with '+'; "" before the first and after a call that launched none. */
+const char* pfb_deint_last_kernel(const pfb_deint_handle* h);
+/* The stats of the last pfb_deint_run that returned PFB_OK; zeros before the first. */
+int pfb_deint_get_stats(const pfb_deint_handle* h, pfb_deint_stats* stats_out);
+/* Host only: tick = llrint((toa - t0) tick_rate) of the n doubles at toa, stride_bytes apart (8 for a plain array,
+ * sizeof(pfb_pdw) to walk a pfb_pdw array's toa field in place), sorted ascending and stably: ticks_out[i] is the tick
+ * of element order_out[i].  PFB_ERR_BAD_ARG for null pointers, stride_bytes < 8, n > 2^31, a tick_rate that is not
+ * finite or <= 0, a t0 that is not finite, a toa that is not finite, a negative tick or one >= 2^62; nothing is
+ * written then. */
+int pfb_deint_ticks_from_toa(const double* toa, uint64_t stride_bytes, uint64_t n, double t0, double tick_rate,
+                             uint64_t* ticks_out, uint32_t* order_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,14 @@ int pfb_stft_set_experiment(pfb_stft_handle* h, int experiment);
  * bin_cells is not 8, 16, 32 or 64; PFB_ERR_BAD_ARG for any other value.  pfb_fold_last_kernel names what ran. */
 int pfb_fold_set_tier(pfb_fold_handle* h, int tier);
 
+/* Which kernels the next calls of a pfb_deint handle run.  histogram_tier: 0 = the library's choice
+ * (pfb_deint_plan.histogram_kernel), 1 = the private LDS histogram (PFB_ERR_UNSUPPORTED when NB is above
+ * pfb_deint_plan.lds_bins), 2 = global atomics.  marking_tier: 0 = the library's choice (the kept doubling
+ * tables), 1 = the walk along b's chain in one lane, 2 = the tables.  All give the same bytes; the tests run one list
+ * through them, the meter (tools/deint_rate.py) times them.  PFB_ERR_BAD_ARG for any other value.
+ * pfb_deint_last_kernel names what ran. */
+int pfb_deint_set_tier(pfb_deint_handle* h, int histogram_tier, int marking_tier);
+
 /* The fused-kernel table, row by row in lookup order (host only, no device needed): what the tests walk, so that a
  * registered plan cannot go untested.  Rows of one (M, P, D, sample_format) are that shape's variants 0, 1, ... */
 typedef struct {

@@ -8,6 +8,8 @@ from ._lib import LIB_PATH, PfbError  # noqa: F401
 from .cfar import (Cfar, cfar_alpha, detect, detect_pulses, detections_to_pdws,  # noqa: F401
                    pulse_detections_from_iq_file)
 from .channelizer import Channelizer, center_frequencies, design_prototype, pinned_empty  # noqa: F401
+from .deinterleave import (EMITTER_DTYPE, Deinterleaver, deinterleave, deinterleave_detections,  # noqa: F401
+                           deinterleave_pdws, describe_deinterleaver, merge_emitters, ticks_from_toa)
 from .event import DwellStats, EventPredictor, analyze_dwell, dwell_from_iq_file, fit_event, next_event  # noqa: F401
 from .matched_filter import (MatchedFilter, compress, compress_iq_file, pulse_delay_from_iq_files,  # noqa: F401
                              replica_from_pulse_train)
@@ -33,6 +35,8 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
            "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",
+           "Deinterleaver", "deinterleave", "deinterleave_pdws", "deinterleave_detections", "merge_emitters",
+           "describe_deinterleaver", "ticks_from_toa", "EMITTER_DTYPE",
            "OsCfar", "os_cfar_alpha", "detect_maps_os",
            "RangeDopplerCfar", "detect_maps", "detect_targets", "targets_to_pdws",
            "PriFold", "find_pri", "fold_z", "describe_fold",

@@ -263,6 +263,32 @@ class PfbOscfarPlan(C.Structure):
                 ("lds_bytes", C.c_uint32), ("reserved", C.c_uint32), ("kernel", C.c_char * 32)]
 
 
+class PfbDeintConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_period", C.c_uint32), ("max_period", C.c_uint32),
+                ("bin_ticks", C.c_uint32), ("max_level", C.c_uint32), ("detect_percent", C.c_uint32),
+                ("min_pulses", C.c_uint32), ("max_missing", C.c_uint32), ("tolerance", C.c_uint32),
+                ("fill_percent", C.c_uint32), ("max_emitters", C.c_uint32), ("flags", C.c_uint32),
+                ("device_id", C.c_int32)]
+
+
+class PfbDeintPlan(C.Structure):
+    _fields_ = [("scratch_bytes", C.c_uint64), ("num_bins", C.c_uint32), ("lds_bins", C.c_uint32),
+                ("tile_pulses", C.c_uint32), ("lds_bytes", C.c_uint32), ("successor_threads", C.c_uint32),
+                ("reserved", C.c_uint32), ("histogram_kernel", C.c_char * 32), ("successor_kernel", C.c_char * 32),
+                ("marking_kernel", C.c_char * 32)]
+
+
+class PfbDeintEmitter(C.Structure):
+    _fields_ = [("first_tick", C.c_uint64), ("last_tick", C.c_uint64), ("period", C.c_double), ("pulses", C.c_uint32),
+                ("periods", C.c_uint32), ("bin", C.c_uint32), ("candidate_period", C.c_uint32),
+                ("first_pulse", C.c_uint32), ("hist_count", C.c_uint32)]
+
+
+class PfbDeintStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint64), ("candidates_tried", C.c_uint64), ("candidates_refused", C.c_uint64),
+                ("pulses_assigned", C.c_uint64)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -379,10 +405,13 @@ EXPORTS = (
     "pfb_oscfar_describe", "pfb_oscfar_alpha", "pfb_oscfar_create", "pfb_oscfar_destroy", "pfb_oscfar_reset",
     "pfb_oscfar_set_stream", "pfb_oscfar_sync", "pfb_oscfar_get_device", "pfb_oscfar_next_map", "pfb_oscfar_get_stats",
     "pfb_oscfar_process", "pfb_oscfar_process_async", "pfb_oscfar_last_kernel",
+    "pfb_deint_describe", "pfb_deint_create", "pfb_deint_destroy", "pfb_deint_set_stream", "pfb_deint_sync",
+    "pfb_deint_get_device", "pfb_deint_run", "pfb_deint_histogram", "pfb_deint_successors", "pfb_deint_last_kernel",
+    "pfb_deint_get_stats", "pfb_deint_ticks_from_toa",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
-               "pfb_fold_set_tier",
+               "pfb_fold_set_tier", "pfb_deint_set_tier",
                "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch", "pfb_last_entry", "pfb_plan_entry")
 
 _lib = None
@@ -655,7 +684,21 @@ def load() -> C.CDLL:
     lib.pfb_oscfar_process_async.argtypes = [vp, vp, u64, vp, u64, vp]
     lib.pfb_oscfar_last_kernel.argtypes = [vp]
     lib.pfb_oscfar_last_kernel.restype = C.c_char_p
+    lib.pfb_deint_describe.argtypes = [C.POINTER(PfbDeintConfig), u64, C.POINTER(PfbDeintPlan)]
+    lib.pfb_deint_create.argtypes = [C.POINTER(PfbDeintConfig), C.POINTER(vp)]
+    lib.pfb_deint_destroy.argtypes = [vp]
+    lib.pfb_deint_set_stream.argtypes = [vp, vp]
+    lib.pfb_deint_sync.argtypes = [vp]
+    lib.pfb_deint_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_deint_run.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp]
+    lib.pfb_deint_histogram.argtypes = [vp, vp, u64, u32, vp, u64]
+    lib.pfb_deint_successors.argtypes = [vp, vp, u64, u32, u64, vp, vp, vp]
+    lib.pfb_deint_last_kernel.argtypes = [vp]
+    lib.pfb_deint_last_kernel.restype = C.c_char_p
+    lib.pfb_deint_get_stats.argtypes = [vp, C.POINTER(PfbDeintStats)]
+    lib.pfb_deint_ticks_from_toa.argtypes = [vp, u64, u64, C.c_double, C.c_double, vp, vp]
     lib.pfb_fold_set_tier.argtypes = [vp, C.c_int]
+    lib.pfb_deint_set_tier.argtypes = [vp, C.c_int, C.c_int]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
     lib.pfb_fast_plan_info.argtypes = [C.c_int, C.POINTER(PfbFastPlanDesc)]
