@@ -1864,6 +1864,178 @@ int pfb_deint_get_stats(const pfb_deint_handle* h, pfb_deint_stats* stats_out);
 int pfb_deint_ticks_from_toa(const double* toa, uint64_t stride_bytes, uint64_t n, double t0, double tick_rate,
                              uint64_t* ticks_out, uint32_t* order_out);
 
+/* ---- Modulation on pulse: what is inside a pulse -------------------------------------------------
+ * The detectors say where a pulse is; pfb_pdw.freq says one median phase step about its inside, so a chirp comes back
+ * as its mid frequency and a phase code as a carrier.  This unit measures, per pulse of a list, a handful of sums of
+ * lag products over the pulse's samples: the mean phase step (mid frequency), the sweep, and the phase flips of a code.
+ * For the integer formats every sum is an exact integer, so any order of summation gives THE SAME BYTES.
+ * This comment is the definition: the device code (csrc/pfb_mop.hip) and the tests' restatement (tests/mop_ref.py)
+ * are each written from it.
+ *
+ * Input: a series x of num_samples rows.  PFB_FMT_INT8_IQ / PFB_FMT_INT16_IQ: interleaved I,Q integers, ld = 1, the
+ * sums in counts (not normalised; bit_width is checked and otherwise unused).  PFB_FMT_CF32: complex float32 with a
+ * pitch: element i of column c is x[i ld + c], 1 <= ld, c < ld -- a column of pfb_process's frame-major matrix is
+ * measured where it lies, and so is a plain cf32 stream (ld = 1).  base_index is the global index of row 0.  A list
+ * of num_pulses pfb_mop_pulse in any order; overlapping and duplicate pulses are allowed; start is a global index.
+ *
+ * Per pulse, with t = trim_samples: n = min(length - 2t, 2^20), or 0 when length <= 2t; u[i] is element
+ * start - base_index + t + i, i = 0 .. n-1, u = I + jQ, the components int64 for the integer formats and converted
+ * to double for cf32.  EVERY EXPRESSION BELOW IS EVALUATED AS WRITTEN, one IEEE operation at a time, no contraction
+ * into fused multiply-adds, so that a float64 restatement gets the same bits for every term.
+ *   z1[i] = u[i+1] conj(u[i]):  a[i] = I[i+1] I[i] + Q[i+1] Q[i],  b[i] = Q[i+1] I[i] - I[i+1] Q[i],  i = 0 .. n-2
+ *   S1 = sum (a[i], b[i]): its argument is the mean phase step, for a symmetric sweep the mid frequency
+ *   L = (n - 1) / 2 (integer division)
+ *   S2 = sum over i = 0 .. n-2-L of z1[i+L] conj(z1[i]):  re = a[i+L] a[i] + b[i+L] b[i],  im = b[i+L] a[i] - a[i+L] b[i]
+ *        its argument is 2 pi rate L / fs^2, unambiguous for every sweep under fs because L <= (n-1)/2.  A lag of 1
+ *        instead has a per-term phase of 2 pi extent / (n fs), which drowns in noise: hence the half-length lag.
+ *   c[i] = a[i+1] a[i] + b[i+1] b[i], i = 0 .. n-3: the real part of the lag-1 second-order product.  neg_count = the
+ *        number of i with c[i] < 0 (a NaN is not < 0); first_neg / last_neg the lowest / highest such i, 0xFFFFFFFF
+ *        when there is none.  The first max_negatives such i go in ascending order to the optional side array
+ *        negs_out[p max_negatives + j] (uint32), the entries of a pulse past its count 0xFFFFFFFF;
+ *        negs_listed = min(neg_count, max_negatives), whether or not negs_out is given.
+ *   energy = sum (I^2 + Q^2); peak_power the largest I^2 + Q^2 and peak_index its lowest i.  A NaN never wins; with no
+ *        winner peak_index = 0xFFFFFFFF and peak_power = 0.
+ * Empty sums are +0.
+ *
+ * Exactness.  Integer formats: exact integer arithmetic.  a, b and the terms of S2 stay within +-2^62 (Cauchy-Schwarz
+ * at int16 full scale); S1 and energy stay under 2^53 and are reported exactly.  An S2 sum needs up to 82 bits: it is
+ * accumulated in two limbs, the terms' signed high 32 bits (term >> 32, arithmetic) and unsigned low 32 bits, each in
+ * an int64 (safe for n <= 2^20), and reported as ldexp((double)hi, 32) + (double)lo, the float64 nearest the exact
+ * sum, one rounding.  No order of summation is prescribed because none matters.  cf32: the terms are the float64
+ * values above, summed in the fixed order of the kernel that takes the pulse: THE SAME CALL TWICE GIVES THE SAME
+ * BYTES; each sum is within (n + 4) 2^-53 sum m_i of the exact one, m_i the sum of the magnitudes of a term's two
+ * products.  There are no floating-point atomics; the integer atomics only build work lists.
+ *
+ * Output: one 96-byte pfb_mop_record per pulse in the caller's order.  Flags: PFB_MOP_OUTSIDE: [start, start+length)
+ * is not wholly inside [base_index, base_index + num_samples), or column >= ld; then n = 0 and everything else is
+ * zero / 0xFFFFFFFF.  PFB_MOP_SHORT: n < 3 (an OUTSIDE pulse is SHORT too).  PFB_MOP_TRUNCATED: length - 2t > 2^20.
+ * PFB_MOP_NEGS_CLIPPED: neg_count > max_negatives.
+ *
+ * Tiers, by n (pfb_mop_plan): mop_wave, one wave per pulse, four pulses to a workgroup, for n < group_min; mop_group,
+ * one workgroup per pulse, each wave a quarter of it, for n < split_min; mop_split + mop_join, the pulse cut into
+ * parts of part_samples for as many workgroups, whose partial sums (integers, or doubles in part order) and first
+ * max_negatives negatives a second small kernel joins, from split_min on.  Lanes take consecutive i, so every load is
+ * coalesced.  The grid is capped at grid_cap workgroups, which loop over their units of work.  pfb_mop_measure_async
+ * cannot read how many pulses are long and keeps them on mop_group.  pfb_mop_last_kernel joins what ran with '+'.
+ *
+ * Host route: with x in host memory only the pulses' windows are uploaded, packed back to back into a page-locked
+ * staging buffer, a batch of whole pulses at a time, and the same kernels run on the packed windows: the bytes equal
+ * the device route's, the records echo the caller's start / length / column.
+ *
+ * Not built: the measurement inside the deinterleaver, polyphase codes (more than two phases), nonlinear sweeps.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers or a wrong
+ * struct_size, max_negatives > 128, trim_samples > 2^19; then PFB_ERR_BAD_FORMAT: an unknown sample format, bit_width
+ * outside 1..8 (int8) or 1..16 (int16; ignored for cf32).  Per call PFB_ERR_BAD_ARG: a null handle, an unknown mem,
+ * ld != 1 for an integer format or ld = 0, num_pulses > 2^24, num_samples ld overflowing 2^63 elements, null x with
+ * num_samples > 0, null pulses or rec_out with num_pulses > 0, a device pointer not aligned (one element for x, 8
+ * bytes for pulses and records, 4 for negs_out).  negs_out == NULL with max_negatives > 0 is allowed: no list is
+ * written.  Then PFB_ERR_NO_DEVICE without a HIP device. */
+enum {
+  PFB_MOP_OUTSIDE = 1,
+  PFB_MOP_SHORT = 2,
+  PFB_MOP_TRUNCATED = 4,
+  PFB_MOP_NEGS_CLIPPED = 8
+};
+enum { /* pfb_mop_figure.kind */
+  PFB_MOP_KIND_UNMODULATED = 0,
+  PFB_MOP_KIND_LFM = 1,
+  PFB_MOP_KIND_PHASE_CODED = 2,
+  PFB_MOP_KIND_BOTH = 3,
+  PFB_MOP_KIND_NOT_MEASURABLE = 4
+};
+
+typedef struct pfb_mop_config {
+  uint32_t struct_size;    /* = sizeof(pfb_mop_config)                         */
+  uint32_t sample_format;  /* PFB_FMT_*                                        */
+  uint32_t bit_width;      /* of the integer formats; the sums are in counts   */
+  uint32_t trim_samples;   /* t: samples left out at each end, <= 2^19         */
+  uint32_t max_negatives;  /* entries per pulse of negs_out, 0 .. 128          */
+  int32_t device_id;       /* -1 = the current device                          */
+} pfb_mop_config;
+
+typedef struct pfb_mop_pulse { /* 16 bytes */
+  uint64_t start;          /* global index of the first sample                 */
+  uint32_t length;         /* samples                                          */
+  uint32_t column;         /* cf32 with a pitch: the column; else 0            */
+} pfb_mop_pulse;
+
+typedef struct pfb_mop_record { /* 96 bytes */
+  uint64_t start;          /* echoed                                           */
+  uint32_t length;
+  uint32_t column;
+  uint32_t n;              /* samples measured                                 */
+  uint32_t flags;          /* PFB_MOP_*                                        */
+  uint32_t neg_count;
+  uint32_t first_neg;
+  uint32_t last_neg;
+  uint32_t peak_index;
+  uint32_t negs_listed;
+  uint32_t reserved;       /* 0 */
+  double energy;
+  double peak_power;
+  double s1_re, s1_im;
+  double s2_re, s2_im;
+} pfb_mop_record;
+
+typedef struct pfb_mop_plan { /* what pfb_mop_describe reports; host only */
+  uint64_t scratch_bytes;  /* device memory a handle holds after a device-route call on a list of any length */
+  uint32_t group_min;      /* the least n that mop_group takes                 */
+  uint32_t split_min;      /* the least n that mop_split takes                 */
+  uint32_t part_samples;   /* i per part of a split pulse                      */
+  uint32_t grid_cap;       /* workgroups of a launch at most                   */
+  uint32_t threads;        /* lanes of a workgroup                             */
+  uint32_t slice_pulses;   /* pulses one round of launches takes               */
+  uint32_t split_slots;    /* split pulses one mop_split launch takes          */
+  uint32_t stage_bytes;    /* the host route's staging chunk                   */
+  char wave_kernel[32];
+  char group_kernel[32];
+  char split_kernel[32];
+  char join_kernel[32];
+} pfb_mop_plan;
+
+typedef struct pfb_mop_figure { /* 48 bytes; what pfb_mop_figures makes of a record */
+  double freq_hz;          /* atan2(s1_im, s1_re) / (2 pi) fs                  */
+  double rate_hz_per_s;    /* atan2(s2_im, s2_re) / (2 pi L) fs^2; 0 when L = 0 */
+  double extent_hz;        /* rate (n - 1) / fs                                */
+  double mean_power;       /* energy / n; 0 when n = 0                         */
+  double flips;            /* neg_count / 2                                    */
+  uint32_t kind;           /* PFB_MOP_KIND_*                                   */
+  uint32_t reserved;       /* 0 */
+} pfb_mop_figure;
+
+typedef struct pfb_mop_handle pfb_mop_handle;
+
+/* Host only: validate cfg (everything pfb_mop_create checks before the device) and report the plan. */
+int pfb_mop_describe(const pfb_mop_config* cfg, pfb_mop_plan* plan_out);
+/* Lifecycle as pfb_deint_*.  The scratch is of a fixed size; the host route's staging grows to the longest window. */
+int pfb_mop_create(const pfb_mop_config* cfg, pfb_mop_handle** out);
+int pfb_mop_destroy(pfb_mop_handle* h);
+int pfb_mop_set_stream(pfb_mop_handle* h, void* hip_stream);
+int pfb_mop_sync(pfb_mop_handle* h);
+int pfb_mop_get_device(const pfb_mop_handle* h, int* device_id);
+/* Measure num_pulses pulses of x.  x is host or device memory by mem, the pulse list independently by pulses_mem;
+ * rec_out (num_pulses records) and negs_out (num_pulses max_negatives uint32, or NULL) follow pulses_mem.
+ * Synchronous. */
+int pfb_mop_measure(pfb_mop_handle* h, const void* x, uint64_t num_samples, uint64_t ld, uint64_t base_index, uint32_t mem,
+                    const pfb_mop_pulse* pulses, uint64_t num_pulses, uint32_t pulses_mem, pfb_mop_record* rec_out,
+                    uint32_t* negs_out);
+/* The same with every pointer in device memory: launches on the handle's stream and does not wait for it. */
+int pfb_mop_measure_async(pfb_mop_handle* h, const void* x, uint64_t num_samples, uint64_t ld, uint64_t base_index,
+                          const pfb_mop_pulse* pulses, uint64_t num_pulses, pfb_mop_record* rec_out, uint32_t* negs_out);
+/* The kernels the last call launched, joined with '+'; "" before the first and after a call that launched none. */
+const char* pfb_mop_last_kernel(const pfb_mop_handle* h);
+/* Host only: records into physical figures at sample rate fs, in double.  kind: NOT_MEASURABLE when n < 3 or OUTSIDE;
+ * else bit 0 (LFM) when |extent_hz| >= fs / n, one Rayleigh bin of the pulse, and bit 1 (phase coded) when
+ * neg_count >= 2.  PFB_ERR_BAD_ARG for null pointers with n > 0 or an fs that is not finite or <= 0. */
+int pfb_mop_figures(const pfb_mop_record* records, uint64_t n, double fs, pfb_mop_figure* out);
+/* Host only: pulses from PDWs whose toa and pw are in seconds of a series at series_rate rows a second that began at
+ * t0: start = llrint((toa - t0) series_rate) - 1 (the scripts' toa is 1-based), length = llrint(pw series_rate),
+ * column = bin.  PFB_ERR_BAD_ARG for null pointers with n > 0, n > 2^31, a series_rate that is not finite or <= 0, a
+ * t0, toa or pw that is not finite, a start under 0 or at or over 2^62, a length under 0 or over 2^32 - 1, a negative
+ * bin; nothing is written then. */
+int pfb_mop_pulses_from_pdw(const pfb_pdw* pdws, uint64_t n, double series_rate, double t0, pfb_mop_pulse* pulses_out);
+
 #ifdef __cplusplus
 }
 #endif

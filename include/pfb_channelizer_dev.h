@@ -64,6 +64,15 @@ int pfb_fold_set_tier(pfb_fold_handle* h, int tier);
  * pfb_deint_last_kernel names what ran. */
 int pfb_deint_set_tier(pfb_deint_handle* h, int histogram_tier, int marking_tier);
 
+/* Which kernel measures the pulses of the next calls of a pfb_mop handle: 0 = the library's choice by n
+ * (pfb_mop_plan.group_min / split_min), 1 = mop_wave, 2 = mop_group, 3 = mop_split + mop_join, for every pulse
+ * whatever its length.  grid_cap: the most workgroups of a launch, 0 = pfb_mop_plan.grid_cap again; stage_bytes: the
+ * host route's staging chunk, 0 = pfb_mop_plan.stage_bytes again (a batch always takes one pulse at least).  For the
+ * integer formats every tier gives the same bytes; the tests run one list through them, the meter (tools/mop_rate.py)
+ * times them.  PFB_ERR_BAD_ARG for a tier outside 0 .. 3 or a grid_cap above 65536.  pfb_mop_last_kernel names what
+ * ran. */
+int pfb_mop_set_tier(pfb_mop_handle* h, int tier, uint32_t grid_cap, uint64_t stage_bytes);
+
 /* The fused-kernel table, row by row in lookup order (host only, no device needed): what the tests walk, so that a
  * registered plan cannot go untested.  Rows of one (M, P, D, sample_format) are that shape's variants 0, 1, ... */
 typedef struct {

@@ -18,6 +18,8 @@ from .mf_bank import (MatchedFilterBank, bank_frequencies, compress_bank,  # noq
 from .os_cfar import OsCfar, detect_maps_os, os_cfar_alpha  # noqa: F401
 from .pri_search import PriFold, describe_fold, find_pri, fold_z  # noqa: F401
 from .pulse_doppler import PulseDoppler, detect_pulse_train, doppler_frequencies, range_doppler  # noqa: F401
+from .pulse_mod import (MOP_DTYPE, PulseModulation, measure_pdws, measure_pulses, modulation_figures,  # noqa: F401
+                        modulation_from_iq_file, phase_code, replica_from_measurement)
 from .pulse_source import PulseTrain, pulse_train, synth_params  # noqa: F401
 from .rd_cfar import RangeDopplerCfar, detect_maps, detect_targets  # noqa: F401
 from .rd_cfar import detections_to_pdws as targets_to_pdws  # noqa: F401
@@ -35,6 +37,8 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
            "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",
+           "MOP_DTYPE", "PulseModulation", "measure_pulses", "measure_pdws", "modulation_figures", "phase_code",
+           "replica_from_measurement", "modulation_from_iq_file",
            "Deinterleaver", "deinterleave", "deinterleave_pdws", "deinterleave_detections", "merge_emitters",
            "describe_deinterleaver", "ticks_from_toa", "EMITTER_DTYPE",
            "OsCfar", "os_cfar_alpha", "detect_maps_os",

@@ -53,6 +53,9 @@ PFB_CFAR_DET_ONE_SIDED = 1
 PFB_PD_COMPLEX, PFB_PD_POWER, PFB_PD_BEST, PFB_PD_NONCOHERENT = 0, 1, 2, 3
 PFB_PD_CENTERED = 1
 PFB_RDCFAR_DET_ONE_SIDED = 1
+PFB_MOP_OUTSIDE, PFB_MOP_SHORT, PFB_MOP_TRUNCATED, PFB_MOP_NEGS_CLIPPED = 1, 2, 4, 8
+PFB_MOP_KIND_UNMODULATED, PFB_MOP_KIND_LFM, PFB_MOP_KIND_PHASE_CODED, PFB_MOP_KIND_BOTH = 0, 1, 2, 3
+PFB_MOP_KIND_NOT_MEASURABLE = 4
 
 
 class PfbConfig(C.Structure):
@@ -289,6 +292,36 @@ class PfbDeintStats(C.Structure):
                 ("pulses_assigned", C.c_uint64)]
 
 
+class PfbMopConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sample_format", C.c_uint32), ("bit_width", C.c_uint32),
+                ("trim_samples", C.c_uint32), ("max_negatives", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbMopPulse(C.Structure):
+    _fields_ = [("start", C.c_uint64), ("length", C.c_uint32), ("column", C.c_uint32)]
+
+
+class PfbMopRecord(C.Structure):
+    _fields_ = [("start", C.c_uint64), ("length", C.c_uint32), ("column", C.c_uint32), ("n", C.c_uint32),
+                ("flags", C.c_uint32), ("neg_count", C.c_uint32), ("first_neg", C.c_uint32), ("last_neg", C.c_uint32),
+                ("peak_index", C.c_uint32), ("negs_listed", C.c_uint32), ("reserved", C.c_uint32),
+                ("energy", C.c_double), ("peak_power", C.c_double), ("s1_re", C.c_double), ("s1_im", C.c_double),
+                ("s2_re", C.c_double), ("s2_im", C.c_double)]
+
+
+class PfbMopPlan(C.Structure):
+    _fields_ = [("scratch_bytes", C.c_uint64), ("group_min", C.c_uint32), ("split_min", C.c_uint32),
+                ("part_samples", C.c_uint32), ("grid_cap", C.c_uint32), ("threads", C.c_uint32),
+                ("slice_pulses", C.c_uint32), ("split_slots", C.c_uint32), ("stage_bytes", C.c_uint32),
+                ("wave_kernel", C.c_char * 32), ("group_kernel", C.c_char * 32), ("split_kernel", C.c_char * 32),
+                ("join_kernel", C.c_char * 32)]
+
+
+class PfbMopFigure(C.Structure):
+    _fields_ = [("freq_hz", C.c_double), ("rate_hz_per_s", C.c_double), ("extent_hz", C.c_double),
+                ("mean_power", C.c_double), ("flips", C.c_double), ("kind", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class PfbFastPlanDesc(C.Structure):
     _fields_ = [
         ("M", C.c_int), ("P", C.c_int), ("D", C.c_int), ("sample_format", C.c_int), ("variant", C.c_int),
@@ -408,10 +441,12 @@ EXPORTS = (
     "pfb_deint_describe", "pfb_deint_create", "pfb_deint_destroy", "pfb_deint_set_stream", "pfb_deint_sync",
     "pfb_deint_get_device", "pfb_deint_run", "pfb_deint_histogram", "pfb_deint_successors", "pfb_deint_last_kernel",
     "pfb_deint_get_stats", "pfb_deint_ticks_from_toa",
+    "pfb_mop_describe", "pfb_mop_create", "pfb_mop_destroy", "pfb_mop_set_stream", "pfb_mop_sync", "pfb_mop_get_device",
+    "pfb_mop_measure", "pfb_mop_measure_async", "pfb_mop_last_kernel", "pfb_mop_figures", "pfb_mop_pulses_from_pdw",
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
-               "pfb_fold_set_tier", "pfb_deint_set_tier",
+               "pfb_fold_set_tier", "pfb_deint_set_tier", "pfb_mop_set_tier",
                "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch", "pfb_last_entry", "pfb_plan_entry")
 
 _lib = None
@@ -697,7 +732,20 @@ def load() -> C.CDLL:
     lib.pfb_deint_last_kernel.restype = C.c_char_p
     lib.pfb_deint_get_stats.argtypes = [vp, C.POINTER(PfbDeintStats)]
     lib.pfb_deint_ticks_from_toa.argtypes = [vp, u64, u64, C.c_double, C.c_double, vp, vp]
+    lib.pfb_mop_describe.argtypes = [C.POINTER(PfbMopConfig), C.POINTER(PfbMopPlan)]
+    lib.pfb_mop_create.argtypes = [C.POINTER(PfbMopConfig), C.POINTER(vp)]
+    lib.pfb_mop_destroy.argtypes = [vp]
+    lib.pfb_mop_set_stream.argtypes = [vp, vp]
+    lib.pfb_mop_sync.argtypes = [vp]
+    lib.pfb_mop_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_mop_measure.argtypes = [vp, vp, u64, u64, u64, u32, vp, u64, u32, vp, vp]
+    lib.pfb_mop_measure_async.argtypes = [vp, vp, u64, u64, u64, vp, u64, vp, vp]
+    lib.pfb_mop_last_kernel.argtypes = [vp]
+    lib.pfb_mop_last_kernel.restype = C.c_char_p
+    lib.pfb_mop_figures.argtypes = [vp, u64, C.c_double, vp]
+    lib.pfb_mop_pulses_from_pdw.argtypes = [vp, u64, C.c_double, C.c_double, vp]
     lib.pfb_fold_set_tier.argtypes = [vp, C.c_int]
+    lib.pfb_mop_set_tier.argtypes = [vp, C.c_int, u32, u64]
     lib.pfb_deint_set_tier.argtypes = [vp, C.c_int, C.c_int]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
     lib.pfb_fast_plan_count.argtypes = []
