@@ -1281,7 +1281,8 @@ const char* pfb_cfar_last_kernel(const pfb_cfar_handle* h);
  * pfb_pd_reset start at 0, pfb_pd_set_index at its argument.  The carry is K R 8 bytes; more than 64 MiB is
  * PFB_ERR_UNSUPPORTED.  pfb_pd_flush transforms the open CPI with its missing samples as zeros (a no-op when none is
  * open); what the stream brings of that CPI afterwards is ignored.  Lengths outside the set, overlapping CPIs,
- * staggered or non-integer PRIs, clutter cancellers and integer I/Q input are not built.
+ * staggered PRIs, clutter cancellers and integer I/Q input are not built (a PRI that is not a whole number of samples
+ * goes through pfb_regrid_* first: the last section of this header).
  *
  * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
  * struct_size, L, R or K of 0, R > L, K > ND, ND outside the set, L > 2^24, origin > 2^62, an unknown output or flag,
@@ -1395,9 +1396,9 @@ const char* pfb_pd_last_kernel(const pfb_pd_handle* h);
  * mu^2).  The true period, its multiples and its divisors (if listed) score high; origin = peak_bin * C is, modulo the
  * period, where the train's compressed peak lies (to one bin), and is what pfb_pd_config.origin takes.
  *
- * Not built: splitting one candidate's time axis over workgroups (the order above forbids it), non-integer and
- * staggered periods, a fast-folding tree that shares additions between candidates, PFB_CFAR_BANK_CELL input, folding
- * fused into the matched filter's store.
+ * Not built: splitting one candidate's time axis over workgroups (the order above forbids it), staggered periods, a
+ * fast-folding tree that shares additions between candidates, PFB_CFAR_BANK_CELL input, folding fused into the matched
+ * filter's store.  Periods that are not whole samples are pfb_qfold_*'s (the last section of this header).
  *
  * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers (the list
  * included), a wrong struct_size, C outside 1 .. 64, NC outside 1 .. 4096, a period < C or > 2^24 or with more than
@@ -2035,6 +2036,163 @@ int pfb_mop_figures(const pfb_mop_record* records, uint64_t n, double fs, pfb_mo
  * t0, toa or pw that is not finite, a start under 0 or at or over 2^62, a length under 0 or over 2^32 - 1, a negative
  * bin; nothing is written then. */
 int pfb_mop_pulses_from_pdw(const pfb_pdw* pdws, uint64_t n, double series_rate, double t0, pfb_mop_pulse* pulses_out);
+
+/* ---- Fractional-PRI search and regridder: trains whose period is not a whole number of samples ----
+ * pfb_fold_* folds at integer periods and pfb_pd_* integrates at an integer PRI.  An emitter's clock is not locked to
+ * the recorder's: off the air a PRI is 2048.37 samples, the train drifts a cell every three periods, an integer fold
+ * smears it over many bins and a coherent integration walks it through the gates.  This section is the two missing
+ * pieces.  pfb_qfold_* is pfb_fold_* at periods given in 2^-32 samples; pfb_regrid_* lays the windows of such a train
+ * onto an integer grid, so that pfb_pd_*, pfb_cfar_*, pfb_rdcfar_* and pfb_oscfar_* take it as they are.  This comment
+ * is the definition: the device code (csrc/pfb_qfold.hip) and the tests' restatement (tests/qfold_ref.py) are each
+ * written from it.
+ *
+ * Period: Pq, a uint64 holding the period times 2^32; Pi = Pq >> 32, Pf = Pq & (2^32 - 1).  Legal (pfb_qfold_*, with
+ * bin_cells C): C <= Pi <= 2^24 and NB = floor(Pi / C) <= 65536 bins.  Period m begins at cell
+ *   start(m) = ceil(m Pq / 2^32) = m Pi + ceil(m Pf / 2^32),
+ * so every period is Pi or Pi + 1 cells long and start is strictly increasing.  The period of global cell i is
+ * m(i) = floor(i 2^32 / Pq), the largest m with start(m) <= i.
+ *
+ * Bin of cell i:  j = min(floor((i - start(m(i))) / C), NB - 1).  Every bin of a period but the last is exactly C
+ * cells; the last takes what is left, Pi - (NB - 1) C cells or one more in a long period.  With Pf = 0 this is
+ * pfb_fold_*'s rule word for word.
+ *
+ * Profile, invariance and limits are pfb_fold_*'s: F[j] is the float32 sum of the cells of bin j, added ONE AT A TIME
+ * IN ASCENDING i starting from +0.0f, no tree, no atomics, no partial sums combined later; the same bits come out under
+ * any cutting of the stream into calls, empty calls included; NaN and Inf go where IEEE addition takes them.  1 <= NC <=
+ * 4096 candidates, C = 1 .. 64, duplicates allowed, profiles of sum_c NB_c * 4 bytes <= 64 MiB (PFB_ERR_UNSUPPORTED
+ * above), stream index <= 2^62.
+ *
+ * Start index: pfb_qfold_set_index(h, N0) clears the profiles and makes N0 (<= 2^62) the index of the next cell.  Cells
+ * before N0 count as never seen.  A caller skips the head of a record with it.  pfb_qfold_reset is set_index(0).
+ *
+ * Counts, all integers.  With n_j(N) the cells i < N of bin j, the handle's count of bin j is n_j(N) - n_j(N0), where,
+ * with M = m(N - 1) + 1 the periods begun,
+ *   n_j(N) = (M - 1) C + clamp(N - start(M - 1) - j C, 0, C)     for j < NB - 1,
+ *   n_{NB-1}(N) = N - sum_{j < NB-1} n_j(N),                       n_j(0) = 0.
+ * pfb_qfold_counts (host only, 128-bit host arithmetic) gives n_j(num_cells) - n_j(first_cell).
+ *
+ * Score: one 64-byte pfb_qfold_score per candidate, in list order.  bins_used counts the bins with a count > 0; after a
+ * set_index into the middle of a period these need not be the leading ones.  The means m_j = (double)F[j] / (double)
+ * count_j, the peak walk and the two sums run over exactly those bins, j ascending.  The peak walk is pfb_fold_score's:
+ * strictly greater replaces, ties go to the lowest j, a NaN never displaces anything, a NaN in the first used bin stays.
+ * peak_sum = F[peak_bin], peak_cells its count, peak_mean = (float)m_peak.  sum_means and sum_sq_means have no fixed
+ * order and are good to (bins_used + 1) 2^-53 sum |terms|, the bound pfb_fold_* states.  Every other field is a fixed
+ * function of the cells.  With no cell taken every field but period_q32, num_bins and cells is 0.  The statistic
+ * pfb_fold_* describes (z from peak_mean, sum_means, sum_sq_means, bins_used) applies unchanged; origin = peak_bin C.
+ *
+ * Regrid (pfb_regrid_*).  Parameters: period_q32 (1 <= Pi <= 2^24), origin o (<= 2^62), row_samples R (1 .. Pi),
+ * elem_bytes (8: complex64, 4: float32).  Output element t = k R + r (r < R) is input element o + start(k) + r, copied
+ * bit for bit.  The source index rises strictly with t, so a call that takes input [s, s + n) writes one contiguous
+ * range of t -- those whose source lies in it -- to out[0 ..).  Their number is known on the host from lengths alone
+ * (pfb_regrid_outputs_for): there is no carry and no flush, and any cutting gives the same bytes because nothing is
+ * computed.  PFB_ERR_CAPACITY reports the count needed and changes no state.  Pulse k of a train at period Pq that
+ * begins at o then sits at k R of the output, so pfb_pd_config{pri = R, origin = 0} takes it; row d of those maps stands
+ * for d fs 2^32 / (ND Pq) -- the true period, not R (pfb_regrid_doppler_frequencies, host only).
+ *
+ * Not built: sub-sample interpolation (a pulse is taken at the first whole sample at or after its true start, up to one
+ * sample late), staggered periods.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers (the list
+ * included), a wrong struct_size, C outside 1 .. 64, NC outside 1 .. 4096, a period with Pi < C or Pq > 2^24 2^32 or
+ * more than 65536 bins, flags != 0; for pfb_regrid_* a period with Pi < 1 or Pq > 2^24 2^32, an origin > 2^62, R outside
+ * 1 .. Pi, elem_bytes not 4 or 8, flags != 0; per call an unknown mem, a device pointer not aligned to its element (4
+ * bytes for cells and profiles, 8 for score records and counts, elem_bytes for regrid elements), an index that would
+ * pass 2^62, a candidate >= NC.  Then PFB_ERR_UNSUPPORTED: profiles over 64 MiB.  Then PFB_ERR_NO_DEVICE without a HIP
+ * device.  Then, per call, PFB_ERR_CAPACITY. */
+typedef struct pfb_qfold_config {
+  uint32_t struct_size;       /* = sizeof(pfb_qfold_config)                                      */
+  uint32_t bin_cells;         /* C                                                               */
+  uint32_t num_periods;       /* NC                                                              */
+  uint32_t flags;             /* 0                                                               */
+  const uint64_t* periods_q32;/* Pq_c, c = 0 .. NC-1, copied at create                           */
+  int32_t device_id;          /* HIP device ordinal, -1 = current device                         */
+  uint32_t reserved;          /* ignored                                                         */
+} pfb_qfold_config;
+
+typedef struct pfb_qfold_plan { /* what pfb_qfold_describe reports; host only                    */
+  uint64_t profile_bytes;     /* sum_c NB_c * 4 (the handle holds a second copy: pfb_qfold_process) */
+  uint64_t total_bins;        /* sum_c NB_c                                                      */
+  uint32_t max_bins;          /* max_c NB_c                                                      */
+  char kernel[32];            /* the kernel that folds a call                                    */
+} pfb_qfold_plan;
+
+typedef struct pfb_qfold_score {  /* 64 bytes */
+  uint64_t period_q32;           /* Pq                                                               */
+  uint32_t num_bins, bins_used;  /* NB; bins with a count > 0                                        */
+  uint32_t peak_bin, reserved;   /* the used bin of largest mean, ties to the lowest; 0              */
+  uint64_t peak_cells;           /* its count                                                        */
+  float peak_sum, peak_mean;     /* F[peak_bin]; (float)m_peak                                       */
+  double sum_means, sum_sq_means;
+  uint64_t cells;                /* N - N0 */
+} pfb_qfold_score;
+
+typedef struct pfb_qfold_handle pfb_qfold_handle;
+
+/* Host only: validate cfg (everything pfb_qfold_create checks before the device) and report the plan. */
+int pfb_qfold_describe(const pfb_qfold_config* cfg, pfb_qfold_plan* plan_out);
+/* Host only: counts_out[j] = n_j(num_cells) - n_j(first_cell) for the NB bins of candidate `candidate` of cfg.
+ * PFB_ERR_BAD_ARG for a cfg pfb_qfold_describe refuses with it, a null counts_out, candidate >= NC, first_cell >
+ * num_cells, num_cells > 2^62. */
+int pfb_qfold_counts(const pfb_qfold_config* cfg, uint32_t candidate, uint64_t first_cell, uint64_t num_cells,
+                     uint64_t* counts_out);
+/* Lifecycle as pfb_fold_*.  The handle owns the period list, the profiles and, per candidate, where in its period the
+ * next cell lies. */
+int pfb_qfold_create(const pfb_qfold_config* cfg, pfb_qfold_handle** out);
+int pfb_qfold_destroy(pfb_qfold_handle* h);
+int pfb_qfold_reset(pfb_qfold_handle* h);   /* pfb_qfold_set_index(h, 0) */
+int pfb_qfold_set_index(pfb_qfold_handle* h, uint64_t next_cell);  /* profiles to +0, N0 = N = next_cell; waits for the stream */
+int pfb_qfold_set_stream(pfb_qfold_handle* h, void* hip_stream);
+int pfb_qfold_sync(pfb_qfold_handle* h);
+int pfb_qfold_get_device(const pfb_qfold_handle* h, int* device_id);
+int pfb_qfold_next_index(const pfb_qfold_handle* h, uint64_t* index_out);  /* N: global index of the next cell taken */
+/* Fold num_cells cells into every profile: memory contracts, staging and what PFB_ERR_HIP leaves behind exactly as
+ * pfb_fold_process states them.  Synchronous. */
+int pfb_qfold_process(pfb_qfold_handle* h, const float* cells, uint64_t num_cells, uint32_t mem);
+/* Same, device pointer, enqueued on the handle's stream without a host sync. */
+int pfb_qfold_process_async(pfb_qfold_handle* h, const float* d_cells, uint64_t num_cells);
+/* The NC score records of the cells taken so far, as pfb_fold_scores: PFB_ERR_CAPACITY when capacity < NC. */
+int pfb_qfold_scores(pfb_qfold_handle* h, pfb_qfold_score* out, uint64_t capacity, uint32_t mem);
+/* F of one candidate, NB floats, as pfb_fold_profile. */
+int pfb_qfold_profile(pfb_qfold_handle* h, uint32_t candidate, float* out, uint64_t capacity_bins, uint32_t mem);
+/* The kernel the last call that took cells launched: plan.kernel; "" before the first. */
+const char* pfb_qfold_last_kernel(const pfb_qfold_handle* h);
+
+typedef struct pfb_regrid_config {
+  uint32_t struct_size;       /* = sizeof(pfb_regrid_config)                                     */
+  uint32_t row_samples;       /* R, 1 .. Pi                                                      */
+  uint64_t period_q32;        /* Pq                                                              */
+  uint64_t origin;            /* o: input index of row 0's first element                         */
+  uint32_t elem_bytes;        /* 8 (complex64) or 4 (float32)                                    */
+  uint32_t flags;             /* 0                                                               */
+  int32_t device_id;          /* HIP device ordinal, -1 = current device                         */
+  uint32_t reserved;          /* ignored                                                         */
+} pfb_regrid_config;
+
+typedef struct pfb_regrid_handle pfb_regrid_handle;
+
+int pfb_regrid_create(const pfb_regrid_config* cfg, pfb_regrid_handle** out);
+int pfb_regrid_destroy(pfb_regrid_handle* h);
+int pfb_regrid_reset(pfb_regrid_handle* h);   /* input index back to 0 */
+int pfb_regrid_set_index(pfb_regrid_handle* h, uint64_t next_input);  /* <= 2^62: the index of the next input element */
+int pfb_regrid_set_stream(pfb_regrid_handle* h, void* hip_stream);
+int pfb_regrid_sync(pfb_regrid_handle* h);
+int pfb_regrid_get_device(const pfb_regrid_handle* h, int* device_id);
+int pfb_regrid_next_index(const pfb_regrid_handle* h, uint64_t* index_out);
+/* The output elements the next num_inputs input elements give, from the handle's index and lengths alone. */
+int pfb_regrid_outputs_for(const pfb_regrid_handle* h, uint64_t num_inputs, uint64_t* outputs_out);
+/* Take num_inputs elements; the output elements whose source lies among them go to out[0 ..) (room for
+ * capacity_outputs), their number to *outputs_out.  PFB_ERR_CAPACITY sets *outputs_out to the number needed and changes
+ * no state.  mem: x and out are both host pointers (staged through the device) or both device pointers.  Synchronous. */
+int pfb_regrid_process(pfb_regrid_handle* h, const void* x, uint64_t num_inputs, void* out, uint64_t capacity_outputs,
+                       uint64_t* outputs_out, uint32_t mem);
+/* Same, device pointers, enqueued on the handle's stream without a host sync; the count is written to *d_outputs_out,
+ * a uint64 in device memory, in stream order.  PFB_ERR_CAPACITY queues nothing. */
+int pfb_regrid_process_async(pfb_regrid_handle* h, const void* d_x, uint64_t num_inputs, void* d_out,
+                             uint64_t capacity_outputs, uint64_t* d_outputs_out);
+/* Host only: out[i] = d fs 2^32 / (ND Pq) for the ND = doppler_length rows in the order pfb_pd_* writes them (d = 0 ..
+ * ND-1, or -ND/2 .. ND/2-1 with centered != 0).  PFB_ERR_BAD_ARG for a null out, a period pfb_regrid_create refuses, ND
+ * outside 1 .. 65536 or fs not finite. */
+int pfb_regrid_doppler_frequencies(uint64_t period_q32, uint32_t doppler_length, int centered, double fs, double* out);
 
 #ifdef __cplusplus
 }

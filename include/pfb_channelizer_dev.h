@@ -73,6 +73,13 @@ int pfb_deint_set_tier(pfb_deint_handle* h, int histogram_tier, int marking_tier
  * ran. */
 int pfb_mop_set_tier(pfb_mop_handle* h, int tier, uint32_t grid_cap, uint64_t stage_bytes);
 
+/* Which kernel folds the next calls of a pfb_qfold handle, and how many cells one launch takes: tier 0 = the library's
+ * choice (pfb_qfold_plan.kernel), 1 = qfold_direct, 2 = qfold_tile (PFB_ERR_UNSUPPORTED when bin_cells is not 8, 16, 32
+ * or 64).  step_cells: cells per kernel launch and per staging step, 1 .. 2^24; 0 = 2^24 again.  A short step puts the
+ * step boundary inside a short stream.  Both tiers and every step length give the same bytes.  PFB_ERR_BAD_ARG for any
+ * other value.  pfb_qfold_last_kernel names what ran. */
+int pfb_qfold_set_tier(pfb_qfold_handle* h, int tier, uint64_t step_cells);
+
 /* The fused-kernel table, row by row in lookup order (host only, no device needed): what the tests walk, so that a
  * registered plan cannot go untested.  Rows of one (M, P, D, sample_format) are that shape's variants 0, 1, ... */
 typedef struct {

@@ -16,6 +16,8 @@ from .matched_filter import (MatchedFilter, compress, compress_iq_file, pulse_de
 from .mf_bank import (MatchedFilterBank, bank_frequencies, compress_bank,  # noqa: F401
                       pulse_delay_and_offset_from_iq_files)
 from .os_cfar import OsCfar, detect_maps_os, os_cfar_alpha  # noqa: F401
+from .pri_fine import (QSCORE_DTYPE, FinePriFold, Regrid, describe_fine_fold, detect_pulse_train_fine,  # noqa: F401
+                       find_pri_fine, period_q32, period_samples, refine_pri, regrid, regrid_doppler_frequencies)
 from .pri_search import PriFold, describe_fold, find_pri, fold_z  # noqa: F401
 from .pulse_doppler import PulseDoppler, detect_pulse_train, doppler_frequencies, range_doppler  # noqa: F401
 from .pulse_mod import (MOP_DTYPE, PulseModulation, measure_pdws, measure_pulses, modulation_figures,  # noqa: F401
@@ -37,6 +39,8 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
            "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",
+           "FinePriFold", "describe_fine_fold", "period_q32", "period_samples", "refine_pri", "find_pri_fine",
+           "Regrid", "regrid", "regrid_doppler_frequencies", "detect_pulse_train_fine", "QSCORE_DTYPE",
            "MOP_DTYPE", "PulseModulation", "measure_pulses", "measure_pdws", "modulation_figures", "phase_code",
            "replica_from_measurement", "modulation_from_iq_file",
            "Deinterleaver", "deinterleave", "deinterleave_pdws", "deinterleave_detections", "merge_emitters",

@@ -232,6 +232,28 @@ class PfbFoldScore(C.Structure):
                 ("sum_means", C.c_double), ("sum_sq_means", C.c_double), ("cells", C.c_uint64)]
 
 
+class PfbQfoldConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("bin_cells", C.c_uint32), ("num_periods", C.c_uint32), ("flags", C.c_uint32),
+                ("periods_q32", C.POINTER(C.c_uint64)), ("device_id", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class PfbQfoldPlan(C.Structure):
+    _fields_ = [("profile_bytes", C.c_uint64), ("total_bins", C.c_uint64), ("max_bins", C.c_uint32),
+                ("kernel", C.c_char * 32)]
+
+
+class PfbQfoldScore(C.Structure):
+    _fields_ = [("period_q32", C.c_uint64), ("num_bins", C.c_uint32), ("bins_used", C.c_uint32), ("peak_bin", C.c_uint32),
+                ("reserved", C.c_uint32), ("peak_cells", C.c_uint64), ("peak_sum", C.c_float), ("peak_mean", C.c_float),
+                ("sum_means", C.c_double), ("sum_sq_means", C.c_double), ("cells", C.c_uint64)]
+
+
+class PfbRegridConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("row_samples", C.c_uint32), ("period_q32", C.c_uint64),
+                ("origin", C.c_uint64), ("elem_bytes", C.c_uint32), ("flags", C.c_uint32), ("device_id", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
 class PfbRdcfarConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("rows", C.c_uint32), ("gates", C.c_uint32), ("pitch", C.c_uint32),
                 ("doppler_half_width", C.c_uint32), ("guard_gates", C.c_uint32), ("train_gates", C.c_uint32),
@@ -432,6 +454,12 @@ EXPORTS = (
     "pfb_fold_describe", "pfb_fold_counts", "pfb_fold_create", "pfb_fold_destroy", "pfb_fold_reset",
     "pfb_fold_set_stream", "pfb_fold_sync", "pfb_fold_get_device", "pfb_fold_next_index", "pfb_fold_process",
     "pfb_fold_process_async", "pfb_fold_scores", "pfb_fold_profile", "pfb_fold_last_kernel",
+    "pfb_qfold_describe", "pfb_qfold_counts", "pfb_qfold_create", "pfb_qfold_destroy", "pfb_qfold_reset",
+    "pfb_qfold_set_index", "pfb_qfold_set_stream", "pfb_qfold_sync", "pfb_qfold_get_device", "pfb_qfold_next_index",
+    "pfb_qfold_process", "pfb_qfold_process_async", "pfb_qfold_scores", "pfb_qfold_profile", "pfb_qfold_last_kernel",
+    "pfb_regrid_create", "pfb_regrid_destroy", "pfb_regrid_reset", "pfb_regrid_set_index", "pfb_regrid_set_stream",
+    "pfb_regrid_sync", "pfb_regrid_get_device", "pfb_regrid_next_index", "pfb_regrid_outputs_for", "pfb_regrid_process",
+    "pfb_regrid_process_async", "pfb_regrid_doppler_frequencies",
     "pfb_rdcfar_describe", "pfb_rdcfar_create", "pfb_rdcfar_destroy", "pfb_rdcfar_reset", "pfb_rdcfar_set_stream",
     "pfb_rdcfar_sync", "pfb_rdcfar_get_device", "pfb_rdcfar_next_map", "pfb_rdcfar_get_stats", "pfb_rdcfar_process",
     "pfb_rdcfar_process_async", "pfb_rdcfar_to_pdw", "pfb_rdcfar_last_kernel",
@@ -446,7 +474,7 @@ EXPORTS = (
 )
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
-               "pfb_fold_set_tier", "pfb_deint_set_tier", "pfb_mop_set_tier",
+               "pfb_fold_set_tier", "pfb_deint_set_tier", "pfb_mop_set_tier", "pfb_qfold_set_tier",
                "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch", "pfb_last_entry", "pfb_plan_entry")
 
 _lib = None
@@ -744,7 +772,36 @@ def load() -> C.CDLL:
     lib.pfb_mop_last_kernel.restype = C.c_char_p
     lib.pfb_mop_figures.argtypes = [vp, u64, C.c_double, vp]
     lib.pfb_mop_pulses_from_pdw.argtypes = [vp, u64, C.c_double, C.c_double, vp]
+    lib.pfb_qfold_describe.argtypes = [C.POINTER(PfbQfoldConfig), C.POINTER(PfbQfoldPlan)]
+    lib.pfb_qfold_counts.argtypes = [C.POINTER(PfbQfoldConfig), u32, u64, u64, C.POINTER(u64)]
+    lib.pfb_qfold_create.argtypes = [C.POINTER(PfbQfoldConfig), C.POINTER(vp)]
+    lib.pfb_qfold_destroy.argtypes = [vp]
+    lib.pfb_qfold_reset.argtypes = [vp]
+    lib.pfb_qfold_set_index.argtypes = [vp, u64]
+    lib.pfb_qfold_set_stream.argtypes = [vp, vp]
+    lib.pfb_qfold_sync.argtypes = [vp]
+    lib.pfb_qfold_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_qfold_next_index.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_qfold_process.argtypes = [vp, vp, u64, u32]
+    lib.pfb_qfold_process_async.argtypes = [vp, vp, u64]
+    lib.pfb_qfold_scores.argtypes = [vp, vp, u64, u32]
+    lib.pfb_qfold_profile.argtypes = [vp, u32, vp, u64, u32]
+    lib.pfb_qfold_last_kernel.argtypes = [vp]
+    lib.pfb_qfold_last_kernel.restype = C.c_char_p
+    lib.pfb_regrid_create.argtypes = [C.POINTER(PfbRegridConfig), C.POINTER(vp)]
+    lib.pfb_regrid_destroy.argtypes = [vp]
+    lib.pfb_regrid_reset.argtypes = [vp]
+    lib.pfb_regrid_set_index.argtypes = [vp, u64]
+    lib.pfb_regrid_set_stream.argtypes = [vp, vp]
+    lib.pfb_regrid_sync.argtypes = [vp]
+    lib.pfb_regrid_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_regrid_next_index.argtypes = [vp, C.POINTER(u64)]
+    lib.pfb_regrid_outputs_for.argtypes = [vp, u64, C.POINTER(u64)]
+    lib.pfb_regrid_process.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    lib.pfb_regrid_process_async.argtypes = [vp, vp, u64, vp, u64, vp]
+    lib.pfb_regrid_doppler_frequencies.argtypes = [u64, u32, C.c_int, C.c_double, C.POINTER(C.c_double)]
     lib.pfb_fold_set_tier.argtypes = [vp, C.c_int]
+    lib.pfb_qfold_set_tier.argtypes = [vp, C.c_int, u64]
     lib.pfb_mop_set_tier.argtypes = [vp, C.c_int, u32, u64]
     lib.pfb_deint_set_tier.argtypes = [vp, C.c_int, C.c_int]
     lib.pfb_stft_set_experiment.argtypes = [vp, C.c_int]
