@@ -2194,6 +2194,147 @@ int pfb_regrid_process_async(pfb_regrid_handle* h, const void* d_x, uint64_t num
  * outside 1 .. 65536 or fs not finite. */
 int pfb_regrid_doppler_frequencies(uint64_t period_q32, uint32_t doppler_length, int centered, double fs, double* out);
 
+/* ---- PDW association: one record per pulse across channels ---------------------------------------
+ * The channelized extractor (pfb_pdw_extract) runs one edge state machine per channel and returns one PDW per
+ * (channel, pulse).  A pulse is never in one channel only: a chirp walks through the channels, a carrier near a channel
+ * edge sits in two, and every pulse edge is wideband and leaves one-frame rows in the neighbouring columns.  This unit
+ * joins the rows of one pulse: rows that touch in time and lie in neighbouring cells are linked, and a connected set
+ * of rows is one group with one record.  It is the piece that the deinterleaver's section lists as not built
+ * (clustering before the time search): pfb_deint_* takes the groups' first_tick.  Every figure is an integer or a
+ * comparison, so the results are bytes, not tolerances.  This comment is the definition: the device code
+ * (csrc/pfb_assoc.hip) and the tests' restatement (tests/assoc_ref.py) are each written from it.
+ *
+ * Input: N <= 2^20 items pfb_assoc_item (24 bytes) in host or device memory by `mem` (a device pointer is 8-byte
+ * aligned): start and length in the caller's ticks, cell (a PDW's bin), weight (a PDW's mag).  start is non-decreasing;
+ * the order among equal starts is the caller's.  With end = start + length, every end + g is below 2^62.  `reserved`
+ * is written as 0 and is not read.
+ *
+ * Parameters: Rc = cell_reach (0 .. 64), g = slack_ticks (0 .. 2^31 - 1), K = window_items (1 .. 4096), flags = 0.
+ *
+ * Edge.  Items i < j are linked iff j - i <= K, start[j] <= end[i] + g and |cell[i] - cell[j]| <= Rc.  start[j] >=
+ * start[i] by the order, which is the other half of the overlap test.  The search of item i ends at the first j with
+ * start[j] > end[i] + g, or at j = i + K.  Item i is CLIPPED iff i + K + 1 < N and start[i + K + 1] <= end[i] + g: the
+ * window ended the search, not the time.
+ *
+ * Groups.  A group is a connected component of that graph; its root is its smallest index; groups are numbered by
+ * ascending root.  labels[i] (int32) is the group of item i: every item has one, a lone item is a group of one.
+ *
+ * Record, pfb_assoc_group: first_tick = the root's start, end_tick = the largest end, length_sum, members, first_item =
+ * the root, best_item = the member with the largest weight, best_cell = its cell, cell_lo / cell_hi = the smallest and
+ * largest cell.  The order of the weights is that of the order-preserving uint32 key of the float's bits (all bits of
+ * a negative flipped, the sign bit of the rest flipped: -NaN < -Inf < -0 < +0 < +Inf < +NaN); ties go to the lowest index.
+ *
+ * Stats of the last good run: groups, edges (pairs that satisfy the rule), clipped, largest_group (members),
+ * linked_items (items in groups of two or more), rounds.  `rounds` is how often the device went round (below); it is
+ * reported, but it is not a function of the input alone and is never compared.  Everything else is a pure function of
+ * the list and the config: THE SAME CALL TWICE, AND HOST AND DEVICE INPUT, GIVE THE SAME BYTES.
+ *
+ * Device.  A first pass splits the items into arrays, checks the order and the bound and labels every item with its
+ * own index.  Edge pass: one lane per item walks the item's window; for K <= 1024 (pfb_assoc_plan.lds_window) a
+ * workgroup of 256 items (tile_items) first stages the start and cell of its items and of the K + 1 behind them, and
+ * its own end + g, in LDS as separate arrays (pfb_assoc_link_lds); above that, or by pfb_assoc_set_tier, it reads the
+ * window through the caches (pfb_assoc_link_global).  Components: rounds of hooking (for every edge whose two labels
+ * differ, an integer atomic min on the larger label's entry with the smaller; pfb_assoc_hook) and ceil(log2 N) + 1
+ * passes of pointer doubling (pfb_assoc_jump), until a round hooks nothing; the host reads one flag a round and gives
+ * up with PFB_ERR_INTERNAL after 64.  A label only decreases and never exceeds its index, so the fixed point is the
+ * smallest index of each component whatever the timing.  Records: root flags, a scan and an ordered scatter number the
+ * groups (pfb_assoc_number), integer min / max / add atomics and one 64-bit max of (key << 32 | ~index) fill them
+ * (pfb_assoc_gather).  There are no float atomics.  pfb_assoc_last_kernel joins the names of what the last call launched
+ * with '+'.
+ *
+ * Not built: a device sort (items arrive sorted; pfb_assoc_items_from_pdws sorts on the host), an async form (a
+ * round's decision returns to the host), a streaming form over chunks of a list, clustering on measured frequency or
+ * pulse width instead of the cell, weighted centroids (float sums: the host can form them from the labels).
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, cell_reach > 64, slack_ticks > 2^31 - 1, window_items outside 1 .. 4096, flags != 0; per call a null
+ * handle, an unknown mem, n > 2^20, a null items with n > 0, a null output (groups_out may be null only with capacity
+ * = 0, labels_out and the link arrays only with n = 0), a device pointer not aligned to its element (8 bytes for items
+ * and records, 4 for labels and the link arrays).  Then PFB_ERR_NO_DEVICE without a HIP device.  The order of the
+ * starts and the bound 2^62 are checked on the device, in the first pass over the list: a list that fails returns
+ * PFB_ERR_BAD_ARG with nothing written. */
+typedef struct pfb_assoc_item {   /* 24 bytes */
+  uint64_t start;             /* ticks                                                            */
+  uint32_t length;            /* ticks; end = start + length                                      */
+  int32_t cell;               /* the channel, or any integer coordinate                           */
+  float weight;               /* what picks the best member                                       */
+  uint32_t reserved;          /* 0                                                                */
+} pfb_assoc_item;
+
+typedef struct pfb_assoc_config {
+  uint32_t struct_size;       /* = sizeof(pfb_assoc_config)                                       */
+  uint32_t cell_reach;        /* Rc                                                               */
+  uint32_t slack_ticks;       /* g                                                                */
+  uint32_t window_items;      /* K: how far behind an item its links are looked for               */
+  uint32_t flags;             /* 0                                                                */
+  int32_t device_id;          /* -1 = the current device                                          */
+} pfb_assoc_config;
+
+typedef struct pfb_assoc_plan {  /* what pfb_assoc_describe reports; host only                    */
+  uint64_t scratch_bytes;     /* device memory a handle holds after pfb_assoc_run on n items      */
+  uint32_t tile_items;        /* items of one workgroup of the edge pass                          */
+  uint32_t lds_window;        /* the largest K the LDS tier takes                                 */
+  uint32_t lds_bytes;         /* of one workgroup of the edge pass at this K                      */
+  uint32_t reserved;          /* 0 */
+  char link_kernel[32];
+  char component_kernel[32];
+  char record_kernel[32];
+} pfb_assoc_plan;
+
+typedef struct pfb_assoc_group {  /* 48 bytes */
+  uint64_t first_tick;        /* the root's start                                                 */
+  uint64_t end_tick;          /* the largest end                                                  */
+  uint64_t length_sum;        /* of the members' lengths                                          */
+  uint32_t members;
+  uint32_t first_item;        /* the root: the group's smallest index                             */
+  uint32_t best_item;         /* the member of largest weight, ties to the lowest index           */
+  int32_t best_cell;          /* its cell                                                         */
+  int32_t cell_lo;            /* the smallest cell                                                */
+  int32_t cell_hi;            /* the largest                                                      */
+} pfb_assoc_group;
+
+typedef struct pfb_assoc_stats {
+  uint64_t groups;
+  uint64_t edges;
+  uint64_t clipped;
+  uint64_t largest_group;
+  uint64_t linked_items;
+  uint64_t rounds;            /* not a function of the input alone                                */
+} pfb_assoc_stats;
+
+typedef struct pfb_assoc_handle pfb_assoc_handle;
+
+/* Host only: validate cfg (everything pfb_assoc_create checks before the device) and report the plan for a list of
+ * n items (n > 2^20: PFB_ERR_BAD_ARG). */
+int pfb_assoc_describe(const pfb_assoc_config* cfg, uint64_t n, pfb_assoc_plan* plan_out);
+/* Lifecycle as pfb_deint_*.  The scratch grows with the longest list seen and is kept. */
+int pfb_assoc_create(const pfb_assoc_config* cfg, pfb_assoc_handle** out);
+int pfb_assoc_destroy(pfb_assoc_handle* h);
+int pfb_assoc_set_stream(pfb_assoc_handle* h, void* hip_stream);
+int pfb_assoc_sync(pfb_assoc_handle* h);
+int pfb_assoc_get_device(const pfb_assoc_handle* h, int* device_id);
+/* The whole association.  groups_out (capacity records) and labels_out (n int32) are host memory, or device memory
+ * with mem = PFB_MEM_DEVICE; *count_out (host) is the number of groups.  PFB_ERR_CAPACITY when that is more than
+ * capacity: *count_out holds the true count, neither array is written and the stats stay those of the run before.
+ * Synchronous. */
+int pfb_assoc_run(pfb_assoc_handle* h, const pfb_assoc_item* items, uint64_t n, uint32_t mem, pfb_assoc_group* groups_out,
+                  uint64_t capacity, uint64_t* count_out, int32_t* labels_out);
+/* The edge search alone: per item the lowest linked j > i (-1 for none) and the number of linked j > i, n int32 each.
+ * Changes no stats. */
+int pfb_assoc_links(pfb_assoc_handle* h, const pfb_assoc_item* items, uint64_t n, uint32_t mem, int32_t* first_link_out,
+                    int32_t* link_count_out);
+/* The kernels the last call launched, joined with '+'; "" before the first and after a call that launched none. */
+const char* pfb_assoc_last_kernel(const pfb_assoc_handle* h);
+/* The stats of the last pfb_assoc_run that returned PFB_OK; zeros before the first. */
+int pfb_assoc_get_stats(const pfb_assoc_handle* h, pfb_assoc_stats* stats_out);
+/* Host only: items from a PDW table in any order.  start = llrint((toa - t0) tick_rate), length = llrint(pw
+ * tick_rate), cell = bin, weight = (float)mag, sorted by start ascending and stably: items_out[i] comes from
+ * pdws[order_out[i]].  PFB_ERR_BAD_ARG as pfb_deint_ticks_from_toa: null pointers, n > 2^31, a tick_rate that is not
+ * finite or <= 0, a t0 that is not finite, a toa or pw that is not finite, a negative start or one >= 2^62, a length
+ * that is negative or >= 2^32; nothing is written then. */
+int pfb_assoc_items_from_pdws(const pfb_pdw* pdws, uint64_t n, double t0, double tick_rate, pfb_assoc_item* items_out,
+                              uint32_t* order_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,13 @@ int pfb_mop_set_tier(pfb_mop_handle* h, int tier, uint32_t grid_cap, uint64_t st
  * other value.  pfb_qfold_last_kernel names what ran. */
 int pfb_qfold_set_tier(pfb_qfold_handle* h, int tier, uint64_t step_cells);
 
+/* Which kernel walks the windows in the next calls of a pfb_assoc handle: 0 = the library's choice
+ * (pfb_assoc_plan.link_kernel), 1 = pfb_assoc_link_lds (PFB_ERR_UNSUPPORTED when window_items is above
+ * pfb_assoc_plan.lds_window), 2 = pfb_assoc_link_global.  Both give the same bytes; the tests run one list through
+ * them, the meter (tools/assoc_rate.py) times them.  PFB_ERR_BAD_ARG for any other value.  pfb_assoc_last_kernel names
+ * what ran. */
+int pfb_assoc_set_tier(pfb_assoc_handle* h, int tier);
+
 /* The fused-kernel table, row by row in lookup order (host only, no device needed): what the tests walk, so that a
  * registered plan cannot go untested.  Rows of one (M, P, D, sample_format) are that shape's variants 0, 1, ... */
 typedef struct {

@@ -5,6 +5,8 @@ The arithmetic lives in libpfb_channelizer.so (HIP, gfx950) behind the C ABI of
 include/pfb_channelizer.h; this package is the thin host side.
 """
 from ._lib import LIB_PATH, PfbError  # noqa: F401
+from .associate import (ASSOC_ITEM_DTYPE, GROUP_DTYPE, PulseAssociator, associate, associate_pdws,  # noqa: F401
+                        describe_associator, fuse_pdws)
 from .cfar import (Cfar, cfar_alpha, detect, detect_pulses, detections_to_pdws,  # noqa: F401
                    pulse_detections_from_iq_file)
 from .channelizer import Channelizer, center_frequencies, design_prototype, pinned_empty  # noqa: F401
@@ -38,6 +40,8 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "Trace", "Envelope", "envelope", "envelope_from_iq_file",
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
+           "PulseAssociator", "associate", "associate_pdws", "fuse_pdws", "describe_associator", "ASSOC_ITEM_DTYPE",
+           "GROUP_DTYPE",
            "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",
            "FinePriFold", "describe_fine_fold", "period_q32", "period_samples", "refine_pri", "find_pri_fine",
            "Regrid", "regrid", "regrid_doppler_frequencies", "detect_pulse_train_fine", "QSCORE_DTYPE",

@@ -314,6 +314,33 @@ class PfbDeintStats(C.Structure):
                 ("pulses_assigned", C.c_uint64)]
 
 
+class PfbAssocItem(C.Structure):
+    _fields_ = [("start", C.c_uint64), ("length", C.c_uint32), ("cell", C.c_int32), ("weight", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
+class PfbAssocConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cell_reach", C.c_uint32), ("slack_ticks", C.c_uint32),
+                ("window_items", C.c_uint32), ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbAssocPlan(C.Structure):
+    _fields_ = [("scratch_bytes", C.c_uint64), ("tile_items", C.c_uint32), ("lds_window", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("reserved", C.c_uint32), ("link_kernel", C.c_char * 32),
+                ("component_kernel", C.c_char * 32), ("record_kernel", C.c_char * 32)]
+
+
+class PfbAssocGroup(C.Structure):
+    _fields_ = [("first_tick", C.c_uint64), ("end_tick", C.c_uint64), ("length_sum", C.c_uint64),
+                ("members", C.c_uint32), ("first_item", C.c_uint32), ("best_item", C.c_uint32), ("best_cell", C.c_int32),
+                ("cell_lo", C.c_int32), ("cell_hi", C.c_int32)]
+
+
+class PfbAssocStats(C.Structure):
+    _fields_ = [("groups", C.c_uint64), ("edges", C.c_uint64), ("clipped", C.c_uint64), ("largest_group", C.c_uint64),
+                ("linked_items", C.c_uint64), ("rounds", C.c_uint64)]
+
+
 class PfbMopConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample_format", C.c_uint32), ("bit_width", C.c_uint32),
                 ("trim_samples", C.c_uint32), ("max_negatives", C.c_uint32), ("device_id", C.c_int32)]
@@ -460,6 +487,9 @@ EXPORTS = (
     "pfb_regrid_create", "pfb_regrid_destroy", "pfb_regrid_reset", "pfb_regrid_set_index", "pfb_regrid_set_stream",
     "pfb_regrid_sync", "pfb_regrid_get_device", "pfb_regrid_next_index", "pfb_regrid_outputs_for", "pfb_regrid_process",
     "pfb_regrid_process_async", "pfb_regrid_doppler_frequencies",
+    "pfb_assoc_describe", "pfb_assoc_create", "pfb_assoc_destroy", "pfb_assoc_set_stream", "pfb_assoc_sync",
+    "pfb_assoc_get_device", "pfb_assoc_run", "pfb_assoc_links", "pfb_assoc_last_kernel", "pfb_assoc_get_stats",
+    "pfb_assoc_items_from_pdws",
     "pfb_rdcfar_describe", "pfb_rdcfar_create", "pfb_rdcfar_destroy", "pfb_rdcfar_reset", "pfb_rdcfar_set_stream",
     "pfb_rdcfar_sync", "pfb_rdcfar_get_device", "pfb_rdcfar_next_map", "pfb_rdcfar_get_stats", "pfb_rdcfar_process",
     "pfb_rdcfar_process_async", "pfb_rdcfar_to_pdw", "pfb_rdcfar_last_kernel",
@@ -475,6 +505,7 @@ EXPORTS = (
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
                "pfb_fold_set_tier", "pfb_deint_set_tier", "pfb_mop_set_tier", "pfb_qfold_set_tier",
+               "pfb_assoc_set_tier",
                "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch", "pfb_last_entry", "pfb_plan_entry")
 
 _lib = None
@@ -800,6 +831,19 @@ def load() -> C.CDLL:
     lib.pfb_regrid_process.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
     lib.pfb_regrid_process_async.argtypes = [vp, vp, u64, vp, u64, vp]
     lib.pfb_regrid_doppler_frequencies.argtypes = [u64, u32, C.c_int, C.c_double, C.POINTER(C.c_double)]
+    lib.pfb_assoc_describe.argtypes = [C.POINTER(PfbAssocConfig), u64, C.POINTER(PfbAssocPlan)]
+    lib.pfb_assoc_create.argtypes = [C.POINTER(PfbAssocConfig), C.POINTER(vp)]
+    lib.pfb_assoc_destroy.argtypes = [vp]
+    lib.pfb_assoc_set_stream.argtypes = [vp, vp]
+    lib.pfb_assoc_sync.argtypes = [vp]
+    lib.pfb_assoc_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_assoc_run.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp]
+    lib.pfb_assoc_links.argtypes = [vp, vp, u64, u32, vp, vp]
+    lib.pfb_assoc_last_kernel.argtypes = [vp]
+    lib.pfb_assoc_last_kernel.restype = C.c_char_p
+    lib.pfb_assoc_get_stats.argtypes = [vp, C.POINTER(PfbAssocStats)]
+    lib.pfb_assoc_items_from_pdws.argtypes = [vp, u64, C.c_double, C.c_double, vp, vp]
+    lib.pfb_assoc_set_tier.argtypes = [vp, C.c_int]
     lib.pfb_fold_set_tier.argtypes = [vp, C.c_int]
     lib.pfb_qfold_set_tier.argtypes = [vp, C.c_int, u64]
     lib.pfb_mop_set_tier.argtypes = [vp, C.c_int, u32, u64]
