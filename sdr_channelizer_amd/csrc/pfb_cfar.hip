@@ -440,10 +440,6 @@ __global__ void __launch_bounds__(256) cfar_carry(const CfarParams p) {
   for (long long i = t0; i < p.s_keep; i += stride) p.S_out[i] = p.S[p.s_from + i];
 }
 
-unsigned grid_for(uint64_t items, unsigned per_block) {
-  return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + per_block - 1) / per_block, 1), kMaxGrid);
-}
-
 // ---------------------------------------------------------------------------------
 // host: checks and plan
 
@@ -593,21 +589,21 @@ int create_cfar(const pfb_cfar_config* cfg, pfb_cfar_handle** out) {
 
 template <int E>
 void launch_step(const CfarParams& p, bool sums, bool decide, bool carry, hipStream_t s) {
-  if (sums) hipLaunchKernelGGL((cfar_sum<E>), dim3(grid_for((uint64_t)(p.nbc1 - p.nbc0) * std::max(p.C / 4, 1), 256)), dim3(256), 0, s, p);
+  if (sums) hipLaunchKernelGGL((cfar_sum<E>), dim3(grid_for((uint64_t)(p.nbc1 - p.nbc0) * std::max(p.C / 4, 1), 256, kMaxGrid)), dim3(256), 0, s, p);
   if (decide) {
     if (p.dec_blocks > 0) {
-      hipLaunchKernelGGL(cfar_threshold, dim3(grid_for(p.dec_blocks, 256)), dim3(256), 0, s, p);
-      hipLaunchKernelGGL((cfar_mask<E>), dim3(grid_for(((uint64_t)p.nwords + 3) / 4, 4)), dim3(256), 0, s, p);
+      hipLaunchKernelGGL(cfar_threshold, dim3(grid_for(p.dec_blocks, 256, kMaxGrid)), dim3(256), 0, s, p);
+      hipLaunchKernelGGL((cfar_mask<E>), dim3(grid_for(((uint64_t)p.nwords + 3) / 4, 4, kMaxGrid)), dim3(256), 0, s, p);
     }
-    const unsigned tiles = grid_for(p.ntiles, 1);
+    const unsigned tiles = grid_for(p.ntiles, 1, kMaxGrid);
     hipLaunchKernelGGL(cfar_tile_last, dim3(tiles), dim3(256), 0, s, p);
     hipLaunchKernelGGL(cfar_tile_scan, dim3(1), dim3(256), 0, s, p);
     hipLaunchKernelGGL(cfar_word_starts, dim3(tiles), dim3(256), 0, s, p);
     hipLaunchKernelGGL(cfar_start_scan, dim3(1), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(cfar_write_starts, dim3(grid_for(p.nwords, 256)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(cfar_write_starts, dim3(grid_for(p.nwords, 256, kMaxGrid)), dim3(256), 0, s, p);
     hipLaunchKernelGGL((cfar_runs<E>), dim3(1024), dim3(64), 0, s, p);
   }
-  if (carry) hipLaunchKernelGGL((cfar_carry<E>), dim3(grid_for(std::max(p.keep_len, p.s_keep), 256)), dim3(256), 0, s, p);
+  if (carry) hipLaunchKernelGGL((cfar_carry<E>), dim3(grid_for(std::max(p.keep_len, p.s_keep), 256, kMaxGrid)), dim3(256), 0, s, p);
 }
 
 // One step: m <= 2^24 device cells (or the flush), queued on the handle's stream; the host counters advance
@@ -716,16 +712,6 @@ int restore_state(pfb_cfar_handle* h, const HostCounters& saved) {
   if (sums) HIP_TRY(hipMemcpyAsync(h->d_S[hc.slot], h->d_S[2], sums * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_state, h->d_state + 1, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  return PFB_OK;
-}
-
-int grow(void** p, size_t* have, size_t want) {
-  if (want <= *have) return PFB_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  HIP_TRY(hipMalloc(p, want));
-  *have = want;
   return PFB_OK;
 }
 

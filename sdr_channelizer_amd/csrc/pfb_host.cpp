@@ -49,6 +49,20 @@ int switch_stream(int device, hipStream_t* stream, hipEvent_t* ev_switch, hipStr
   return PFB_OK;
 }
 
+int grow(void** p, size_t* have, size_t want) {
+  if (want <= *have) return PFB_OK;
+  (void)hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  HIP_TRY(hipMalloc(p, want));
+  *have = want;
+  return PFB_OK;
+}
+
+unsigned grid_for(uint64_t items, unsigned per_block, unsigned cap) {
+  return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + per_block - 1) / per_block, 1), cap);
+}
+
 hipError_t upload_twiddles(uint32_t n, float2** d_tw) {
   std::vector<float2> tw(n);
   const double two_pi = 6.283185307179586476925286766559;

@@ -47,6 +47,12 @@ int dwell_check_config(const pfb_dwell_config* cfg, bool from_file);
 // pfb_*_set_stream: what the old stream still has queued for the handle comes first on the new one
 int switch_stream(int device, hipStream_t* stream, hipEvent_t* ev_switch, hipStream_t next);
 
+// a grow-only device buffer: at least `want` bytes at *p, *have of them now; what it held is not kept
+int grow(void** p, size_t* have, size_t want);
+
+// workgroups for `items` at `per_block` each: one at least, `cap` at most (the kernels stride)
+unsigned grid_for(uint64_t items, unsigned per_block, unsigned cap);
+
 // tw[m] = e^{+j 2 pi m / n}, m = 0..n-1 (from float64), into a new device array
 hipError_t upload_twiddles(uint32_t n, float2** d_tw);
 

@@ -519,16 +519,6 @@ int pd_flush_open(pfb_pd_handle* h, void* out) {  // the open CPI, from the carr
   return PFB_OK;
 }
 
-int grow(void** p, size_t* have, size_t want) {
-  if (want <= *have) return PFB_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  HIP_TRY(hipMalloc(p, want));
-  *have = want;
-  return PFB_OK;
-}
-
 void undo(pfb_pd_handle* h, const HostState& saved) {
   put_back(&h->hs, saved, h->carry_reused, h->cfg.origin, (uint64_t)h->cfg.num_pulses * h->cfg.pri);
 }

@@ -7,11 +7,11 @@ import numpy as np
 
 import rdcfar_cases
 
-GRID_CAP = 1 << 16      # kMaxGrid in pfb_cfar.hip, pfb_rdcfar.hip and pfb_oscfar.hip
+GRID_CAP = 1 << 16      # kMaxGrid in pfb_cfar.hip and in pfb_rdmap.hpp (pfb_rdcfar.hip, pfb_oscfar.hip)
 RUN_GRID = 1024         # workgroups of the cfar_runs launch in launch_step (pfb_cfar.hip), one wave and one run each
-STEP_CELLS = 1 << 24    # kStepCells in pfb_cfar.hip, pfb_rdcfar.hip and pfb_oscfar.hip: cells of a step at most
-STEP_WORDS = 1 << 18    # kStepWords in pfb_rdcfar.hip and pfb_oscfar.hip: words of 64 gates of a step at most
-TILE = 256              # kTileGates in pfb_rdcfar.hip and pfb_oscfar.hip (plan.tile_gates)
+STEP_CELLS = 1 << 24    # kStepCells in pfb_cfar.hip and pfb_rdmap.hpp: cells of a step at most
+STEP_WORDS = 1 << 18    # kStepWords in pfb_rdmap.hpp: words of 64 gates of a step at most
+TILE = 256              # kTileGates in pfb_rdmap.hpp (plan.tile_gates)
 
 noise_maps = rdcfar_cases.noise_maps
 

@@ -30,20 +30,31 @@ def shifts(pattern, text):
 
 
 def test_the_constants_are_the_sources():
-    for name in ("pfb_cfar.hip", "pfb_rdcfar.hip", "pfb_oscfar.hip"):
+    # the 1-D unit has its constants; the two 2-D units have theirs in the core they share, and no other
+    for name in ("pfb_cfar.hip", "pfb_rdmap.hpp"):
         text = source(name)
         assert shifts(r"constexpr unsigned kMaxGrid = 1u << (\d+);", text) == [16], name
         assert shifts(r"constexpr uint64_t kStepCells = \(uint64_t\)1 << (\d+);", text) == [24], name
-        assert "std::max<uint64_t>((items + per_block - 1) / per_block, 1), kMaxGrid)" in text, name
+        # the clamp is one function of the host plumbing, and every grid of the unit takes the unit's cap through it
+        assert text.count("grid_for(") == text.count(", kMaxGrid)") > 0 and "unsigned grid_for" not in text, name
+    clamp = "std::min<uint64_t>(std::max<uint64_t>((items + per_block - 1) / per_block, 1), cap)"
+    assert source("pfb_host.cpp").count(clamp) == 1
+    assert len(re.findall(r"^unsigned grid_for\(uint64_t items, unsigned per_block, unsigned cap\) \{", source("pfb_host.cpp"), re.M)) == 1
     assert K.GRID_CAP == 1 << 16 and K.STEP_CELLS == 1 << 24 and K.STEP_WORDS == 1 << 18
+    core = source("pfb_rdmap.hpp")
+    assert shifts(r"constexpr uint64_t kStepWords = \(uint64_t\)1 << (\d+);", core) == [18]
+    assert shifts(r"constexpr int kTileGates = (\d+);", core) == [K.TILE]
+    assert core.count("std::min(kStepCells / h->map_cells, kStepWords / h->map_words)") == 1
+    assert len(re.findall(r"const unsigned units = grid_for\(\(uint64_t\)m \* p\.NB \* p\.NT, 1, kMaxGrid\)", core)) == 1
+    assert core.count("const char* kernel = h->cells(p, units);") == 1     # the units launch on that grid
     for name, cells in (("pfb_rdcfar.hip", "rdcfar_cells"), ("pfb_oscfar.hip", "oscfar_cells")):
         text = source(name)
-        assert shifts(r"constexpr uint64_t kStepWords = \(uint64_t\)1 << (\d+);", text) == [18], name
-        assert shifts(r"constexpr int kTileGates = (\d+);", text) == [K.TILE], name
-        assert "std::min(kStepCells / h->map_cells, kStepWords / h->map_words)" in text
+        for constant in ("kMaxGrid", "kStepCells", "kStepWords", "kTileGates"):
+            assert not re.search(r"constexpr \w+ %s\b" % constant, text), (name, constant)
+        assert "grid_for(" not in text, name
         assert "for (long long u = blockIdx.x; u < units; u += gridDim.x)" in text
-        assert re.search(r"const unsigned units = grid_for\(\(uint64_t\)m \* p\.NB \* p\.NT, 1\)", text)
         assert len(re.findall(cells + r"<(?:true|false)>, dim3\(units\), dim3\(kTileGates\)", text)) == 2, name
+        assert re.search(r"const char\* cells\(\w+& p, unsigned units\) const \{", text), name
     runs = re.findall(r"hipLaunchKernelGGL\(\(cfar_runs<E>\), dim3\((\d+)\), dim3\((\d+)\)", source("pfb_cfar.hip"))
     assert runs == [(str(K.RUN_GRID), "64")]
     assert "for (int c = blockIdx.x; c < sc.candidates; c += gridDim.x)" in source("pfb_cfar.hip")

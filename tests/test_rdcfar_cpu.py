@@ -405,9 +405,14 @@ def test_rdcfar_entry_points_sit_under_the_abi_guard():
     assert src.count('extern "C"') == len(found) + 1
     from sdr_channelizer_amd import build
     assert "pfb_rdcfar.hip" in build.SOURCES
-    create = src[src.index("int create_rdcfar("):]
-    create = create[: create.index("\n}\n")]
-    assert create.index("rdcfar_check(cfg") < create.index("resolve_device") < create.index("allocate_rdcfar(")
+    # the unit's create checks the config first; the create path it shares with pfb_oscfar.hip takes the device, then memory
+    create = found["pfb_rdcfar_create"]
+    assert create.index("rdcfar_check(cfg") < create.index("create_detector(")
+    assert "resolve_device" not in src and "hipMalloc" not in src
+    core = open(os.path.join(ROOT, "sdr_channelizer_amd", "csrc", "pfb_rdmap.hpp")).read()
+    shared = core[core.index("int create_detector("):]
+    shared = shared[: shared.index("\n}\n")]
+    assert shared.index("resolve_device") < shared.index("new H()") < shared.index("h->allocate()")
 
 
 def test_to_pdw_and_event_fit():
