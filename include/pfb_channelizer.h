@@ -1769,7 +1769,7 @@ const char* pfb_oscfar_last_kernel(const pfb_oscfar_handle* h);
  * b's chain in one lane (pfb_deint_mark_walk).  pfb_deint_last_kernel joins the names of what the last call launched with '+'.
  *
  * Not built: an async form (the decision of every round returns to the host), staggered, jittered-by-design or
- * sliding PRIs, frequency or pulse-width clustering before the time search (split the table by `bin` first), a
+ * sliding PRIs, frequency or pulse-width clustering inside this unit (pfb_cluster_* splits the list first), a
  * streaming form over PDW chunks, the PRI transform's phase weighting, a histogram fused into the detectors' emit.
  *
  * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
@@ -2244,7 +2244,7 @@ int pfb_regrid_doppler_frequencies(uint64_t period_q32, uint32_t doppler_length,
  *
  * Not built: a device sort (items arrive sorted; pfb_assoc_items_from_pdws sorts on the host), an async form (a
  * round's decision returns to the host), a streaming form over chunks of a list, clustering on measured frequency or
- * pulse width instead of the cell, weighted centroids (float sums: the host can form them from the labels).
+ * pulse width instead of the cell (that is pfb_cluster_*), weighted centroids (float sums: the host can form them from the labels).
  *
  * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
  * struct_size, cell_reach > 64, slack_ticks > 2^31 - 1, window_items outside 1 .. 4096, flags != 0; per call a null
@@ -2334,6 +2334,191 @@ int pfb_assoc_get_stats(const pfb_assoc_handle* h, pfb_assoc_stats* stats_out);
  * that is negative or >= 2^32; nothing is written then. */
 int pfb_assoc_items_from_pdws(const pfb_pdw* pdws, uint64_t n, double t0, double tick_rate, pfb_assoc_item* items_out,
                               uint32_t* order_out);
+
+/* ---- PDW clustering: cells of frequency and pulse width before the time search -------------------
+ * The deinterleaver (pfb_deint_*) searches ONE time-ordered list for periods; with tens of trains in it thousands of
+ * histogram bins pass the candidate rule and nearly all are refused.  Emitters differ in frequency and pulse width
+ * long before they differ in period, so the first stage of a deinterleaver is a cell clustering on those two: this
+ * unit.  It takes two integer features per pulse, counts the pulses of every cell of a U x V grid, joins the dense
+ * cells that lie near each other into clusters, and returns per pulse its cluster and per cluster the pulses' indices
+ * in the caller's (time) order, ready to be cut out of the tick list (pfb_cluster_gather) and searched one cluster at
+ * a time.  Every figure is an integer or a comparison, so the results are bytes, not tolerances.  This comment is the
+ * definition: the device code (csrc/pfb_cluster.hip) and the tests' restatement (tests/cluster_ref.py) are each
+ * written from it.
+ *
+ * Input: N <= 2^20 items pfb_cluster_item {int32 u; int32 v;} (8 bytes) in host or device memory by `mem` (a device
+ * pointer is 8-byte aligned), in the caller's order: the time order the deinterleaver wants.  Any int32 is a valid u
+ * or v.
+ *
+ * Parameters: U = cells_u, V = cells_v (each >= 1, U V <= 2^20), reach_u, reach_v (0 .. 8), min_cell_count
+ * (1 .. 2^20), min_pulses (1 .. 2^20), flags (0 or PFB_CLUSTER_BORDER).
+ *
+ * An item is IN THE GRID iff 0 <= u < U and 0 <= v < V; its cell is g = u V + v, and cell g has u = g / V, v = g mod V.
+ *  1. Histogram: H[g], uint32, is the number of in-grid items of cell g.  A count of a set: the order is free.
+ *  2. Dense: cell g is dense iff H[g] >= min_cell_count.
+ *  3. Components: dense cells (u, v) and (u', v') are linked iff |u - u'| <= reach_u and |v - v'| <= reach_v.  A
+ *     component is a connected set of dense cells; its root is its lowest g.
+ *  4. Border, only with PFB_CLUSTER_BORDER: a cell with 0 < H[g] < min_cell_count whose reach box (the cells within
+ *     reach_u and reach_v of it) holds at least one dense cell joins the component of the LOWEST ROOT among the dense
+ *     cells of its box.  It links nothing onwards: two components that share a border cell stay two.  Without the
+ *     flag such cells belong to nobody.
+ *  5. Clusters: pulses(component) = the sum of H over its dense and border cells.  A component is a cluster iff
+ *     pulses >= min_pulses.  Clusters are numbered 0 .. G - 1 by ascending root.  G <= 65535: a call that finds more,
+ *     or more than its `capacity`, returns PFB_ERR_CAPACITY with *count_out = G, writes nothing else and leaves the
+ *     stats those of the run before.
+ *  6. Output.  labels[i], int32: the cluster of item i, or -1 (outside the grid, in a cell of no component, or in a
+ *     component under min_pulses).  One pfb_cluster_group per cluster: root_u, root_v; pulses; cells (dense and
+ *     border); u_min .. v_max over its cells; sum_u, sum_v over its items (the host forms centroids, as for
+ *     pfb_assoc_*); peak_u, peak_v, peak_count: the cell of largest H, ties to the lowest g; first_item, the lowest
+ *     item index.  order_out[N], uint32: the item indices sorted by (label with -1 last, index) -- a STABLE partition,
+ *     time order is kept within a cluster.  offsets_out[G + 2], uint32: cluster c's items are order[offsets[c] ..
+ *     offsets[c + 1]), the unassigned are order[offsets[G] .. offsets[G + 1]) and offsets[G + 1] = N.  order_out and
+ *     offsets_out may be null together.
+ * Everything is a pure function of the list and the config: THE SAME CALL TWICE, AND HOST AND DEVICE INPUT, GIVE THE
+ * SAME BYTES.
+ *
+ * Stats of the last good run: outside (items not in the grid), unassigned (in-grid items with label -1), dense_cells,
+ * border_cells (cells that step 4 joined), components (before min_pulses), hook_rounds.  hook_rounds is defined by
+ * the rounds of step 3 as the device makes them, and is a function of the input too.  Every dense cell starts with
+ * the label L[g] = g.  One round: with L as it stands, every linked pair of dense cells whose labels a = L[g] < b =
+ * L[g'] differ lowers the new label of cell b to at most a (all pairs read the same L; the new labels start as L);
+ * then every cell's label is replaced by the label at the end of its chain g -> L[g] -> ... .  hook_rounds counts the
+ * rounds made, the last of which lowered nothing; it is 0 when no cell is dense.
+ *
+ * Device.  Histogram: one lane per item, pfb_cluster_plan.hist_tile items a workgroup; for U V <= 8192
+ * (pfb_cluster_plan.lds_cells) a workgroup counts in a private LDS histogram that it adds to the global one once
+ * (pfb_cluster_hist_lds), above that straight into the global one (pfb_cluster_hist_global).  In both a wave first
+ * combines the lanes that hit the same cell as its first remaining lane, twice, so that a train that sits in one cell
+ * costs one atomic a wave.  Components: one lane per cell, a workgroup takes a block of block_u x block_v cells and
+ * stages their labels with a halo of the reach in LDS (pfb_cluster_hook); a lowered label is an integer atomic min
+ * into the new labels; ceil(log2 U V) + 1 passes of pointer doubling follow (pfb_cluster_jump); the host reads one
+ * flag a round and gives up with PFB_ERR_INTERNAL after 64.  Border: one lane per cell, a min over the box
+ * (pfb_cluster_border).  Per-root integer add / min / max atomics and one 64-bit max of (H << 32 | ~g) collect what a
+ * record takes from the cells (pfb_cluster_cells); root flags, a scan and an ordered scatter number the clusters
+ * (pfb_cluster_number).  Labels: one lane per item, label_tile items a workgroup, a gather through the cell table and
+ * wave-combined 64-bit adds and a min for sum_u, sum_v and first_item (pfb_cluster_label).  Partition: an LSD radix
+ * over the label (-1 taken as G) with 8-bit digits, one pass when G + 1 <= 256 and two above; a pass is a digit
+ * histogram per tile of part_tile items, a scan over (digit, tile) and a rank inside the tile made of wave ballots,
+ * the count of lower lanes and the counts of lower waves through LDS -- no atomics, so the order never depends on
+ * arrival (pfb_cluster_part1 / pfb_cluster_part2).  There is no float on the device.  pfb_cluster_last_kernel joins
+ * the names of what the last call launched with '+'.
+ *
+ * Not built: more than two features, float features on the device, an async form (a round's decision returns to the
+ * host), a streaming form over chunks of a list, density-reachability beyond the border rule, the deinterleaver's
+ * rounds for all clusters in one launch.
+ *
+ * Every argument is validated before the device is touched, in this order.  PFB_ERR_BAD_ARG: null pointers, a wrong
+ * struct_size, cells_u = 0, cells_v = 0, U V > 2^20, reach_u > 8, reach_v > 8, min_cell_count outside 1 .. 2^20,
+ * min_pulses outside 1 .. 2^20, flags with a bit other than PFB_CLUSTER_BORDER; per call a null handle, an unknown
+ * mem, n > 2^20, a null items with n > 0, a null output (count_out never; groups_out may be null only with capacity =
+ * 0, labels_out only with n = 0; order_out and offsets_out only together), a device pointer not aligned to its
+ * element (8 bytes for items and records, 4 for labels, order, offsets, counts and roots); for pfb_cluster_gather an
+ * elem_bytes other than 4 or 8, n > 2^20, a null src, order or dst with n > 0, src or dst not aligned to elem_bytes,
+ * order not aligned to 4.  PFB_ERR_CAPACITY: capacity_cells < U V.  Then PFB_ERR_NO_DEVICE without a HIP device. */
+#define PFB_CLUSTER_BORDER 1u     /* step 4 */
+
+typedef struct pfb_cluster_item {   /* 8 bytes */
+  int32_t u;                  /* the first feature's cell: frequency                              */
+  int32_t v;                  /* the second: pulse width; 0 where there is one feature            */
+} pfb_cluster_item;
+
+typedef struct pfb_cluster_config {
+  uint32_t struct_size;       /* = sizeof(pfb_cluster_config)                                     */
+  uint32_t cells_u;           /* U                                                                */
+  uint32_t cells_v;           /* V                                                                */
+  uint32_t reach_u;
+  uint32_t reach_v;
+  uint32_t min_cell_count;    /* items that make a cell dense                                     */
+  uint32_t min_pulses;        /* items that make a component a cluster                            */
+  uint32_t flags;             /* 0 or PFB_CLUSTER_BORDER                                          */
+  int32_t device_id;          /* -1 = the current device                                          */
+} pfb_cluster_config;
+
+typedef struct pfb_cluster_plan {  /* what pfb_cluster_describe reports; host only                */
+  uint64_t scratch_bytes;     /* device memory a handle holds after pfb_cluster_run on n items    */
+  uint32_t cells;             /* U V                                                              */
+  uint32_t lds_cells;         /* the largest U V the LDS histogram takes                          */
+  uint32_t hist_tile;         /* items of one workgroup of the histogram                          */
+  uint32_t label_tile;        /* of the label kernel                                              */
+  uint32_t part_tile;         /* of a partition pass                                              */
+  uint32_t block_u;           /* cells of one workgroup of the component kernels, along u         */
+  uint32_t block_v;           /* and along v; block_u block_v = 256                               */
+  uint32_t lds_bytes;         /* of one histogram workgroup                                       */
+  uint32_t max_clusters;      /* 65535                                                            */
+  uint32_t reserved;          /* 0 */
+  char histogram_kernel[32];
+  char component_kernel[32];
+  char partition_kernel[32];
+} pfb_cluster_plan;
+
+typedef struct pfb_cluster_group {  /* 64 bytes */
+  int32_t root_u;             /* the lowest cell of the cluster                                   */
+  int32_t root_v;
+  uint32_t pulses;            /* items                                                            */
+  uint32_t cells;             /* dense and border cells                                           */
+  int32_t u_min;              /* over its cells                                                   */
+  int32_t u_max;
+  int32_t v_min;
+  int32_t v_max;
+  int64_t sum_u;              /* over its items                                                   */
+  int64_t sum_v;
+  int32_t peak_u;             /* the cell of largest H, ties to the lowest g                      */
+  int32_t peak_v;
+  uint32_t peak_count;        /* its H                                                            */
+  uint32_t first_item;        /* the lowest item index                                            */
+} pfb_cluster_group;
+
+typedef struct pfb_cluster_stats {
+  uint64_t outside;
+  uint64_t unassigned;
+  uint64_t dense_cells;
+  uint64_t border_cells;
+  uint64_t components;
+  uint64_t hook_rounds;
+} pfb_cluster_stats;
+
+typedef struct pfb_cluster_handle pfb_cluster_handle;
+
+/* Host only: validate cfg (everything pfb_cluster_create checks before the device) and report the plan for a list of
+ * n items (n > 2^20: PFB_ERR_BAD_ARG). */
+int pfb_cluster_describe(const pfb_cluster_config* cfg, uint64_t n, pfb_cluster_plan* plan_out);
+/* Lifecycle as pfb_assoc_*.  The scratch grows with the longest list seen and is kept. */
+int pfb_cluster_create(const pfb_cluster_config* cfg, pfb_cluster_handle** out);
+int pfb_cluster_destroy(pfb_cluster_handle* h);
+int pfb_cluster_set_stream(pfb_cluster_handle* h, void* hip_stream);
+int pfb_cluster_sync(pfb_cluster_handle* h);
+int pfb_cluster_get_device(const pfb_cluster_handle* h, int* device_id);
+/* Steps 1 to 6.  groups_out (capacity records), labels_out (n int32), order_out (n uint32) and offsets_out (G + 2
+ * uint32, so capacity + 2 always hold them) are host memory, or device memory with mem = PFB_MEM_DEVICE; *count_out
+ * (host) is G.  PFB_ERR_CAPACITY when G is more than capacity or than 65535: *count_out holds G, no array is written
+ * and the stats stay those of the run before.  Synchronous. */
+int pfb_cluster_run(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n, uint32_t mem,
+                    pfb_cluster_group* groups_out, uint64_t capacity, uint64_t* count_out, int32_t* labels_out,
+                    uint32_t* order_out, uint32_t* offsets_out);
+/* Step 1 alone: U V uint32 counts.  Changes no stats. */
+int pfb_cluster_histogram(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n, uint32_t mem,
+                          uint32_t* counts_out, uint64_t capacity_cells);
+/* Steps 1 to 4 alone: per cell the root g of its component, int32, -1 for none, U V of them.  Border cells count as
+ * members; components under min_pulses are included.  For plots and for the tests.  Changes no stats. */
+int pfb_cluster_cell_roots(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n, uint32_t mem,
+                           int32_t* roots_out, uint64_t capacity_cells);
+/* dst[k] = src[order[k]] for k < n, elements of elem_bytes = 4 or 8, all three in device memory, on the handle's
+ * stream; returns without waiting (pfb_cluster_sync waits).  Every order[k] indexes src: with order_out of
+ * pfb_cluster_run and the tick list the items came from, dst is the list cut into per-cluster lists, cluster c at
+ * dst[offsets[c] .. offsets[c + 1]), each in time order: what pfb_deint_run takes. */
+int pfb_cluster_gather(pfb_cluster_handle* h, const void* src, uint32_t elem_bytes, const uint32_t* order, uint64_t n,
+                       void* dst);
+/* The kernels the last call launched, joined with '+'; "" before the first. */
+const char* pfb_cluster_last_kernel(const pfb_cluster_handle* h);
+/* The stats of the last pfb_cluster_run that returned PFB_OK; zeros before the first. */
+int pfb_cluster_get_stats(const pfb_cluster_handle* h, pfb_cluster_stats* stats_out);
+/* Host only: items from a PDW table, in the table's order, n PDWs stride_bytes apart (sizeof(pfb_pdw) for a plain
+ * array).  u = floor((freq - freq0) / freq_step); v = pw_step > 0 ? floor(pw / pw_step) : 0.  A figure that is not
+ * finite or does not fit an int32 gives the item u = INT32_MIN, v = 0, which is outside every grid.  PFB_ERR_BAD_ARG
+ * for null pointers with n > 0, n > 2^31, stride_bytes < sizeof(pfb_pdw) or no multiple of 8, a freq0 that is not
+ * finite, a freq_step that is not finite or <= 0, a pw_step that is not finite or < 0; nothing is written then. */
+int pfb_cluster_items_from_pdws(const pfb_pdw* pdws, uint64_t n, uint64_t stride_bytes, double freq0, double freq_step,
+                                double pw_step, pfb_cluster_item* items_out);
 
 #ifdef __cplusplus
 }

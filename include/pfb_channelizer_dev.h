@@ -87,6 +87,13 @@ int pfb_qfold_set_tier(pfb_qfold_handle* h, int tier, uint64_t step_cells);
  * what ran. */
 int pfb_assoc_set_tier(pfb_assoc_handle* h, int tier);
 
+/* Which kernel counts the cells in the next calls of a pfb_cluster handle: 0 = the library's choice
+ * (pfb_cluster_plan.histogram_kernel), 1 = pfb_cluster_hist_lds (PFB_ERR_UNSUPPORTED when U V is above
+ * pfb_cluster_plan.lds_cells), 2 = pfb_cluster_hist_global.  Both give the same bytes; the tests run one list through
+ * them, the meter (tools/cluster_rate.py) times them.  PFB_ERR_BAD_ARG for any other value.  pfb_cluster_last_kernel
+ * names what ran. */
+int pfb_cluster_set_tier(pfb_cluster_handle* h, int tier);
+
 /* The fused-kernel table, row by row in lookup order (host only, no device needed): what the tests walk, so that a
  * registered plan cannot go untested.  Rows of one (M, P, D, sample_format) are that shape's variants 0, 1, ... */
 typedef struct {

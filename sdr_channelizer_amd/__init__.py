@@ -10,6 +10,9 @@ from .associate import (ASSOC_ITEM_DTYPE, GROUP_DTYPE, PulseAssociator, associat
 from .cfar import (Cfar, cfar_alpha, detect, detect_pulses, detections_to_pdws,  # noqa: F401
                    pulse_detections_from_iq_file)
 from .channelizer import Channelizer, center_frequencies, design_prototype, pinned_empty  # noqa: F401
+from .cluster import (CLUSTER_GROUP_DTYPE, CLUSTER_ITEM_DTYPE, PulseClusterer, cluster_pdws, cluster_pulses,  # noqa: F401
+                      deinterleave_clustered, deinterleave_clustered_figures, describe_clusterer)
+from .cluster import items_from_pdws as cluster_items_from_pdws  # noqa: F401
 from .deinterleave import (EMITTER_DTYPE, Deinterleaver, deinterleave, deinterleave_detections,  # noqa: F401
                            deinterleave_pdws, describe_deinterleaver, merge_emitters, ticks_from_toa)
 from .event import DwellStats, EventPredictor, analyze_dwell, dwell_from_iq_file, fit_event, next_event  # noqa: F401
@@ -40,6 +43,8 @@ __all__ = ["Channelizer", "center_frequencies", "design_prototype", "pinned_empt
            "Trace", "Envelope", "envelope", "envelope_from_iq_file",
            "MatchedFilter", "compress", "compress_iq_file", "replica_from_pulse_train", "pulse_delay_from_iq_files",
            "Waterfall", "WaterfallImage", "waterfall", "waterfall_from_iq_file",
+           "PulseClusterer", "cluster_pulses", "cluster_pdws", "cluster_items_from_pdws", "describe_clusterer",
+           "deinterleave_clustered", "deinterleave_clustered_figures", "CLUSTER_ITEM_DTYPE", "CLUSTER_GROUP_DTYPE",
            "PulseAssociator", "associate", "associate_pdws", "fuse_pdws", "describe_associator", "ASSOC_ITEM_DTYPE",
            "GROUP_DTYPE",
            "ChannelSynthesizer", "synthesize", "design_synthesis_taps", "synthesis_delay", "isolate_band",

@@ -341,6 +341,36 @@ class PfbAssocStats(C.Structure):
                 ("linked_items", C.c_uint64), ("rounds", C.c_uint64)]
 
 
+class PfbClusterItem(C.Structure):
+    _fields_ = [("u", C.c_int32), ("v", C.c_int32)]
+
+
+class PfbClusterConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cells_u", C.c_uint32), ("cells_v", C.c_uint32), ("reach_u", C.c_uint32),
+                ("reach_v", C.c_uint32), ("min_cell_count", C.c_uint32), ("min_pulses", C.c_uint32),
+                ("flags", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class PfbClusterPlan(C.Structure):
+    _fields_ = [("scratch_bytes", C.c_uint64), ("cells", C.c_uint32), ("lds_cells", C.c_uint32),
+                ("hist_tile", C.c_uint32), ("label_tile", C.c_uint32), ("part_tile", C.c_uint32),
+                ("block_u", C.c_uint32), ("block_v", C.c_uint32), ("lds_bytes", C.c_uint32),
+                ("max_clusters", C.c_uint32), ("reserved", C.c_uint32), ("histogram_kernel", C.c_char * 32),
+                ("component_kernel", C.c_char * 32), ("partition_kernel", C.c_char * 32)]
+
+
+class PfbClusterGroup(C.Structure):
+    _fields_ = [("root_u", C.c_int32), ("root_v", C.c_int32), ("pulses", C.c_uint32), ("cells", C.c_uint32),
+                ("u_min", C.c_int32), ("u_max", C.c_int32), ("v_min", C.c_int32), ("v_max", C.c_int32),
+                ("sum_u", C.c_int64), ("sum_v", C.c_int64), ("peak_u", C.c_int32), ("peak_v", C.c_int32),
+                ("peak_count", C.c_uint32), ("first_item", C.c_uint32)]
+
+
+class PfbClusterStats(C.Structure):
+    _fields_ = [("outside", C.c_uint64), ("unassigned", C.c_uint64), ("dense_cells", C.c_uint64),
+                ("border_cells", C.c_uint64), ("components", C.c_uint64), ("hook_rounds", C.c_uint64)]
+
+
 class PfbMopConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample_format", C.c_uint32), ("bit_width", C.c_uint32),
                 ("trim_samples", C.c_uint32), ("max_negatives", C.c_uint32), ("device_id", C.c_int32)]
@@ -481,6 +511,9 @@ EXPORTS = (
     "pfb_fold_describe", "pfb_fold_counts", "pfb_fold_create", "pfb_fold_destroy", "pfb_fold_reset",
     "pfb_fold_set_stream", "pfb_fold_sync", "pfb_fold_get_device", "pfb_fold_next_index", "pfb_fold_process",
     "pfb_fold_process_async", "pfb_fold_scores", "pfb_fold_profile", "pfb_fold_last_kernel",
+    "pfb_cluster_describe", "pfb_cluster_create", "pfb_cluster_destroy", "pfb_cluster_set_stream", "pfb_cluster_sync",
+    "pfb_cluster_get_device", "pfb_cluster_run", "pfb_cluster_histogram", "pfb_cluster_cell_roots", "pfb_cluster_gather",
+    "pfb_cluster_last_kernel", "pfb_cluster_get_stats", "pfb_cluster_items_from_pdws",
     "pfb_qfold_describe", "pfb_qfold_counts", "pfb_qfold_create", "pfb_qfold_destroy", "pfb_qfold_reset",
     "pfb_qfold_set_index", "pfb_qfold_set_stream", "pfb_qfold_sync", "pfb_qfold_get_device", "pfb_qfold_next_index",
     "pfb_qfold_process", "pfb_qfold_process_async", "pfb_qfold_scores", "pfb_qfold_profile", "pfb_qfold_last_kernel",
@@ -505,7 +538,7 @@ EXPORTS = (
 # include/pfb_channelizer_dev.h: measurement yardsticks and the ABI self test (bench.py, tools/, tests/)
 DEV_EXPORTS = ("pfb_measure_stream_copy", "pfb_measure_mix_copy", "pfb_selftest_exception_guard", "pfb_stft_set_experiment",
                "pfb_fold_set_tier", "pfb_deint_set_tier", "pfb_mop_set_tier", "pfb_qfold_set_tier",
-               "pfb_assoc_set_tier",
+               "pfb_assoc_set_tier", "pfb_cluster_set_tier",
                "pfb_fast_plan_count", "pfb_fast_plan_info", "pfb_last_launch", "pfb_plan_launch", "pfb_last_entry", "pfb_plan_entry")
 
 _lib = None
@@ -844,6 +877,21 @@ def load() -> C.CDLL:
     lib.pfb_assoc_get_stats.argtypes = [vp, C.POINTER(PfbAssocStats)]
     lib.pfb_assoc_items_from_pdws.argtypes = [vp, u64, C.c_double, C.c_double, vp, vp]
     lib.pfb_assoc_set_tier.argtypes = [vp, C.c_int]
+    lib.pfb_cluster_describe.argtypes = [C.POINTER(PfbClusterConfig), u64, C.POINTER(PfbClusterPlan)]
+    lib.pfb_cluster_create.argtypes = [C.POINTER(PfbClusterConfig), C.POINTER(vp)]
+    lib.pfb_cluster_destroy.argtypes = [vp]
+    lib.pfb_cluster_set_stream.argtypes = [vp, vp]
+    lib.pfb_cluster_sync.argtypes = [vp]
+    lib.pfb_cluster_get_device.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.pfb_cluster_run.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp, vp, vp]
+    lib.pfb_cluster_histogram.argtypes = [vp, vp, u64, u32, vp, u64]
+    lib.pfb_cluster_cell_roots.argtypes = [vp, vp, u64, u32, vp, u64]
+    lib.pfb_cluster_gather.argtypes = [vp, vp, u32, vp, u64, vp]
+    lib.pfb_cluster_last_kernel.argtypes = [vp]
+    lib.pfb_cluster_last_kernel.restype = C.c_char_p
+    lib.pfb_cluster_get_stats.argtypes = [vp, C.POINTER(PfbClusterStats)]
+    lib.pfb_cluster_items_from_pdws.argtypes = [vp, u64, u64, C.c_double, C.c_double, C.c_double, vp]
+    lib.pfb_cluster_set_tier.argtypes = [vp, C.c_int]
     lib.pfb_fold_set_tier.argtypes = [vp, C.c_int]
     lib.pfb_qfold_set_tier.argtypes = [vp, C.c_int, u64]
     lib.pfb_mop_set_tier.argtypes = [vp, C.c_int, u32, u64]

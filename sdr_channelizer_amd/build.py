@@ -15,7 +15,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libpfb_channelizer.so")
-SOURCES = ["pfb_api.cpp", "pfb_stft_api.cpp", "pfb_host.cpp", "pfb_ols_host.cpp", "pfb_event.cpp", "pfb_kernels.hip", "pfb_kernels_mid.hip", "pfb_kernels_big.hip", "pfb_kernels_mixed.hip", "pfb_pdw.hip", "pfb_stft.hip", "pfb_synth.hip", "pfb_trace.hip", "pfb_mf.hip", "pfb_waterfall.hip", "pfb_chsyn.hip", "pfb_mfbank.hip", "pfb_cfar.hip", "pfb_pd.hip", "pfb_fold.hip", "pfb_rdcfar.hip", "pfb_oscfar.hip", "pfb_deint.hip", "pfb_mop.hip", "pfb_qfold.hip", "pfb_assoc.hip", "iq_packet.c"]
+SOURCES = ["pfb_api.cpp", "pfb_stft_api.cpp", "pfb_host.cpp", "pfb_ols_host.cpp", "pfb_event.cpp", "pfb_kernels.hip", "pfb_kernels_mid.hip", "pfb_kernels_big.hip", "pfb_kernels_mixed.hip", "pfb_pdw.hip", "pfb_stft.hip", "pfb_synth.hip", "pfb_trace.hip", "pfb_mf.hip", "pfb_waterfall.hip", "pfb_chsyn.hip", "pfb_mfbank.hip", "pfb_cfar.hip", "pfb_pd.hip", "pfb_fold.hip", "pfb_rdcfar.hip", "pfb_oscfar.hip", "pfb_deint.hip", "pfb_mop.hip", "pfb_qfold.hip", "pfb_assoc.hip", "pfb_cluster.hip", "iq_packet.c"]
 # every header under csrc/: one that a hand-kept list misses would let a stale library pass for current
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hpp")))
 ARCH = "gfx950"
