@@ -10,7 +10,7 @@
 //   assoc_hook        one lane per item that has links walks them again: where the labels of the two ends differ, an
 //                     atomicMin on the larger label's entry with the smaller.  Sets the round's flag when it hooked.
 //   assoc_jump        label[i] = label[label[i]], in place: a read gives the old or the new entry, both ancestors.
-//   assoc_count / assoc_scan / assoc_scatter   the groups' numbers: root flags (label[i] == i), a scan of the
+//   assoc_count / list_scan / assoc_scatter   the groups' numbers: root flags (label[i] == i), a scan of the
 //                     workgroups' counts, an ordered scatter that also clears the group's accumulators.
 //   assoc_gather      one lane per item: its group's number into the output labels, integer min / max / add into the
 //                     group's accumulators, one 64-bit max of (key << 32 | ~index) for the best member.
@@ -27,20 +27,15 @@
 #include <string>
 #include <vector>
 
-#include "pfb_common.h"
-#include "pfb_host.h"
+#include "pfb_list.hpp"
 
 namespace {
-
-using namespace pfb;
-using u64 = unsigned long long;
 
 constexpr uint32_t kMaxItems = 1u << 20, kMaxReach = 64, kMaxWindow = 4096;
 constexpr uint32_t kMaxSlack = 0x7fffffffu;
 constexpr uint32_t kLdsWindow = 1024;    // the LDS tier's bound
 constexpr uint32_t kTile = 256;          // items of one workgroup of the edge pass: one to a lane
 constexpr uint32_t kNumTile = 1024;      // items of one workgroup of the numbering: four to a lane
-constexpr int kThreads = 256;            // lanes of every workgroup here
 constexpr uint32_t kStaged = kTile + kLdsWindow + 4;  // entries the LDS tier stages at most (K + 1 behind the tile), in whole 16 bytes
 constexpr u64 kMaxTick = 1ull << 62;
 constexpr int kMaxRounds = 64;           // after which the host gives up
@@ -61,7 +56,7 @@ struct Arrays {             // the items as separate arrays, and what the passes
   int32_t* first;           // the lowest linked j, -1 for none
   int32_t* count;           // linked j
   int32_t* group;           // the output labels
-  uint32_t* counts;         // roots of every numbering workgroup, then (assoc_scan) those before it
+  uint32_t* counts;         // roots of every numbering workgroup, then (list_scan) those before it
   // per group, by its number
   uint32_t* root;
   u64* acc_end;
@@ -74,6 +69,7 @@ struct Arrays {             // the items as separate arrays, and what the passes
   Control* ctl;
   uint32_t n, K, Rc;
 };
+static_assert(sizeof(Control) == 296 && sizeof(Arrays) == 168, "the kernels' parameter layout");
 
 // the order of the floats, -0 under +0, as the order of unsigned integers
 __host__ __device__ __forceinline__ uint32_t weight_key(uint32_t bits) {
@@ -181,27 +177,6 @@ __global__ void __launch_bounds__(kThreads) assoc_jump(int32_t* label, uint32_t 
   if (q != p) label[i] = q;
 }
 
-// exclusive scan of one value per lane over the workgroup; *total: the sum
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wave_sum[kThreads / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();  // wave_sum of a call before is read
-  if (lane == 63) wave_sum[wv] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-  for (int k = 0; k < kThreads / 64; ++k) {
-    if (k < wv) before += wave_sum[k];
-    all += wave_sum[k];
-  }
-  *total = all;
-  return before + inc - v;
-}
-
 // a lane takes 4 consecutive items, a workgroup kNumTile; the labels are padded to a whole tile
 __device__ __forceinline__ void roots_of(const Arrays& a, uint32_t i0, bool root[4]) {
   const int4 l = *reinterpret_cast<const int4*>(a.label + i0);
@@ -217,24 +192,6 @@ __global__ void __launch_bounds__(kThreads) assoc_count(const Arrays a) {
   uint32_t total;
   (void)block_scan((uint32_t)root[0] + root[1] + root[2] + root[3], &total);
   if (threadIdx.x == 0) a.counts[blockIdx.x] = total;
-}
-
-// one workgroup: counts[0 .. blocks) become the counts before each, blocks <= 1024; the sum is the number of groups
-__global__ void __launch_bounds__(kThreads) assoc_scan(uint32_t* counts, uint32_t blocks, Control* ctl) {
-  uint32_t v[4], sum = 0;
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = threadIdx.x * 4 + k;
-    v[k] = i < blocks ? counts[i] : 0;
-    sum += v[k];
-  }
-  uint32_t total;
-  uint32_t at = block_scan(sum, &total);
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = threadIdx.x * 4 + k;
-    if (i < blocks) counts[i] = at;
-    at += v[k];
-  }
-  if (threadIdx.x == 0) ctl->groups = total;
 }
 
 __global__ void __launch_bounds__(kThreads) assoc_scatter(const Arrays a) {
@@ -304,48 +261,43 @@ __global__ void __launch_bounds__(kThreads) assoc_emit(const Arrays a, uint32_t 
 // ---------------------------------------------------------------------------------
 // host: checks and plan
 
-enum { kTierAuto = 0, kTierLds = 1, kTierGlobal = 2 };
-
 struct Settings {
   uint32_t Rc = 0, g = 0, K = 0;
 };
 
-constexpr size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+// the carving of a handle's scratch for lists of up to cap items, cap a multiple of kNumTile: every array once.
+// *items: where a host list is staged
+Arrays carve(Carver& c, size_t cap, pfb_assoc_item** items) {
+  Arrays a{};
+  *items = c.array<pfb_assoc_item>(cap);
+  a.start = c.array<u64>(cap);
+  a.lim = c.array<u64>(cap);
+  a.cell = c.array<int32_t>(cap);
+  a.length = c.array<uint32_t>(cap);
+  a.key = c.array<uint32_t>(cap);
+  a.label = c.array<int32_t>(cap);
+  a.first = c.array<int32_t>(cap);
+  a.count = c.array<int32_t>(cap);
+  a.group = c.array<int32_t>(cap);
+  a.counts = c.array<uint32_t>(kMaxItems / kNumTile);
+  a.root = c.array<uint32_t>(cap);
+  a.acc_end = c.array<u64>(cap);
+  a.acc_sum = c.array<u64>(cap);
+  a.acc_best = c.array<u64>(cap);
+  a.acc_members = c.array<uint32_t>(cap);
+  a.acc_lo = c.array<int32_t>(cap);
+  a.acc_hi = c.array<int32_t>(cap);
+  a.records = c.array<pfb_assoc_group>(cap);
+  a.ctl = c.array<Control>(1);
+  return a;
+}
 
-// the carving of a handle's scratch for lists of up to cap items, cap a multiple of kNumTile
-struct Layout {
-  size_t items, start, lim, cell, length, key, label, first, count, group, counts, root, acc_end, acc_sum, acc_best,
-      acc_members, acc_lo, acc_hi, records, ctl, bytes;
-  explicit Layout(size_t cap) {
-    size_t at = 0;
-    auto take = [&at](size_t b) {
-      const size_t here = at;
-      at += round_up(b, 256);
-      return here;
-    };
-    items = take(cap * sizeof(pfb_assoc_item));
-    start = take(cap * 8);
-    lim = take(cap * 8);
-    cell = take(cap * 4);
-    length = take(cap * 4);
-    key = take(cap * 4);
-    label = take(cap * 4);
-    first = take(cap * 4);
-    count = take(cap * 4);
-    group = take(cap * 4);
-    counts = take((kMaxItems / kNumTile) * 4);
-    root = take(cap * 4);
-    acc_end = take(cap * 8);
-    acc_sum = take(cap * 8);
-    acc_best = take(cap * 8);
-    acc_members = take(cap * 4);
-    acc_lo = take(cap * 4);
-    acc_hi = take(cap * 4);
-    records = take(cap * sizeof(pfb_assoc_group));
-    ctl = take(sizeof(Control));
-    bytes = at;
-  }
-};
+size_t scratch_bytes(size_t cap) {
+  Carver c;
+  pfb_assoc_item* items;
+  carve(c, cap, &items);
+  return c.bytes();
+}
 
 size_t capacity_for(uint64_t n) { return round_up(std::max<uint64_t>(n, 1), kNumTile); }
 
@@ -370,85 +322,33 @@ int assoc_check(const pfb_assoc_config* cfg, Settings* s) {
 
 }  // namespace
 
-struct pfb_assoc_handle {
-  int device = 0;
+struct pfb_assoc_handle : ListHandle {
   Settings s;
   int tier = kTierAuto;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_switch = nullptr;
-  char* d_scratch = nullptr;
-  size_t cap = 0;  // items the scratch is carved for
   pfb_assoc_stats stats{};
-  std::string last_kernel;
 };
 
 namespace {
 
 bool runs_lds(const pfb_assoc_handle* h) { return h->tier == kTierAuto ? h->s.K <= kLdsWindow : h->tier == kTierLds; }
 
-void free_assoc(pfb_assoc_handle* h) {
-  if (!h) return;
-  DeviceGuard g(h->device);
-  (void)hipFree(h->d_scratch);
-  if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
-  delete h;
-}
-
 // one call's view of the scratch
-struct Call {
+struct Call : ListCall {
   pfb_assoc_handle* h;
-  Layout lay;
-  Arrays a{};
-  std::string kernels;  // what it launched
-  explicit Call(pfb_assoc_handle* hh, uint32_t n) : h(hh), lay(hh->cap) {
-    a.start = at<u64>(lay.start);
-    a.lim = at<u64>(lay.lim);
-    a.cell = at<int32_t>(lay.cell);
-    a.length = at<uint32_t>(lay.length);
-    a.key = at<uint32_t>(lay.key);
-    a.label = at<int32_t>(lay.label);
-    a.first = at<int32_t>(lay.first);
-    a.count = at<int32_t>(lay.count);
-    a.group = at<int32_t>(lay.group);
-    a.counts = at<uint32_t>(lay.counts);
-    a.root = at<uint32_t>(lay.root);
-    a.acc_end = at<u64>(lay.acc_end);
-    a.acc_sum = at<u64>(lay.acc_sum);
-    a.acc_best = at<u64>(lay.acc_best);
-    a.acc_members = at<uint32_t>(lay.acc_members);
-    a.acc_lo = at<int32_t>(lay.acc_lo);
-    a.acc_hi = at<int32_t>(lay.acc_hi);
-    a.records = at<pfb_assoc_group>(lay.records);
-    a.ctl = at<Control>(lay.ctl);
+  pfb_assoc_item* items = nullptr;  // where a host list is staged
+  Arrays a;
+  Call(pfb_assoc_handle* hh, uint32_t n) : h(hh) {
+    Carver c{hh->d_scratch};
+    a = carve(c, hh->cap, &items);
     a.n = n;
     a.K = hh->s.K;
     a.Rc = hh->s.Rc;
   }
-  template <class T>
-  T* at(size_t off) const { return reinterpret_cast<T*>(h->d_scratch + off); }
-  void ran(const char* name) {
-    if (kernels.find(name) != std::string::npos) return;
-    if (!kernels.empty()) kernels += "+";
-    kernels += name;
-  }
 };
 
-int ensure_scratch(pfb_assoc_handle* h, uint64_t n) {
+int reserve(pfb_assoc_handle* h, uint64_t n) {
   const size_t cap = capacity_for(n);
-  if (cap > h->cap) {
-    (void)hipFree(h->d_scratch);
-    h->d_scratch = nullptr;
-    h->cap = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_scratch), Layout(cap).bytes));
-    h->cap = cap;
-  }
-  return PFB_OK;
-}
-
-int copy_control(Call& c, Control* out) {
-  HIP_TRY(hipMemcpyAsync(out, c.a.ctl, sizeof(Control), hipMemcpyDeviceToHost, c.h->stream));
-  HIP_TRY(hipStreamSynchronize(c.h->stream));
-  return PFB_OK;
+  return cap > h->cap ? h->ensure(cap, scratch_bytes(cap)) : PFB_OK;  // the size only when it grows
 }
 
 // The list onto the device, the first pass and the edge pass; PFB_ERR_BAD_ARG for a list the device refuses.  n > 0
@@ -457,9 +357,8 @@ int begin_call(Call& c, const pfb_assoc_item* items, uint32_t mem, Control* ctl)
   const uint32_t n = c.a.n;
   const u64* d_items = reinterpret_cast<const u64*>(items);
   if (mem == PFB_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(c.at<char>(c.lay.items), items, (size_t)n * sizeof(pfb_assoc_item), hipMemcpyHostToDevice,
-                           h->stream));
-    d_items = c.at<u64>(c.lay.items);
+    HIP_TRY(hipMemcpyAsync(c.items, items, (size_t)n * sizeof(pfb_assoc_item), hipMemcpyHostToDevice, h->stream));
+    d_items = reinterpret_cast<const u64*>(c.items);
   }
   // the padding of the labels is never a root: -1 is no index
   HIP_TRY(hipMemsetAsync(c.a.label, 0xff, h->cap * sizeof(int32_t), h->stream));
@@ -473,23 +372,9 @@ int begin_call(Call& c, const pfb_assoc_item* items, uint32_t mem, Control* ctl)
   HIP_TRY(hipGetLastError());
   c.ran("pfb_assoc_prep");
   c.ran(link_name(lds));
-  const int rc = copy_control(c, ctl);
+  const int rc = fetch(h->stream, c.a.ctl, ctl);
   if (rc != PFB_OK) return rc;
   return ctl->bad ? PFB_ERR_BAD_ARG : PFB_OK;
-}
-
-// what every call that takes a list checks before the device is touched
-int check_list(const pfb_assoc_handle* h, const pfb_assoc_item* items, uint64_t n, uint32_t mem) {
-  if (!h || mem > PFB_MEM_DEVICE || n > kMaxItems || (n > 0 && !items)) return PFB_ERR_BAD_ARG;
-  if (mem == PFB_MEM_DEVICE && reinterpret_cast<uintptr_t>(items) % 8) return PFB_ERR_BAD_ARG;
-  return PFB_OK;
-}
-
-int copy_out(pfb_assoc_handle* h, void* dst, const void* d_src, size_t bytes, uint32_t mem) {
-  if (!bytes) return PFB_OK;
-  HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, mem == PFB_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                         h->stream));
-  return PFB_OK;
 }
 
 int run(pfb_assoc_handle* h, const pfb_assoc_item* items, uint64_t n64, uint32_t mem, pfb_assoc_group* groups_out,
@@ -501,7 +386,7 @@ int run(pfb_assoc_handle* h, const pfb_assoc_item* items, uint64_t n64, uint32_t
     h->last_kernel.clear();
     return PFB_OK;
   }
-  int rc = ensure_scratch(h, n64);
+  int rc = reserve(h, n64);
   if (rc != PFB_OK) return rc;
   const uint32_t n = (uint32_t)n64;
   Call c(h, n);
@@ -511,42 +396,38 @@ int run(pfb_assoc_handle* h, const pfb_assoc_item* items, uint64_t n64, uint32_t
   const dim3 block(kThreads), grid((n + kThreads - 1) / kThreads);
   int passes = 1;  // ceil(log2 n) + 1: a chain of roots is shorter than n
   while ((1ull << (passes - 1)) < n) ++passes;
-  uint64_t rounds = 0;
+  int rounds = 0;
   if (ctl.edges > 0) {
-    for (;;) {
-      if (rounds == (uint64_t)kMaxRounds) return PFB_ERR_INTERNAL;
-      hipLaunchKernelGGL(assoc_hook, grid, block, 0, h->stream, c.a, (uint32_t)rounds);
+    rounds = hook_until_still(h->stream, c.a.ctl->hooked, kMaxRounds, [&](uint32_t round) -> int {
+      hipLaunchKernelGGL(assoc_hook, grid, block, 0, h->stream, c.a, round);
       for (int p = 0; p < passes; ++p) hipLaunchKernelGGL(assoc_jump, grid, block, 0, h->stream, c.a.label, n);
       HIP_TRY(hipGetLastError());
-      uint32_t hooked = 0;
-      HIP_TRY(hipMemcpyAsync(&hooked, &c.a.ctl->hooked[rounds], sizeof(hooked), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      ++rounds;
-      if (!hooked) break;
-    }
+      return PFB_OK;
+    });
+    if (rounds < 0) return rounds;
     c.ran("pfb_assoc_hook");
     c.ran("pfb_assoc_jump");
   }
   const unsigned blocks = (n + kNumTile - 1) / kNumTile;
   hipLaunchKernelGGL(assoc_count, dim3(blocks), block, 0, h->stream, c.a);
-  hipLaunchKernelGGL(assoc_scan, dim3(1), block, 0, h->stream, c.a.counts, blocks, c.a.ctl);
+  hipLaunchKernelGGL(list_scan<true>, dim3(1), block, 0, h->stream, c.a.counts, blocks, &c.a.ctl->groups);
   hipLaunchKernelGGL(assoc_scatter, dim3(blocks), block, 0, h->stream, c.a);
   HIP_TRY(hipGetLastError());
   c.ran("pfb_assoc_number");
-  rc = copy_control(c, &ctl);
+  rc = fetch(h->stream, c.a.ctl, &ctl);
   if (rc != PFB_OK) return rc;
   *count_out = ctl.groups;
   if (ctl.groups > capacity) return PFB_ERR_CAPACITY;
   // the numbers go to a scratch array when the caller's labels are host memory
-  int32_t* d_labels = mem == PFB_MEM_DEVICE ? labels_out : c.at<int32_t>(c.lay.first);
+  int32_t* d_labels = mem == PFB_MEM_DEVICE ? labels_out : c.a.first;
   hipLaunchKernelGGL(assoc_gather, grid, block, 0, h->stream, c.a, d_labels, (u64)h->s.g);
   hipLaunchKernelGGL(assoc_emit, dim3((ctl.groups + kThreads - 1) / kThreads), block, 0, h->stream, c.a, ctl.groups);
   HIP_TRY(hipGetLastError());
   c.ran("pfb_assoc_gather");
-  if (mem == PFB_MEM_HOST && (rc = copy_out(h, labels_out, d_labels, (size_t)n * sizeof(int32_t), mem)) != PFB_OK) return rc;
-  rc = copy_out(h, groups_out, c.a.records, (size_t)ctl.groups * sizeof(pfb_assoc_group), mem);
+  if (mem == PFB_MEM_HOST && (rc = copy_out(h->stream, labels_out, d_labels, (size_t)n * sizeof(int32_t), mem)) != PFB_OK) return rc;
+  rc = copy_out(h->stream, groups_out, c.a.records, (size_t)ctl.groups * sizeof(pfb_assoc_group), mem);
   if (rc != PFB_OK) return rc;
-  rc = copy_control(c, &ctl);
+  rc = fetch(h->stream, c.a.ctl, &ctl);
   if (rc != PFB_OK) return rc;
   pfb_assoc_stats stats{};
   stats.groups = ctl.groups;
@@ -569,7 +450,7 @@ extern "C" int pfb_assoc_describe(const pfb_assoc_config* cfg, uint64_t n, pfb_a
     if (rc != PFB_OK) return rc;
     if (n > kMaxItems) return PFB_ERR_BAD_ARG;
     pfb_assoc_plan plan{};
-    plan.scratch_bytes = Layout(capacity_for(n)).bytes;
+    plan.scratch_bytes = scratch_bytes(capacity_for(n));
     plan.tile_items = kTile;
     plan.lds_window = kLdsWindow;
     plan.lds_bytes = lds_bytes_for(s.K);
@@ -601,33 +482,25 @@ extern "C" int pfb_assoc_create(const pfb_assoc_config* cfg, pfb_assoc_handle** 
 
 extern "C" int pfb_assoc_destroy(pfb_assoc_handle* h) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    free_assoc(h);
-    return PFB_OK;
+    return destroy_list(h);
   });
 }
 
 extern "C" int pfb_assoc_set_stream(pfb_assoc_handle* h, void* hip_stream) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    return pfb::switch_stream(h->device, &h->stream, &h->ev_switch, static_cast<hipStream_t>(hip_stream));
+    return set_list_stream(h, hip_stream);
   });
 }
 
 extern "C" int pfb_assoc_sync(pfb_assoc_handle* h) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    DeviceGuard g(h->device);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PFB_OK;
+    return sync_list(h);
   });
 }
 
 extern "C" int pfb_assoc_get_device(const pfb_assoc_handle* h, int* device_id) {
   return pfb::abi_guard([&]() -> int {
-    if (!h || !device_id) return PFB_ERR_BAD_ARG;
-    *device_id = h->device;
-    return PFB_OK;
+    return list_device(h, device_id);
   });
 }
 
@@ -643,10 +516,10 @@ extern "C" int pfb_assoc_set_tier(pfb_assoc_handle* h, int tier) {
 extern "C" int pfb_assoc_run(pfb_assoc_handle* h, const pfb_assoc_item* items, uint64_t n, uint32_t mem,
                              pfb_assoc_group* groups_out, uint64_t capacity, uint64_t* count_out, int32_t* labels_out) {
   return pfb::abi_guard([&]() -> int {
-    const int rc = check_list(h, items, n, mem);
+    const int rc = check_list(h, items, n, kMaxItems, mem, 8);
     if (rc != PFB_OK) return rc;
     if (!count_out || (capacity > 0 && !groups_out) || (n > 0 && !labels_out)) return PFB_ERR_BAD_ARG;
-    if (mem == PFB_MEM_DEVICE && (reinterpret_cast<uintptr_t>(groups_out) % 8 || reinterpret_cast<uintptr_t>(labels_out) % 4))
+    if (mem == PFB_MEM_DEVICE && (misaligned(groups_out, 8) || misaligned(labels_out, 4)))
       return PFB_ERR_BAD_ARG;
     return run(h, items, n, mem, groups_out, capacity, count_out, labels_out);
   });
@@ -655,26 +528,26 @@ extern "C" int pfb_assoc_run(pfb_assoc_handle* h, const pfb_assoc_item* items, u
 extern "C" int pfb_assoc_links(pfb_assoc_handle* h, const pfb_assoc_item* items, uint64_t n, uint32_t mem,
                                int32_t* first_link_out, int32_t* link_count_out) {
   return pfb::abi_guard([&]() -> int {
-    int rc = check_list(h, items, n, mem);
+    int rc = check_list(h, items, n, kMaxItems, mem, 8);
     if (rc != PFB_OK) return rc;
     if (n > 0 && (!first_link_out || !link_count_out)) return PFB_ERR_BAD_ARG;
     if (mem == PFB_MEM_DEVICE &&
-        (reinterpret_cast<uintptr_t>(first_link_out) % 4 || reinterpret_cast<uintptr_t>(link_count_out) % 4))
+        (misaligned(first_link_out, 4) || misaligned(link_count_out, 4)))
       return PFB_ERR_BAD_ARG;
     if (n == 0) {
       h->last_kernel.clear();
       return PFB_OK;
     }
     DeviceGuard g(h->device);
-    rc = ensure_scratch(h, n);
+    rc = reserve(h, n);
     if (rc != PFB_OK) return rc;
     Call c(h, (uint32_t)n);
     Control ctl{};
     rc = begin_call(c, items, mem, &ctl);
     if (rc != PFB_OK) return rc;
     const size_t bytes = n * sizeof(int32_t);
-    if ((rc = copy_out(h, first_link_out, c.a.first, bytes, mem)) != PFB_OK) return rc;
-    if ((rc = copy_out(h, link_count_out, c.a.count, bytes, mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, first_link_out, c.a.first, bytes, mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, link_count_out, c.a.count, bytes, mem)) != PFB_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->last_kernel = c.kernels;
     return PFB_OK;
@@ -685,9 +558,7 @@ extern "C" const char* pfb_assoc_last_kernel(const pfb_assoc_handle* h) { return
 
 extern "C" int pfb_assoc_get_stats(const pfb_assoc_handle* h, pfb_assoc_stats* stats_out) {
   return pfb::abi_guard([&]() -> int {
-    if (!h || !stats_out) return PFB_ERR_BAD_ARG;
-    *stats_out = h->stats;
-    return PFB_OK;
+    return list_stats(h, stats_out);
   });
 }
 

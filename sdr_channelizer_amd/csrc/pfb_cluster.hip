@@ -10,7 +10,7 @@
 //   cluster_jump        label[g] = label[label[g]], in place: a read gives the old or the new entry, both ancestors.
 //   cluster_border      one lane per cell: the cell's root -- its label, or for a border cell the lowest label in its box.
 //   cluster_cells       one lane per cell: integer add / min / max into the root's slots, a 64-bit max of (H << 32 | ~g).
-//   cluster_count / cluster_scan / cluster_scatter   the clusters' numbers: flags (a root with pulses >= min_pulses), a
+//   cluster_count / list_scan / cluster_scatter   the clusters' numbers: flags (a root with pulses >= min_pulses), a
 //                       scan of the workgroups' counts, an ordered scatter that also clears the cluster's item sums.
 //   cluster_label       one lane per item: its cluster through the cell tables, wave-combined adds into sum_u / sum_v and
 //                       a min into first_item.
@@ -29,18 +29,13 @@
 #include <new>
 #include <string>
 
-#include "pfb_common.h"
-#include "pfb_host.h"
+#include "pfb_list.hpp"
 
 namespace {
-
-using namespace pfb;
-using u64 = unsigned long long;
 
 constexpr uint32_t kMaxItems = 1u << 20, kMaxCells = 1u << 20, kMaxReach = 8, kMaxClusters = 65535;
 constexpr uint32_t kMaxCount = 1u << 20;
 constexpr uint32_t kLdsCells = 8192;     // the LDS histogram's bound
-constexpr int kThreads = 256;            // lanes of every workgroup here
 constexpr uint32_t kHistTile = 4096;     // items of one histogram workgroup: 16 to a lane
 constexpr uint32_t kLabelTile = 256;     // items of one label workgroup: one to a lane
 constexpr uint32_t kPartTile = 1024;     // items of one partition workgroup: four steps of one to a lane
@@ -71,7 +66,7 @@ struct Arrays {             // all in the handle's scratch
   int32_t* c_vmin;
   int32_t* c_vmax;
   u64* c_peak;
-  uint32_t* counts;         // clusters of every numbering workgroup, then (cluster_scan) those before it
+  uint32_t* counts;         // clusters of every numbering workgroup, then (list_scan) those before it
   // per cluster, by its number
   uint32_t* root;
   u64* sum_u;
@@ -87,6 +82,7 @@ struct Arrays {             // all in the handle's scratch
   Control* ctl;
   uint32_t n, U, V, cells, ru, rv, minc, minp, border;
 };
+static_assert(sizeof(Control) == 304 && sizeof(Arrays) == 232, "the kernels' parameter layout");
 
 __device__ __forceinline__ u64 lanes_below() { return (1ull << (threadIdx.x & 63)) - 1; }
 
@@ -249,27 +245,6 @@ __global__ void __launch_bounds__(kThreads) cluster_cells(const Arrays a) {
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.ctl->components, (u64)__popcll(m));
 }
 
-// exclusive scan of one value per lane over the workgroup; *total: the sum
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wave_total[kThreads / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();  // wave_total of a call before is read
-  if (lane == 63) wave_total[wv] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-  for (int k = 0; k < kThreads / 64; ++k) {
-    if (k < wv) before += wave_total[k];
-    all += wave_total[k];
-  }
-  *total = all;
-  return before + inc - v;
-}
-
 // a lane takes 4 consecutive cells, a workgroup kNumTile; croot is padded with -1 to a whole tile
 __device__ __forceinline__ void clusters_of(const Arrays& a, uint32_t g0, bool is[4]) {
   const int4 r = *reinterpret_cast<const int4*>(a.croot + g0);
@@ -283,24 +258,6 @@ __global__ void __launch_bounds__(kThreads) cluster_count(const Arrays a) {
   uint32_t total;
   (void)block_scan((uint32_t)is[0] + is[1] + is[2] + is[3], &total);
   if (threadIdx.x == 0) a.counts[blockIdx.x] = total;
-}
-
-// one workgroup: counts[0 .. blocks) become the counts before each, blocks <= 1024; the sum is the number of clusters
-__global__ void __launch_bounds__(kThreads) cluster_scan(uint32_t* counts, uint32_t blocks, Control* ctl) {
-  uint32_t v[4], sum = 0;
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = threadIdx.x * 4 + k;
-    v[k] = i < blocks ? counts[i] : 0;
-    sum += v[k];
-  }
-  uint32_t total;
-  uint32_t at = block_scan(sum, &total);
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = threadIdx.x * 4 + k;
-    if (i < blocks) counts[i] = at;
-    at += v[k];
-  }
-  if (threadIdx.x == 0) ctl->groups = total;
 }
 
 __global__ void __launch_bounds__(kThreads) cluster_scatter(const Arrays a) {
@@ -498,57 +455,52 @@ __global__ void __launch_bounds__(kThreads) cluster_gather(const T* src, const u
 // ---------------------------------------------------------------------------------
 // host: checks and plan
 
-enum { kTierAuto = 0, kTierLds = 1, kTierGlobal = 2 };
-
 struct Settings {
   uint32_t U = 0, V = 0, cells = 0, ru = 0, rv = 0, minc = 0, minp = 0, border = 0;
   uint32_t bu = 0, bv = 0;  // the component kernels' block
 };
 
-constexpr size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+size_t cells_padded(size_t cells) { return round_up(cells, kNumTile); }
 
-// the carving of a handle's scratch for lists of up to cap items (a multiple of kPartTile) on a grid of `cells`
-struct Layout {
-  size_t items, H, label, next, croot, cnum, c_pulses, c_cells, c_umin, c_umax, c_vmin, c_vmax, c_peak, counts, root, sum_u,
-      sum_v, first, records, labels, order_a, order_b, table, offsets, ctl, bytes;
-  size_t cells_padded;
-  Layout(size_t cap, size_t cells) {
-    size_t at = 0;
-    auto take = [&at](size_t b) {
-      const size_t here = at;
-      at += round_up(b, 256);
-      return here;
-    };
-    cells_padded = round_up(cells, kNumTile);
-    const size_t slots = std::min<size_t>(cells, kSlots);
-    items = take(cap * sizeof(pfb_cluster_item));
-    H = take(cells * 4);
-    label = take(cells_padded * 4);
-    next = take(cells_padded * 4);
-    croot = take(cells_padded * 4);
-    cnum = take(cells * 4);
-    c_pulses = take(cells * 4);
-    c_cells = take(cells * 4);
-    c_umin = take(cells * 4);
-    c_umax = take(cells * 4);
-    c_vmin = take(cells * 4);
-    c_vmax = take(cells * 4);
-    c_peak = take(cells * 8);
-    counts = take((kMaxCells / kNumTile) * 4);
-    root = take(slots * 4);
-    sum_u = take(slots * 8);
-    sum_v = take(slots * 8);
-    first = take(slots * 4);
-    records = take(slots * sizeof(pfb_cluster_group));
-    labels = take(cap * 4);
-    order_a = take(cap * 4);
-    order_b = take(cap * 4);
-    table = take((size_t)kDigits * (cap / kPartTile) * 4);
-    offsets = take((kSlots + 2) * 4);
-    ctl = take(sizeof(Control));
-    bytes = at;
-  }
-};
+// the carving of a handle's scratch for lists of up to cap items (a multiple of kPartTile) on a grid of `cells`: every
+// array once.  *items: where a host list is staged
+Arrays carve(Carver& c, size_t cap, size_t cells, pfb_cluster_item** items) {
+  const size_t padded = cells_padded(cells), slots = std::min<size_t>(cells, kSlots);
+  Arrays a{};
+  *items = c.array<pfb_cluster_item>(cap);
+  a.H = c.array<uint32_t>(cells);
+  a.label = c.array<int32_t>(padded);
+  a.next = c.array<int32_t>(padded);
+  a.croot = c.array<int32_t>(padded);
+  a.cnum = c.array<int32_t>(cells);
+  a.c_pulses = c.array<uint32_t>(cells);
+  a.c_cells = c.array<uint32_t>(cells);
+  a.c_umin = c.array<int32_t>(cells);
+  a.c_umax = c.array<int32_t>(cells);
+  a.c_vmin = c.array<int32_t>(cells);
+  a.c_vmax = c.array<int32_t>(cells);
+  a.c_peak = c.array<u64>(cells);
+  a.counts = c.array<uint32_t>(kMaxCells / kNumTile);
+  a.root = c.array<uint32_t>(slots);
+  a.sum_u = c.array<u64>(slots);
+  a.sum_v = c.array<u64>(slots);
+  a.first = c.array<uint32_t>(slots);
+  a.records = c.array<pfb_cluster_group>(slots);
+  a.labels = c.array<int32_t>(cap);
+  a.order_a = c.array<uint32_t>(cap);
+  a.order_b = c.array<uint32_t>(cap);
+  a.table = c.array<uint32_t>((size_t)kDigits * (cap / kPartTile));
+  a.offsets = c.array<uint32_t>(kSlots + 2);
+  a.ctl = c.array<Control>(1);
+  return a;
+}
+
+size_t scratch_bytes(size_t cap, size_t cells) {
+  Carver c;
+  pfb_cluster_item* items;
+  carve(c, cap, cells, &items);
+  return c.bytes();
+}
 
 size_t capacity_for(uint64_t n) { return round_up(std::max<uint64_t>(n, 1), kPartTile); }
 
@@ -579,16 +531,10 @@ int cluster_check(const pfb_cluster_config* cfg, Settings* s) {
 
 }  // namespace
 
-struct pfb_cluster_handle {
-  int device = 0;
+struct pfb_cluster_handle : ListHandle {
   Settings s;
   int tier = kTierAuto;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_switch = nullptr;
-  char* d_scratch = nullptr;
-  size_t cap = 0;  // items the scratch is carved for
   pfb_cluster_stats stats{};
-  std::string last_kernel;
 };
 
 namespace {
@@ -597,48 +543,17 @@ bool runs_lds(const pfb_cluster_handle* h) {
   return h->tier == kTierAuto ? h->s.cells <= kLdsCells : h->tier == kTierLds;
 }
 
-void free_cluster(pfb_cluster_handle* h) {
-  if (!h) return;
-  DeviceGuard g(h->device);
-  (void)hipFree(h->d_scratch);
-  if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
-  delete h;
-}
-
 unsigned blocks_for(uint32_t n, uint32_t per) { return (n + per - 1) / per; }
 
 // one call's view of the scratch
-struct Call {
+struct Call : ListCall {
   pfb_cluster_handle* h;
-  Layout lay;
-  Arrays a{};
+  pfb_cluster_item* staged = nullptr;  // where a host list is staged
+  Arrays a;
   const int2* d_items = nullptr;
-  std::string kernels;  // what it launched
-  Call(pfb_cluster_handle* hh, uint32_t n) : h(hh), lay(hh->cap, hh->s.cells) {
-    a.H = at<uint32_t>(lay.H);
-    a.label = at<int32_t>(lay.label);
-    a.next = at<int32_t>(lay.next);
-    a.croot = at<int32_t>(lay.croot);
-    a.cnum = at<int32_t>(lay.cnum);
-    a.c_pulses = at<uint32_t>(lay.c_pulses);
-    a.c_cells = at<uint32_t>(lay.c_cells);
-    a.c_umin = at<int32_t>(lay.c_umin);
-    a.c_umax = at<int32_t>(lay.c_umax);
-    a.c_vmin = at<int32_t>(lay.c_vmin);
-    a.c_vmax = at<int32_t>(lay.c_vmax);
-    a.c_peak = at<u64>(lay.c_peak);
-    a.counts = at<uint32_t>(lay.counts);
-    a.root = at<uint32_t>(lay.root);
-    a.sum_u = at<u64>(lay.sum_u);
-    a.sum_v = at<u64>(lay.sum_v);
-    a.first = at<uint32_t>(lay.first);
-    a.records = at<pfb_cluster_group>(lay.records);
-    a.labels = at<int32_t>(lay.labels);
-    a.order_a = at<uint32_t>(lay.order_a);
-    a.order_b = at<uint32_t>(lay.order_b);
-    a.table = at<uint32_t>(lay.table);
-    a.offsets = at<uint32_t>(lay.offsets);
-    a.ctl = at<Control>(lay.ctl);
+  Call(pfb_cluster_handle* hh, uint32_t n) : h(hh) {
+    Carver c{hh->d_scratch};
+    a = carve(c, hh->cap, hh->s.cells, &staged);
     a.n = n;
     a.U = hh->s.U;
     a.V = hh->s.V;
@@ -649,31 +564,11 @@ struct Call {
     a.minp = hh->s.minp;
     a.border = hh->s.border;
   }
-  template <class T>
-  T* at(size_t off) const { return reinterpret_cast<T*>(h->d_scratch + off); }
-  void ran(const char* name) {
-    if (kernels.find(name) != std::string::npos) return;
-    if (!kernels.empty()) kernels += "+";
-    kernels += name;
-  }
 };
 
-int ensure_scratch(pfb_cluster_handle* h, uint64_t n) {
+int reserve(pfb_cluster_handle* h, uint64_t n) {
   const size_t cap = capacity_for(n);
-  if (cap > h->cap) {
-    (void)hipFree(h->d_scratch);
-    h->d_scratch = nullptr;
-    h->cap = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_scratch), Layout(cap, h->s.cells).bytes));
-    h->cap = cap;
-  }
-  return PFB_OK;
-}
-
-int copy_control(Call& c, Control* out) {
-  HIP_TRY(hipMemcpyAsync(out, c.a.ctl, sizeof(Control), hipMemcpyDeviceToHost, c.h->stream));
-  HIP_TRY(hipStreamSynchronize(c.h->stream));
-  return PFB_OK;
+  return cap > h->cap ? h->ensure(cap, scratch_bytes(cap, h->s.cells)) : PFB_OK;  // the size only when it grows
 }
 
 // step 1: the list onto the device and the histogram
@@ -682,9 +577,8 @@ int histogram(Call& c, const pfb_cluster_item* items, uint32_t mem) {
   const uint32_t n = c.a.n;
   c.d_items = reinterpret_cast<const int2*>(items);
   if (mem == PFB_MEM_HOST && n > 0) {
-    HIP_TRY(hipMemcpyAsync(c.at<char>(c.lay.items), items, (size_t)n * sizeof(pfb_cluster_item), hipMemcpyHostToDevice,
-                           h->stream));
-    c.d_items = c.at<int2>(c.lay.items);
+    HIP_TRY(hipMemcpyAsync(c.staged, items, (size_t)n * sizeof(pfb_cluster_item), hipMemcpyHostToDevice, h->stream));
+    c.d_items = reinterpret_cast<const int2*>(c.staged);
   }
   HIP_TRY(hipMemsetAsync(c.a.H, 0, (size_t)c.a.cells * 4, h->stream));
   HIP_TRY(hipMemsetAsync(c.a.ctl, 0, sizeof(Control), h->stream));
@@ -705,32 +599,28 @@ int components(Call& c, Control* ctl, uint64_t* rounds) {
   const uint32_t cells = c.a.cells;
   const dim3 block(kThreads), grid(blocks_for(cells, kThreads));
   // the padding of the labels and roots is never a root: -1 is no cell
-  HIP_TRY(hipMemsetAsync(c.a.label, 0xff, c.lay.cells_padded * 4, h->stream));
-  HIP_TRY(hipMemsetAsync(c.a.croot, 0xff, c.lay.cells_padded * 4, h->stream));
+  HIP_TRY(hipMemsetAsync(c.a.label, 0xff, cells_padded(cells) * 4, h->stream));
+  HIP_TRY(hipMemsetAsync(c.a.croot, 0xff, cells_padded(cells) * 4, h->stream));
   hipLaunchKernelGGL(cluster_init, grid, block, 0, h->stream, c.a);
   HIP_TRY(hipGetLastError());
   c.ran("pfb_cluster_init");
-  int rc = copy_control(c, ctl);
+  int rc = fetch(h->stream, c.a.ctl, ctl);
   if (rc != PFB_OK) return rc;
   *rounds = 0;
   if (ctl->dense > 0) {
     int passes = 1;  // ceil(log2 cells) + 1: a chain of roots is shorter than the cells
     while ((1ull << (passes - 1)) < cells) ++passes;
     const uint32_t blocks_u = blocks_for(h->s.U, h->s.bu), blocks_v = blocks_for(h->s.V, h->s.bv);
-    for (;;) {
-      if (*rounds == (uint64_t)kMaxRounds) return PFB_ERR_INTERNAL;
+    rc = hook_until_still(h->stream, c.a.ctl->hooked, kMaxRounds, [&](uint32_t round) -> int {
       HIP_TRY(hipMemcpyAsync(c.a.next, c.a.label, (size_t)cells * 4, hipMemcpyDeviceToDevice, h->stream));
-      hipLaunchKernelGGL(cluster_hook, dim3(blocks_u * blocks_v), block, 0, h->stream, c.a, h->s.bu, h->s.bv, blocks_v,
-                         (uint32_t)*rounds);
+      hipLaunchKernelGGL(cluster_hook, dim3(blocks_u * blocks_v), block, 0, h->stream, c.a, h->s.bu, h->s.bv, blocks_v, round);
       for (int p = 0; p < passes; ++p) hipLaunchKernelGGL(cluster_jump, grid, block, 0, h->stream, c.a.next, cells);
       HIP_TRY(hipGetLastError());
       std::swap(c.a.label, c.a.next);
-      uint32_t hooked = 0;
-      HIP_TRY(hipMemcpyAsync(&hooked, &c.a.ctl->hooked[*rounds], sizeof(hooked), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      ++*rounds;
-      if (!hooked) break;
-    }
+      return PFB_OK;
+    });
+    if (rc < 0) return rc;
+    *rounds = (uint64_t)rc;
     c.ran("pfb_cluster_hook");
     c.ran("pfb_cluster_jump");
   }
@@ -740,25 +630,10 @@ int components(Call& c, Control* ctl, uint64_t* rounds) {
   return PFB_OK;
 }
 
-// what every call that takes a list checks before the device is touched
-int check_list(const pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n, uint32_t mem) {
-  if (!h || mem > PFB_MEM_DEVICE || n > kMaxItems || (n > 0 && !items)) return PFB_ERR_BAD_ARG;
-  return PFB_OK;
-}
-
-bool misaligned(const void* p, uintptr_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
-int copy_out(pfb_cluster_handle* h, void* dst, const void* d_src, size_t bytes, uint32_t mem) {
-  if (!bytes) return PFB_OK;
-  HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, mem == PFB_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                         h->stream));
-  return PFB_OK;
-}
-
 int run(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n64, uint32_t mem, pfb_cluster_group* groups_out,
         uint64_t capacity, uint64_t* count_out, int32_t* labels_out, uint32_t* order_out, uint32_t* offsets_out) {
   DeviceGuard g(h->device);
-  int rc = ensure_scratch(h, n64);
+  int rc = reserve(h, n64);
   if (rc != PFB_OK) return rc;
   const uint32_t n = (uint32_t)n64, cells = h->s.cells;
   Call c(h, n);
@@ -770,12 +645,12 @@ int run(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n64, uint
   hipLaunchKernelGGL(cluster_cells, dim3(blocks_for(cells, kThreads)), block, 0, h->stream, c.a);
   const unsigned blocks = blocks_for(cells, kNumTile);
   hipLaunchKernelGGL(cluster_count, dim3(blocks), block, 0, h->stream, c.a);
-  hipLaunchKernelGGL(cluster_scan, dim3(1), block, 0, h->stream, c.a.counts, blocks, c.a.ctl);
+  hipLaunchKernelGGL(list_scan<true>, dim3(1), block, 0, h->stream, c.a.counts, blocks, &c.a.ctl->groups);
   hipLaunchKernelGGL(cluster_scatter, dim3(blocks), block, 0, h->stream, c.a);
   HIP_TRY(hipGetLastError());
   c.ran("pfb_cluster_cells");
   c.ran("pfb_cluster_number");
-  if ((rc = copy_control(c, &ctl)) != PFB_OK) return rc;
+  if ((rc = fetch(h->stream, c.a.ctl, &ctl)) != PFB_OK) return rc;
   const uint32_t G = ctl.groups;
   *count_out = G;
   if (G > capacity || G > kMaxClusters) return PFB_ERR_CAPACITY;
@@ -785,18 +660,18 @@ int run(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n64, uint
     hipLaunchKernelGGL(cluster_label, dim3(blocks_for(n, kLabelTile)), block, 0, h->stream, c.d_items, c.a, d_labels);
     HIP_TRY(hipGetLastError());
     c.ran("pfb_cluster_label");
-    if (mem == PFB_MEM_HOST && (rc = copy_out(h, labels_out, d_labels, (size_t)n * 4, mem)) != PFB_OK) return rc;
+    if (mem == PFB_MEM_HOST && (rc = copy_out(h->stream, labels_out, d_labels, (size_t)n * 4, mem)) != PFB_OK) return rc;
   }
   if (G > 0) {
     hipLaunchKernelGGL(cluster_emit, dim3(blocks_for(G, kThreads)), block, 0, h->stream, c.a, G);
     HIP_TRY(hipGetLastError());
     c.ran("pfb_cluster_emit");
-    if ((rc = copy_out(h, groups_out, c.a.records, (size_t)G * sizeof(pfb_cluster_group), mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, groups_out, c.a.records, (size_t)G * sizeof(pfb_cluster_group), mem)) != PFB_OK) return rc;
   }
   if (order_out) {
     hipLaunchKernelGGL(cluster_offsets, dim3(1), block, 0, h->stream, c.a, G);
     HIP_TRY(hipGetLastError());
-    if ((rc = copy_out(h, offsets_out, c.a.offsets, (size_t)(G + 2) * 4, mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, offsets_out, c.a.offsets, (size_t)(G + 2) * 4, mem)) != PFB_OK) return rc;
     if (n > 0) {
       const uint32_t tiles = blocks_for(n, kPartTile);
       const bool two = G + 1 > kDigits;
@@ -814,10 +689,10 @@ int run(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n64, uint
         src = dst;
       }
       c.ran(two ? "pfb_cluster_part2" : "pfb_cluster_part1");
-      if (mem == PFB_MEM_HOST && (rc = copy_out(h, order_out, d_order, (size_t)n * 4, mem)) != PFB_OK) return rc;
+      if (mem == PFB_MEM_HOST && (rc = copy_out(h->stream, order_out, d_order, (size_t)n * 4, mem)) != PFB_OK) return rc;
     }
   }
-  if ((rc = copy_control(c, &ctl)) != PFB_OK) return rc;
+  if ((rc = fetch(h->stream, c.a.ctl, &ctl)) != PFB_OK) return rc;
   pfb_cluster_stats stats{};
   stats.outside = ctl.outside;
   stats.unassigned = ctl.unassigned;
@@ -839,7 +714,7 @@ extern "C" int pfb_cluster_describe(const pfb_cluster_config* cfg, uint64_t n, p
     if (rc != PFB_OK) return rc;
     if (n > kMaxItems) return PFB_ERR_BAD_ARG;
     pfb_cluster_plan plan{};
-    plan.scratch_bytes = Layout(capacity_for(n), s.cells).bytes;
+    plan.scratch_bytes = scratch_bytes(capacity_for(n), s.cells);
     plan.cells = s.cells;
     plan.lds_cells = kLdsCells;
     plan.hist_tile = kHistTile;
@@ -877,33 +752,25 @@ extern "C" int pfb_cluster_create(const pfb_cluster_config* cfg, pfb_cluster_han
 
 extern "C" int pfb_cluster_destroy(pfb_cluster_handle* h) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    free_cluster(h);
-    return PFB_OK;
+    return destroy_list(h);
   });
 }
 
 extern "C" int pfb_cluster_set_stream(pfb_cluster_handle* h, void* hip_stream) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    return pfb::switch_stream(h->device, &h->stream, &h->ev_switch, static_cast<hipStream_t>(hip_stream));
+    return set_list_stream(h, hip_stream);
   });
 }
 
 extern "C" int pfb_cluster_sync(pfb_cluster_handle* h) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    DeviceGuard g(h->device);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PFB_OK;
+    return sync_list(h);
   });
 }
 
 extern "C" int pfb_cluster_get_device(const pfb_cluster_handle* h, int* device_id) {
   return pfb::abi_guard([&]() -> int {
-    if (!h || !device_id) return PFB_ERR_BAD_ARG;
-    *device_id = h->device;
-    return PFB_OK;
+    return list_device(h, device_id);
   });
 }
 
@@ -920,12 +787,12 @@ extern "C" int pfb_cluster_run(pfb_cluster_handle* h, const pfb_cluster_item* it
                                pfb_cluster_group* groups_out, uint64_t capacity, uint64_t* count_out, int32_t* labels_out,
                                uint32_t* order_out, uint32_t* offsets_out) {
   return pfb::abi_guard([&]() -> int {
-    const int rc = check_list(h, items, n, mem);
+    const int rc = check_list(h, items, n, kMaxItems, mem, 8);
     if (rc != PFB_OK) return rc;
     if (!count_out || (capacity > 0 && !groups_out) || (n > 0 && !labels_out)) return PFB_ERR_BAD_ARG;
     if (!order_out != !offsets_out) return PFB_ERR_BAD_ARG;
-    if (mem == PFB_MEM_DEVICE && (misaligned(items, 8) || misaligned(groups_out, 8) || misaligned(labels_out, 4) ||
-                                  misaligned(order_out, 4) || misaligned(offsets_out, 4)))
+    if (mem == PFB_MEM_DEVICE && (misaligned(groups_out, 8) || misaligned(labels_out, 4) || misaligned(order_out, 4) ||
+                                  misaligned(offsets_out, 4)))
       return PFB_ERR_BAD_ARG;
     return run(h, items, n, mem, groups_out, capacity, count_out, labels_out, order_out, offsets_out);
   });
@@ -934,16 +801,16 @@ extern "C" int pfb_cluster_run(pfb_cluster_handle* h, const pfb_cluster_item* it
 extern "C" int pfb_cluster_histogram(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n, uint32_t mem,
                                      uint32_t* counts_out, uint64_t capacity_cells) {
   return pfb::abi_guard([&]() -> int {
-    int rc = check_list(h, items, n, mem);
+    int rc = check_list(h, items, n, kMaxItems, mem, 8);
     if (rc != PFB_OK) return rc;
     if (!counts_out) return PFB_ERR_BAD_ARG;
-    if (mem == PFB_MEM_DEVICE && (misaligned(items, 8) || misaligned(counts_out, 4))) return PFB_ERR_BAD_ARG;
+    if (mem == PFB_MEM_DEVICE && misaligned(counts_out, 4)) return PFB_ERR_BAD_ARG;
     if (capacity_cells < h->s.cells) return PFB_ERR_CAPACITY;
     DeviceGuard g(h->device);
-    if ((rc = ensure_scratch(h, n)) != PFB_OK) return rc;
+    if ((rc = reserve(h, n)) != PFB_OK) return rc;
     Call c(h, (uint32_t)n);
     if ((rc = histogram(c, items, mem)) != PFB_OK) return rc;
-    if ((rc = copy_out(h, counts_out, c.a.H, (size_t)h->s.cells * 4, mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, counts_out, c.a.H, (size_t)h->s.cells * 4, mem)) != PFB_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->last_kernel = c.kernels;
     return PFB_OK;
@@ -953,19 +820,19 @@ extern "C" int pfb_cluster_histogram(pfb_cluster_handle* h, const pfb_cluster_it
 extern "C" int pfb_cluster_cell_roots(pfb_cluster_handle* h, const pfb_cluster_item* items, uint64_t n, uint32_t mem,
                                       int32_t* roots_out, uint64_t capacity_cells) {
   return pfb::abi_guard([&]() -> int {
-    int rc = check_list(h, items, n, mem);
+    int rc = check_list(h, items, n, kMaxItems, mem, 8);
     if (rc != PFB_OK) return rc;
     if (!roots_out) return PFB_ERR_BAD_ARG;
-    if (mem == PFB_MEM_DEVICE && (misaligned(items, 8) || misaligned(roots_out, 4))) return PFB_ERR_BAD_ARG;
+    if (mem == PFB_MEM_DEVICE && misaligned(roots_out, 4)) return PFB_ERR_BAD_ARG;
     if (capacity_cells < h->s.cells) return PFB_ERR_CAPACITY;
     DeviceGuard g(h->device);
-    if ((rc = ensure_scratch(h, n)) != PFB_OK) return rc;
+    if ((rc = reserve(h, n)) != PFB_OK) return rc;
     Call c(h, (uint32_t)n);
     Control ctl{};
     uint64_t rounds = 0;
     if ((rc = histogram(c, items, mem)) != PFB_OK) return rc;
     if ((rc = components(c, &ctl, &rounds)) != PFB_OK) return rc;
-    if ((rc = copy_out(h, roots_out, c.a.croot, (size_t)h->s.cells * 4, mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, roots_out, c.a.croot, (size_t)h->s.cells * 4, mem)) != PFB_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->last_kernel = c.kernels;
     return PFB_OK;
@@ -997,9 +864,7 @@ extern "C" const char* pfb_cluster_last_kernel(const pfb_cluster_handle* h) { re
 
 extern "C" int pfb_cluster_get_stats(const pfb_cluster_handle* h, pfb_cluster_stats* stats_out) {
   return pfb::abi_guard([&]() -> int {
-    if (!h || !stats_out) return PFB_ERR_BAD_ARG;
-    *stats_out = h->stats;
-    return PFB_OK;
+    return list_stats(h, stats_out);
   });
 }
 

@@ -1,6 +1,6 @@
 // pfb_deint.hip -- PDW deinterleaver (pfb_deint_* in include/pfb_channelizer.h, where every figure is defined): emitters
 // from a time-ordered list of arrival ticks, kernels and host side.
-//   deint_count / deint_scan / deint_scatter   the alive list of a round: flags (label == -1), a scan of the workgroups'
+//   deint_count / list_scan / deint_scatter   the alive list of a round: flags (label == -1), a scan of the workgroups'
 //                     counts, an ordered scatter of (tick, original index).  The first round's count pass also checks
 //                     the list's order and the ticks' bound.
 //   deint_hist<LDS>   a workgroup stages tiles of 1024 consecutive alive ticks plus Lv more in LDS (16-byte loads) and
@@ -32,18 +32,13 @@
 #include <string>
 #include <vector>
 
-#include "pfb_common.h"
-#include "pfb_host.h"
+#include "pfb_list.hpp"
 
 namespace {
-
-using namespace pfb;
-using u64 = unsigned long long;
 
 constexpr uint32_t kMaxPulses = 1u << 20, kMaxBins = 1u << 16, kMaxLevel = 256;
 constexpr uint32_t kLdsBins = 8192;      // the LDS tier's bound
 constexpr uint32_t kTile = 1024;         // alive pulses of one histogram tile, and of one compaction workgroup
-constexpr int kThreads = 256;            // lanes of every workgroup here
 constexpr unsigned kHistGrid = 1024;     // workgroups of the histogram at most: four to a CU
 constexpr u64 kMaxTick = 1ull << 62;
 constexpr int kMaxRounds = 20;           // doubling rounds for 2^20 pulses
@@ -56,37 +51,18 @@ struct Control {            // what a round hands back to the host
   u64 first_tick, last_tick;
   uint32_t b, hops, per, first_pulse;
 };
+static_assert(sizeof(Control) == 64, "deint_scatter, deint_argmax and deint_pick write it by these offsets");
 
 struct CompactParams {
   const u64* t;             // the caller's list
   const int32_t* labels;    // -1: alive
-  uint32_t* counts;         // alive pulses of every workgroup, then (deint_scan) those before it
+  uint32_t* counts;         // alive pulses of every workgroup, then (list_scan) those before it
   u64* a;                   // the alive ticks ...
   uint32_t* idx;            // ... and their indices in the caller's list
   Control* ctl;
   uint32_t n, alive, check;
 };
-
-// exclusive scan of one value per lane over the workgroup; *total: the sum
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wave_sum[kThreads / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();  // wave_sum of a call before is read
-  if (lane == 63) wave_sum[wv] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-  for (int k = 0; k < kThreads / 64; ++k) {
-    if (k < wv) before += wave_sum[k];
-    all += wave_sum[k];
-  }
-  *total = all;
-  return before + inc - v;
-}
+static_assert(sizeof(CompactParams) == 64, "the kernels' parameter layout");
 
 // a lane takes 4 consecutive pulses, a workgroup kTile
 __device__ __forceinline__ void alive_of(const CompactParams& p, uint32_t i0, bool live[4]) {
@@ -116,23 +92,6 @@ __global__ void __launch_bounds__(kThreads) deint_count(const CompactParams p) {
   if (threadIdx.x == 0) p.counts[blockIdx.x] = total;
 }
 
-// one workgroup: counts[0 .. blocks) become the counts before each, blocks <= 1024
-__global__ void __launch_bounds__(kThreads) deint_scan(uint32_t* counts, uint32_t blocks) {
-  uint32_t v[4], sum = 0;
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = threadIdx.x * 4 + k;
-    v[k] = i < blocks ? counts[i] : 0;
-    sum += v[k];
-  }
-  uint32_t total;
-  uint32_t at = block_scan(sum, &total);
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = threadIdx.x * 4 + k;
-    if (i < blocks) counts[i] = at;
-    at += v[k];
-  }
-}
-
 __global__ void __launch_bounds__(kThreads) deint_scatter(const CompactParams p) {
   const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * 4;
   bool live[4];
@@ -157,6 +116,7 @@ struct HistParams {
   uint32_t pmin, W, NB, Lv;
   u64 pmax;
 };
+static_assert(sizeof(HistParams) == 48, "the kernels' parameter layout");
 
 template <bool LDS>
 __global__ void __launch_bounds__(kThreads) deint_hist(const HistParams p) {
@@ -229,6 +189,7 @@ struct SuccParams {
   u64 tau, e;
   uint32_t n, X;
 };
+static_assert(sizeof(SuccParams) == 56, "the kernels' parameter layout");
 
 __global__ void __launch_bounds__(kThreads) deint_succ(const SuccParams p) {
   const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
@@ -328,40 +289,51 @@ __global__ void __launch_bounds__(kThreads) deint_lengths(const int4* table, int
 // ---------------------------------------------------------------------------------
 // host: checks and plan
 
-enum { kHistAuto = 0, kHistLds = 1, kHistGlobal = 2, kMarkAuto = 0, kMarkWalk = 1, kMarkTables = 2 };
+enum { kMarkAuto = 0, kMarkWalk = 1, kMarkTables = 2 };  // the histogram's tiers are kTier*
 
 struct Settings {
   uint32_t pmin = 0, W = 0, NB = 0, Lv = 0, detect = 0, min_pulses = 0, X = 0, fill = 0, max_emitters = 0;
   u64 pmax = 0, e = 0;
 };
 
-constexpr size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
-
-// the carving of a handle's scratch for lists of up to cap pulses, cap a multiple of kTile
-struct Layout {
-  size_t t, labels, a, idx, succ, step, len, table0, table1, counts, hist, ctl, bytes;
-  Layout(size_t cap, uint32_t NB) {
-    size_t at = 0;
-    auto take = [&at](size_t b) {
-      const size_t here = at;
-      at += round_up(b, 256);
-      return here;
-    };
-    t = take(cap * 8);
-    labels = take(cap * 4);
-    a = take(cap * 8);
-    idx = take(cap * 4);
-    succ = take(cap * 4);
-    step = take(cap * 4);
-    len = take(cap * 4);
-    table0 = take(cap * 16);
-    table1 = take(cap * 16);
-    counts = take((kMaxPulses / kTile) * 4);
-    hist = take((size_t)NB * 4);
-    ctl = take(sizeof(Control));
-    bytes = at;
-  }
+struct Arrays {             // a handle's scratch
+  u64* t;                   // a host list on its way in
+  int32_t* labels;          // -1: alive; padded to a whole kTile
+  u64* a;                   // the alive ticks ...
+  uint32_t* idx;            // ... and their indices in the caller's list
+  int32_t* succ;
+  int32_t* step;
+  int32_t* len;
+  int4* table0;             // the doubling goes from one table into the other
+  int4* table1;
+  uint32_t* counts;         // alive pulses of every compaction workgroup
+  uint32_t* hist;           // NB counts
+  Control* ctl;
 };
+
+// the carving of a handle's scratch for lists of up to cap pulses, cap a multiple of kTile: every array once
+Arrays carve(Carver& c, size_t cap, uint32_t NB) {
+  Arrays s{};
+  s.t = c.array<u64>(cap);
+  s.labels = c.array<int32_t>(cap);
+  s.a = c.array<u64>(cap);
+  s.idx = c.array<uint32_t>(cap);
+  s.succ = c.array<int32_t>(cap);
+  s.step = c.array<int32_t>(cap);
+  s.len = c.array<int32_t>(cap);
+  s.table0 = c.array<int4>(cap);
+  s.table1 = c.array<int4>(cap);
+  s.counts = c.array<uint32_t>(kMaxPulses / kTile);
+  s.hist = c.array<uint32_t>(NB);
+  s.ctl = c.array<Control>(1);
+  return s;
+}
+
+size_t scratch_bytes(size_t cap, uint32_t NB) {
+  Carver c;
+  carve(c, cap, NB);
+  return c.bytes();
+}
 
 size_t capacity_for(uint64_t n) { return round_up(std::max<uint64_t>(n, 1), kTile); }
 // the jump tables of every doubling round, kept for the marking pass of pfb_deint_run
@@ -402,63 +374,43 @@ int deint_check(const pfb_deint_config* cfg, Settings* s) {
 
 }  // namespace
 
-struct pfb_deint_handle {
-  int device = 0;
+struct pfb_deint_handle : ListHandle {
   Settings s;
-  int hist_tier = kHistAuto, mark_tier = kMarkAuto;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_switch = nullptr;
-  char* d_scratch = nullptr;
-  size_t cap = 0;               // pulses the scratch is carved for
+  int hist_tier = kTierAuto, mark_tier = kMarkAuto;
   int32_t* d_levels = nullptr;  // the marking tables: kMaxRounds x level_cap jumps
   size_t level_cap = 0;
   pfb_deint_stats stats{};
-  std::string last_kernel;
   std::vector<uint32_t> hist;   // a round's histogram on the host
+  void release() {
+    DeviceGuard g(device);
+    (void)hipFree(d_levels);
+    ListHandle::release();
+  }
 };
 
 namespace {
 
-bool runs_lds(const pfb_deint_handle* h) { return h->hist_tier == kHistAuto ? h->s.NB <= kLdsBins : h->hist_tier == kHistLds; }
+bool runs_lds(const pfb_deint_handle* h) { return h->hist_tier == kTierAuto ? h->s.NB <= kLdsBins : h->hist_tier == kTierLds; }
 // the kept tables wherever they were measured, which is everywhere; kMarkWalk is for tests and meter
 bool runs_tables(const pfb_deint_handle* h) { return h->mark_tier != kMarkWalk; }
 
-void free_deint(pfb_deint_handle* h) {
-  if (!h) return;
-  DeviceGuard g(h->device);
-  (void)hipFree(h->d_scratch);
-  (void)hipFree(h->d_levels);
-  if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
-  delete h;
-}
-
 // one call's view of the scratch
-struct Call {
+struct Call : ListCall {
   pfb_deint_handle* h;
-  Layout lay;
+  Arrays scr;
   const u64* d_t = nullptr;  // the list on the device
   uint32_t n = 0;
-  std::string kernels;       // what it launched
-  Call(pfb_deint_handle* hh) : h(hh), lay(hh->cap, hh->s.NB) {}
-  template <class T>
-  T* at(size_t off) const { return reinterpret_cast<T*>(h->d_scratch + off); }
-  Control* ctl() const { return at<Control>(lay.ctl); }
-  void ran(const char* name) {
-    if (kernels.find(name) != std::string::npos) return;
-    if (!kernels.empty()) kernels += "+";
-    kernels += name;
+  Call(pfb_deint_handle* hh) : h(hh) {
+    Carver c{hh->d_scratch};
+    scr = carve(c, hh->cap, hh->s.NB);
   }
 };
 
-int ensure_scratch(pfb_deint_handle* h, uint64_t n, bool levels = false) {
+// the scratch for a list of n pulses; levels: the marking tables too
+int reserve(pfb_deint_handle* h, uint64_t n, bool levels = false) {
   const size_t cap = capacity_for(n);
-  if (cap > h->cap) {
-    (void)hipFree(h->d_scratch);
-    h->d_scratch = nullptr;
-    h->cap = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_scratch), Layout(cap, h->s.NB).bytes));
-    h->cap = cap;
-  }
+  const int rc = cap > h->cap ? h->ensure(cap, scratch_bytes(cap, h->s.NB)) : PFB_OK;  // the size only when it grows
+  if (rc != PFB_OK) return rc;
   if (levels && runs_tables(h) && h->level_cap < h->cap) {
     (void)hipFree(h->d_levels);
     h->d_levels = nullptr;
@@ -469,27 +421,21 @@ int ensure_scratch(pfb_deint_handle* h, uint64_t n, bool levels = false) {
   return PFB_OK;
 }
 
-int copy_control(Call& c, Control* out) {
-  HIP_TRY(hipMemcpyAsync(out, c.ctl(), sizeof(Control), hipMemcpyDeviceToHost, c.h->stream));
-  HIP_TRY(hipStreamSynchronize(c.h->stream));
-  return PFB_OK;
-}
-
 // the alive list of a round: `alive` pulses have label -1.  check: the first round, which also reads the list's order
 int compact(Call& c, uint32_t alive, bool check) {
   CompactParams p{};
   p.t = c.d_t;
-  p.labels = c.at<int32_t>(c.lay.labels);
-  p.counts = c.at<uint32_t>(c.lay.counts);
-  p.a = c.at<u64>(c.lay.a);
-  p.idx = c.at<uint32_t>(c.lay.idx);
-  p.ctl = c.ctl();
+  p.labels = c.scr.labels;
+  p.counts = c.scr.counts;
+  p.a = c.scr.a;
+  p.idx = c.scr.idx;
+  p.ctl = c.scr.ctl;
   p.n = c.n;
   p.alive = alive;
   p.check = check ? 1u : 0u;
   const unsigned blocks = (c.n + kTile - 1) / kTile;
   hipLaunchKernelGGL(deint_count, dim3(blocks), dim3(kThreads), 0, c.h->stream, p);
-  hipLaunchKernelGGL(deint_scan, dim3(1), dim3(kThreads), 0, c.h->stream, p.counts, blocks);
+  hipLaunchKernelGGL(list_scan<false>, dim3(1), dim3(kThreads), 0, c.h->stream, p.counts, blocks, (uint32_t*)nullptr);
   hipLaunchKernelGGL(deint_scatter, dim3(blocks), dim3(kThreads), 0, c.h->stream, p);
   HIP_TRY(hipGetLastError());
   c.ran("pfb_deint_compact");
@@ -501,16 +447,16 @@ int begin_call(Call& c, const uint64_t* ticks, uint64_t n, uint32_t mem, Control
   pfb_deint_handle* h = c.h;
   c.n = (uint32_t)n;
   if (mem == PFB_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(c.at<u64>(c.lay.t), ticks, n * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    c.d_t = c.at<u64>(c.lay.t);
+    HIP_TRY(hipMemcpyAsync(c.scr.t, ticks, n * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    c.d_t = c.scr.t;
   } else {
     c.d_t = reinterpret_cast<const u64*>(ticks);
   }
-  HIP_TRY(hipMemsetAsync(c.at<int32_t>(c.lay.labels), 0xff, h->cap * sizeof(int32_t), h->stream));
-  HIP_TRY(hipMemsetAsync(c.ctl(), 0, sizeof(Control), h->stream));
+  HIP_TRY(hipMemsetAsync(c.scr.labels, 0xff, h->cap * sizeof(int32_t), h->stream));
+  HIP_TRY(hipMemsetAsync(c.scr.ctl, 0, sizeof(Control), h->stream));
   int rc = compact(c, c.n, true);
   if (rc != PFB_OK) return rc;
-  rc = copy_control(c, ctl);
+  rc = fetch(c.h->stream, c.scr.ctl, ctl);
   if (rc != PFB_OK) return rc;
   return ctl->bad ? PFB_ERR_BAD_ARG : PFB_OK;
 }
@@ -518,8 +464,8 @@ int begin_call(Call& c, const uint64_t* ticks, uint64_t n, uint32_t mem, Control
 int histogram(Call& c, uint32_t alive) {
   pfb_deint_handle* h = c.h;
   HistParams p{};
-  p.a = c.at<u64>(c.lay.a);
-  p.C = c.at<uint32_t>(c.lay.hist);
+  p.a = c.scr.a;
+  p.C = c.scr.hist;
   p.n = alive;
   p.tiles = (alive + kTile - 1) / kTile;
   p.pmin = h->s.pmin;
@@ -542,10 +488,10 @@ int histogram(Call& c, uint32_t alive) {
 int chains(Call& c, uint32_t alive, u64 tau, u64 span, bool keep, const int4** table_out, int* rounds_out) {
   pfb_deint_handle* h = c.h;
   SuccParams p{};
-  p.a = c.at<u64>(c.lay.a);
-  p.succ = c.at<int32_t>(c.lay.succ);
-  p.step = c.at<int32_t>(c.lay.step);
-  p.table = c.at<int4>(c.lay.table0);
+  p.a = c.scr.a;
+  p.succ = c.scr.succ;
+  p.step = c.scr.step;
+  p.table = c.scr.table0;
   p.tau = tau;
   p.e = h->s.e;
   p.n = alive;
@@ -556,8 +502,8 @@ int chains(Call& c, uint32_t alive, u64 tau, u64 span, bool keep, const int4** t
   const u64 most = std::min<u64>(alive - 1, span / (tau - h->s.e));
   int rounds = 0;
   while ((1ull << rounds) < most) ++rounds;
-  int4* in = c.at<int4>(c.lay.table0);
-  int4* out = c.at<int4>(c.lay.table1);
+  int4* in = c.scr.table0;
+  int4* out = c.scr.table1;
   for (int r = 0; r < rounds; ++r) {
     hipLaunchKernelGGL(deint_double, grid, block, 0, h->stream, in, out, keep ? h->d_levels + (size_t)r * h->level_cap : nullptr,
                        alive);
@@ -568,20 +514,6 @@ int chains(Call& c, uint32_t alive, u64 tau, u64 span, bool keep, const int4** t
   if (rounds) c.ran("pfb_deint_double");
   *table_out = in;
   *rounds_out = rounds;
-  return PFB_OK;
-}
-
-// what every call that takes a list checks before the device is touched
-int check_list(const pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem) {
-  if (!h || mem > PFB_MEM_DEVICE || n > kMaxPulses || (n > 0 && !ticks)) return PFB_ERR_BAD_ARG;
-  if (mem == PFB_MEM_DEVICE && reinterpret_cast<uintptr_t>(ticks) % 8) return PFB_ERR_BAD_ARG;
-  return PFB_OK;
-}
-
-int copy_out(pfb_deint_handle* h, void* dst, const void* d_src, size_t bytes, uint32_t mem) {
-  if (!bytes) return PFB_OK;
-  HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, mem == PFB_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                         h->stream));
   return PFB_OK;
 }
 
@@ -603,7 +535,7 @@ int run(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, pf
     h->last_kernel.clear();
     return PFB_OK;
   }
-  int rc = ensure_scratch(h, n, true);
+  int rc = reserve(h, n, true);
   if (rc != PFB_OK) return rc;
   Call c(h);
   Control ctl{};
@@ -618,9 +550,8 @@ int run(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, pf
     }
     rc = histogram(c, alive);
     if (rc != PFB_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(h->hist.data(), c.at<uint32_t>(c.lay.hist), (size_t)s.NB * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, h->stream));
-    rc = copy_control(c, &ctl);
+    HIP_TRY(hipMemcpyAsync(h->hist.data(), c.scr.hist, (size_t)s.NB * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    rc = fetch(c.h->stream, c.scr.ctl, &ctl);
     if (rc != PFB_OK) return rc;
     ++stats.rounds;
     const u64 span = ctl.last - ctl.first;
@@ -636,14 +567,13 @@ int run(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, pf
       int rounds = 0;
       rc = chains(c, alive, tau, span, runs_tables(h), &table, &rounds);
       if (rc != PFB_OK) return rc;
-      HIP_TRY(hipMemsetAsync(&c.ctl()->best, 0, sizeof(u64), h->stream));
+      HIP_TRY(hipMemsetAsync(&c.scr.ctl->best, 0, sizeof(u64), h->stream));
       hipLaunchKernelGGL(deint_argmax, dim3(std::min((alive + kThreads - 1) / kThreads, 1024u)), dim3(kThreads), 0, h->stream,
-                         table, alive, c.ctl());
-      hipLaunchKernelGGL(deint_pick, dim3(1), dim3(1), 0, h->stream, table, c.at<u64>(c.lay.a), c.at<uint32_t>(c.lay.idx),
-                         c.ctl());
+                         table, alive, c.scr.ctl);
+      hipLaunchKernelGGL(deint_pick, dim3(1), dim3(1), 0, h->stream, table, c.scr.a, c.scr.idx, c.scr.ctl);
       HIP_TRY(hipGetLastError());
       c.ran("pfb_deint_argmax");
-      rc = copy_control(c, &ctl);
+      rc = fetch(c.h->stream, c.scr.ctl, &ctl);
       if (rc != PFB_OK) return rc;
       const u64 len = (u64)ctl.hops + 1;
       if (len < s.min_pulses || 100 * (len - 1) < (u64)s.fill * ctl.per) {
@@ -651,14 +581,13 @@ int run(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, pf
         continue;
       }
       const int32_t E = (int32_t)found.size();
-      int32_t* labels = c.at<int32_t>(c.lay.labels);
+      int32_t* labels = c.scr.labels;
       if (runs_tables(h))
         hipLaunchKernelGGL(deint_mark_tables, dim3((unsigned)((len + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream,
-                           h->d_levels, (uint32_t)h->level_cap, rounds, table, c.at<uint32_t>(c.lay.idx), labels, ctl.b,
+                           h->d_levels, (uint32_t)h->level_cap, rounds, table, c.scr.idx, labels, ctl.b,
                            ctl.hops, E);
       else
-        hipLaunchKernelGGL(deint_mark_walk, dim3(1), dim3(1), 0, h->stream, c.at<int32_t>(c.lay.succ),
-                           c.at<uint32_t>(c.lay.idx), labels, ctl.b, E);
+        hipLaunchKernelGGL(deint_mark_walk, dim3(1), dim3(1), 0, h->stream, c.scr.succ, c.scr.idx, labels, ctl.b, E);
       HIP_TRY(hipGetLastError());
       c.ran(mark_name(runs_tables(h)));
       pfb_deint_emitter rec{};
@@ -690,7 +619,7 @@ int run(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, pf
     else
       std::memcpy(emitters_out, found.data(), found.size() * sizeof(pfb_deint_emitter));
   }
-  rc = copy_out(h, labels_out, c.at<int32_t>(c.lay.labels), n * sizeof(int32_t), mem);
+  rc = copy_out(h->stream, labels_out, c.scr.labels, n * sizeof(int32_t), mem);
   if (rc != PFB_OK) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->stats = stats;
@@ -707,7 +636,7 @@ extern "C" int pfb_deint_describe(const pfb_deint_config* cfg, uint64_t n, pfb_d
     if (rc != PFB_OK) return rc;
     if (n > kMaxPulses) return PFB_ERR_BAD_ARG;
     pfb_deint_plan plan{};
-    plan.scratch_bytes = Layout(capacity_for(n), s.NB).bytes + level_bytes(capacity_for(n));
+    plan.scratch_bytes = scratch_bytes(capacity_for(n), s.NB) + level_bytes(capacity_for(n));
     plan.num_bins = s.NB;
     plan.lds_bins = kLdsBins;
     plan.tile_pulses = kTile;
@@ -742,41 +671,33 @@ extern "C" int pfb_deint_create(const pfb_deint_config* cfg, pfb_deint_handle** 
 
 extern "C" int pfb_deint_destroy(pfb_deint_handle* h) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    free_deint(h);
-    return PFB_OK;
+    return destroy_list(h);
   });
 }
 
 extern "C" int pfb_deint_set_stream(pfb_deint_handle* h, void* hip_stream) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    return pfb::switch_stream(h->device, &h->stream, &h->ev_switch, static_cast<hipStream_t>(hip_stream));
+    return set_list_stream(h, hip_stream);
   });
 }
 
 extern "C" int pfb_deint_sync(pfb_deint_handle* h) {
   return pfb::abi_guard([&]() -> int {
-    if (!h) return PFB_ERR_BAD_ARG;
-    DeviceGuard g(h->device);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return PFB_OK;
+    return sync_list(h);
   });
 }
 
 extern "C" int pfb_deint_get_device(const pfb_deint_handle* h, int* device_id) {
   return pfb::abi_guard([&]() -> int {
-    if (!h || !device_id) return PFB_ERR_BAD_ARG;
-    *device_id = h->device;
-    return PFB_OK;
+    return list_device(h, device_id);
   });
 }
 
 extern "C" int pfb_deint_set_tier(pfb_deint_handle* h, int histogram_tier, int marking_tier) {
   return pfb::abi_guard([&]() -> int {
-    if (!h || histogram_tier < kHistAuto || histogram_tier > kHistGlobal) return PFB_ERR_BAD_ARG;
+    if (!h || histogram_tier < kTierAuto || histogram_tier > kTierGlobal) return PFB_ERR_BAD_ARG;
     if (marking_tier < kMarkAuto || marking_tier > kMarkTables) return PFB_ERR_BAD_ARG;
-    if (histogram_tier == kHistLds && h->s.NB > kLdsBins) return PFB_ERR_UNSUPPORTED;
+    if (histogram_tier == kTierLds && h->s.NB > kLdsBins) return PFB_ERR_UNSUPPORTED;
     h->hist_tier = histogram_tier;
     h->mark_tier = marking_tier;
     return PFB_OK;
@@ -786,11 +707,10 @@ extern "C" int pfb_deint_set_tier(pfb_deint_handle* h, int histogram_tier, int m
 extern "C" int pfb_deint_run(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem,
                              pfb_deint_emitter* emitters_out, uint64_t capacity, uint64_t* count_out, int32_t* labels_out) {
   return pfb::abi_guard([&]() -> int {
-    const int rc = check_list(h, ticks, n, mem);
+    const int rc = check_list(h, ticks, n, kMaxPulses, mem, 8);
     if (rc != PFB_OK) return rc;
     if (!count_out || (capacity > 0 && !emitters_out) || (n > 0 && !labels_out)) return PFB_ERR_BAD_ARG;
-    if (mem == PFB_MEM_DEVICE && (reinterpret_cast<uintptr_t>(emitters_out) % 8 || reinterpret_cast<uintptr_t>(labels_out) % 4))
-      return PFB_ERR_BAD_ARG;
+    if (mem == PFB_MEM_DEVICE && (misaligned(emitters_out, 8) || misaligned(labels_out, 4))) return PFB_ERR_BAD_ARG;
     return run(h, ticks, n, mem, emitters_out, capacity, count_out, labels_out);
   });
 }
@@ -798,12 +718,12 @@ extern "C" int pfb_deint_run(pfb_deint_handle* h, const uint64_t* ticks, uint64_
 extern "C" int pfb_deint_histogram(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem,
                                    uint32_t* counts_out, uint64_t capacity_bins) {
   return pfb::abi_guard([&]() -> int {
-    int rc = check_list(h, ticks, n, mem);
+    int rc = check_list(h, ticks, n, kMaxPulses, mem, 8);
     if (rc != PFB_OK) return rc;
-    if (!counts_out || (mem == PFB_MEM_DEVICE && reinterpret_cast<uintptr_t>(counts_out) % 4)) return PFB_ERR_BAD_ARG;
+    if (!counts_out || (mem == PFB_MEM_DEVICE && misaligned(counts_out, 4))) return PFB_ERR_BAD_ARG;
     if (capacity_bins < h->s.NB) return PFB_ERR_CAPACITY;
     DeviceGuard g(h->device);
-    rc = ensure_scratch(h, n);
+    rc = reserve(h, n);
     if (rc != PFB_OK) return rc;
     Call c(h);
     if (n > 0) {
@@ -813,7 +733,7 @@ extern "C" int pfb_deint_histogram(pfb_deint_handle* h, const uint64_t* ticks, u
     }
     rc = histogram(c, (uint32_t)n);
     if (rc != PFB_OK) return rc;
-    rc = copy_out(h, counts_out, c.at<uint32_t>(c.lay.hist), (size_t)h->s.NB * sizeof(uint32_t), mem);
+    rc = copy_out(h->stream, counts_out, c.scr.hist, (size_t)h->s.NB * sizeof(uint32_t), mem);
     if (rc != PFB_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->last_kernel = c.kernels;
@@ -824,11 +744,10 @@ extern "C" int pfb_deint_histogram(pfb_deint_handle* h, const uint64_t* ticks, u
 extern "C" int pfb_deint_successors(pfb_deint_handle* h, const uint64_t* ticks, uint64_t n, uint32_t mem, uint64_t period,
                                     int32_t* succ_out, int32_t* step_out, int32_t* len_out) {
   return pfb::abi_guard([&]() -> int {
-    int rc = check_list(h, ticks, n, mem);
+    int rc = check_list(h, ticks, n, kMaxPulses, mem, 8);
     if (rc != PFB_OK) return rc;
     if (n > 0 && (!succ_out || !step_out || !len_out)) return PFB_ERR_BAD_ARG;
-    if (mem == PFB_MEM_DEVICE && (reinterpret_cast<uintptr_t>(succ_out) % 4 || reinterpret_cast<uintptr_t>(step_out) % 4 ||
-                                  reinterpret_cast<uintptr_t>(len_out) % 4))
+    if (mem == PFB_MEM_DEVICE && (misaligned(succ_out, 4) || misaligned(step_out, 4) || misaligned(len_out, 4)))
       return PFB_ERR_BAD_ARG;
     if (period < 1 || period > 0xffffffffull || h->s.e * (2 * (uint64_t)h->s.X + 3) >= period) return PFB_ERR_BAD_ARG;
     if (n == 0) {
@@ -836,7 +755,7 @@ extern "C" int pfb_deint_successors(pfb_deint_handle* h, const uint64_t* ticks, 
       return PFB_OK;
     }
     DeviceGuard g(h->device);
-    rc = ensure_scratch(h, n);
+    rc = reserve(h, n);
     if (rc != PFB_OK) return rc;
     Call c(h);
     Control ctl{};
@@ -846,13 +765,13 @@ extern "C" int pfb_deint_successors(pfb_deint_handle* h, const uint64_t* ticks, 
     int rounds = 0;
     rc = chains(c, (uint32_t)n, period, ctl.last - ctl.first, false, &table, &rounds);
     if (rc != PFB_OK) return rc;
-    hipLaunchKernelGGL(deint_lengths, dim3(((unsigned)n + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, table,
-                       c.at<int32_t>(c.lay.len), (uint32_t)n);
+    hipLaunchKernelGGL(deint_lengths, dim3(((unsigned)n + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream,
+                       table, c.scr.len, (uint32_t)n);
     HIP_TRY(hipGetLastError());
     const size_t bytes = n * sizeof(int32_t);
-    if ((rc = copy_out(h, succ_out, c.at<int32_t>(c.lay.succ), bytes, mem)) != PFB_OK) return rc;
-    if ((rc = copy_out(h, step_out, c.at<int32_t>(c.lay.step), bytes, mem)) != PFB_OK) return rc;
-    if ((rc = copy_out(h, len_out, c.at<int32_t>(c.lay.len), bytes, mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, succ_out, c.scr.succ, bytes, mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, step_out, c.scr.step, bytes, mem)) != PFB_OK) return rc;
+    if ((rc = copy_out(h->stream, len_out, c.scr.len, bytes, mem)) != PFB_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->last_kernel = c.kernels;
     return PFB_OK;
@@ -863,9 +782,7 @@ extern "C" const char* pfb_deint_last_kernel(const pfb_deint_handle* h) { return
 
 extern "C" int pfb_deint_get_stats(const pfb_deint_handle* h, pfb_deint_stats* stats_out) {
   return pfb::abi_guard([&]() -> int {
-    if (!h || !stats_out) return PFB_ERR_BAD_ARG;
-    *stats_out = h->stats;
-    return PFB_OK;
+    return list_stats(h, stats_out);
   });
 }
 

@@ -1,7 +1,8 @@
 // pfb_host.h -- host-only plumbing of every unit that has a host side (pfb_api.cpp, pfb_stft_api.cpp, pfb_event.cpp and
 // the .hip units with entry points of their own; defined in pfb_host.cpp): HIP error mapping, device selection, stream
-// switch, twiddle upload, the staged host-pointer pipeline and the .iq record reader.  What only the matched filter and
-// its bank share is in pfb_ols_host.h.
+// switch, twiddle upload, the carving of a scratch block, the staged host-pointer pipeline and the .iq record reader.
+// What only the matched filter and its bank share is in pfb_ols_host.h, the two map detectors in pfb_rdmap.hpp, the
+// three list units (deinterleaver, associator, clusterer) in pfb_list.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,6 +53,22 @@ int grow(void** p, size_t* have, size_t want);
 
 // workgroups for `items` at `per_block` each: one at least, `cap` at most (the kernels stride)
 unsigned grid_for(uint64_t items, unsigned per_block, unsigned cap);
+
+constexpr size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+
+// A scratch block cut into typed arrays of whole 256-byte pieces, in the order they are asked for.  Without a base it
+// only measures: every array is null then, and bytes() is what the block must hold.
+struct Carver {
+  char* base = nullptr;
+  size_t at = 0;
+  template <class T>
+  T* array(size_t count) {
+    const size_t here = at;
+    at += round_up(count * sizeof(T), 256);
+    return base ? reinterpret_cast<T*>(base + here) : nullptr;
+  }
+  size_t bytes() const { return at; }
+};
 
 // tw[m] = e^{+j 2 pi m / n}, m = 0..n-1 (from float64), into a new device array
 hipError_t upload_twiddles(uint32_t n, float2** d_tw);

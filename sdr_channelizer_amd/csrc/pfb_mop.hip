@@ -421,28 +421,30 @@ __global__ void __launch_bounds__(kThreads) mop_join(const MopParams p) {
 // ---------------------------------------------------------------------------------
 // host: checks and plan
 
-constexpr size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
-
 // the carving of a handle's scratch: fixed, for slices of kSlice pulses
-struct Layout {
-  size_t work, glist, slist, ctl, partial, part_negs, pulses, rec, negs, bytes;
-  explicit Layout(uint32_t maxneg) {
-    size_t at = 0;
-    auto take = [&at](size_t b) {
-      const size_t here = at;
-      at += round_up(b, 256);
-      return here;
-    };
-    work = take((size_t)kSlice * sizeof(Work));
-    glist = take((size_t)kSlice * 4);
-    slist = take((size_t)kSlice * 4);
-    ctl = take(8);
-    partial = take((size_t)kSlots * kMaxParts * sizeof(Acc<double>));
-    part_negs = take((size_t)kSlots * kMaxParts * maxneg * 4);
-    pulses = take((size_t)kSlice * sizeof(pfb_mop_pulse));  // a host list's slice, its records and negatives
-    rec = take((size_t)kSlice * sizeof(pfb_mop_record));
-    negs = take((size_t)kSlice * maxneg * 4);
-    bytes = at;
+struct Scratch {
+  Work* work;
+  uint32_t* glist;
+  uint32_t* slist;
+  uint32_t* ctl;                // the two lists' counts
+  Acc<double>* partial;
+  uint32_t* part_negs;
+  pfb_mop_pulse* pulses;        // a host list's slice, its records and negatives
+  pfb_mop_record* rec;
+  uint32_t* negs;
+  size_t bytes;
+  Scratch(char* base, uint32_t maxneg) {
+    Carver c{base};
+    work = c.array<Work>(kSlice);
+    glist = c.array<uint32_t>(kSlice);
+    slist = c.array<uint32_t>(kSlice);
+    ctl = c.array<uint32_t>(2);
+    partial = c.array<Acc<double>>((size_t)kSlots * kMaxParts);
+    part_negs = c.array<uint32_t>((size_t)kSlots * kMaxParts * maxneg);
+    pulses = c.array<pfb_mop_pulse>(kSlice);
+    rec = c.array<pfb_mop_record>(kSlice);
+    negs = c.array<uint32_t>((size_t)kSlice * maxneg);
+    bytes = c.bytes();
   }
 };
 
@@ -525,20 +527,19 @@ struct Series {  // where the kernels read: the caller's device series, or a bat
 // counts; without it every tier that could have work is launched and the long pulses stay on mop_group.
 int run_slice(pfb_mop_handle* h, const Series& sx, const pfb_mop_pulse* d_pulses, uint32_t count, bool geometry,
               pfb_mop_record* d_rec, uint32_t* d_negs, bool may_wait, Names* names) {
-  const Layout lay(h->maxneg);
-  char* s = h->d_scratch;
-  uint32_t* ctl = reinterpret_cast<uint32_t*>(s + lay.ctl);
+  const Scratch scr(h->d_scratch, h->maxneg);
+  uint32_t* ctl = scr.ctl;
   PrepParams pp{};
   pp.pulses = geometry ? d_pulses : nullptr;
-  pp.work = reinterpret_cast<Work*>(s + lay.work);
+  pp.work = scr.work;
   pp.count = count;
   pp.trim = h->trim;
   pp.num_samples = sx.num_samples;
   pp.ld = sx.ld;
   pp.base = sx.base;
   pp.tiers = Tiers{h->forced, kGroupMin, may_wait ? kSplitMin : 0xffffffffu};
-  pp.glist = reinterpret_cast<uint32_t*>(s + lay.glist);
-  pp.slist = reinterpret_cast<uint32_t*>(s + lay.slist);
+  pp.glist = scr.glist;
+  pp.slist = scr.slist;
   pp.ctl = ctl;
   HIP_TRY(hipMemsetAsync(ctl, 0, 8, h->stream));
   hipLaunchKernelGGL(mop_prep, dim3((count + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, pp);
@@ -567,8 +568,8 @@ int run_slice(pfb_mop_handle* h, const Series& sx, const pfb_mop_pulse* d_pulses
   p.count = count;
   p.maxneg = h->maxneg;
   p.tiers = pp.tiers;
-  p.partial = s + lay.partial;
-  p.part_negs = reinterpret_cast<uint32_t*>(s + lay.part_negs);
+  p.partial = scr.partial;
+  p.part_negs = scr.part_negs;
   if (waves) {
     launch(h, kWave, (count + kWaves - 1) / kWaves, p);
     names->ran[0] = true;
@@ -610,12 +611,11 @@ int check_call(const pfb_mop_handle* h, const void* x, uint64_t num_samples, uin
 }
 
 // records and negatives of a slice from the scratch to the caller's host arrays
-int copy_back(pfb_mop_handle* h, const Layout& lay, uint64_t first, uint32_t count, pfb_mop_record* rec_out,
+int copy_back(pfb_mop_handle* h, const Scratch& scr, uint64_t first, uint32_t count, pfb_mop_record* rec_out,
               uint32_t* negs_out) {
-  HIP_TRY(hipMemcpyAsync(rec_out + first, h->d_scratch + lay.rec, (size_t)count * sizeof(pfb_mop_record),
-                         hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(rec_out + first, scr.rec, (size_t)count * sizeof(pfb_mop_record), hipMemcpyDeviceToHost, h->stream));
   if (negs_out && h->maxneg)
-    HIP_TRY(hipMemcpyAsync(negs_out + first * h->maxneg, h->d_scratch + lay.negs, (size_t)count * h->maxneg * 4,
+    HIP_TRY(hipMemcpyAsync(negs_out + first * h->maxneg, scr.negs, (size_t)count * h->maxneg * 4,
                            hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return PFB_OK;
@@ -624,17 +624,16 @@ int copy_back(pfb_mop_handle* h, const Layout& lay, uint64_t first, uint32_t cou
 // x on the device: slices of the list, a host list through the scratch
 int measure_device(pfb_mop_handle* h, const Series& sx, const pfb_mop_pulse* pulses, uint64_t num_pulses,
                    uint32_t pulses_mem, pfb_mop_record* rec_out, uint32_t* negs_out, bool may_wait, Names* names) {
-  const Layout lay(h->maxneg);
+  const Scratch scr(h->d_scratch, h->maxneg);
   for (uint64_t first = 0; first < num_pulses; first += kSlice) {
     const uint32_t count = (uint32_t)std::min<uint64_t>(kSlice, num_pulses - first);
     int rc;
     if (pulses_mem == PFB_MEM_HOST) {
-      pfb_mop_pulse* d_pulses = reinterpret_cast<pfb_mop_pulse*>(h->d_scratch + lay.pulses);
+      pfb_mop_pulse* d_pulses = scr.pulses;
       HIP_TRY(hipMemcpyAsync(d_pulses, pulses + first, (size_t)count * sizeof(pfb_mop_pulse), hipMemcpyHostToDevice,
                              h->stream));
-      rc = run_slice(h, sx, d_pulses, count, true, reinterpret_cast<pfb_mop_record*>(h->d_scratch + lay.rec),
-                     reinterpret_cast<uint32_t*>(h->d_scratch + lay.negs), may_wait, names);
-      if (rc == PFB_OK) rc = copy_back(h, lay, first, count, rec_out, negs_out);
+      rc = run_slice(h, sx, d_pulses, count, true, scr.rec, scr.negs, may_wait, names);
+      if (rc == PFB_OK) rc = copy_back(h, scr, first, count, rec_out, negs_out);
     } else {
       rc = run_slice(h, sx, pulses + first, count, true, rec_out + first, negs_out ? negs_out + first * h->maxneg : nullptr,
                      may_wait, names);
@@ -659,7 +658,7 @@ int ensure_stage(pfb_mop_handle* h, size_t bytes) {
 // x on the host: the windows of a batch of whole pulses, packed back to back, are all that is uploaded
 int measure_host(pfb_mop_handle* h, const char* x, const Series& sx, const pfb_mop_pulse* pulses, uint64_t num_pulses,
                  uint32_t pulses_mem, pfb_mop_record* rec_out, uint32_t* negs_out, Names* names) {
-  const Layout lay(h->maxneg);
+  const Scratch scr(h->d_scratch, h->maxneg);
   std::vector<pfb_mop_pulse> copy;
   const pfb_mop_pulse* list = pulses;  // on the host
   if (pulses_mem == PFB_MEM_DEVICE) {
@@ -698,16 +697,14 @@ int measure_host(pfb_mop_handle* h, const char* x, const Series& sx, const pfb_m
       at += (size_t)w.n * bps;
     }
     if (bytes) HIP_TRY(hipMemcpyAsync(h->d_stage, h->h_stage, bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_scratch + lay.work, work.data(), (size_t)count * sizeof(Work), hipMemcpyHostToDevice,
-                           h->stream));
+    HIP_TRY(hipMemcpyAsync(scr.work, work.data(), (size_t)count * sizeof(Work), hipMemcpyHostToDevice, h->stream));
     const Series packed{h->d_stage, bytes / bps, 1, 0};
     if (pulses_mem == PFB_MEM_HOST) {
-      pfb_mop_pulse* d_pulses = reinterpret_cast<pfb_mop_pulse*>(h->d_scratch + lay.pulses);
+      pfb_mop_pulse* d_pulses = scr.pulses;
       HIP_TRY(hipMemcpyAsync(d_pulses, list + first, (size_t)count * sizeof(pfb_mop_pulse), hipMemcpyHostToDevice,
                              h->stream));
-      rc = run_slice(h, packed, d_pulses, count, false, reinterpret_cast<pfb_mop_record*>(h->d_scratch + lay.rec),
-                     reinterpret_cast<uint32_t*>(h->d_scratch + lay.negs), true, names);
-      if (rc == PFB_OK) rc = copy_back(h, lay, first, count, rec_out, negs_out);
+      rc = run_slice(h, packed, d_pulses, count, false, scr.rec, scr.negs, true, names);
+      if (rc == PFB_OK) rc = copy_back(h, scr, first, count, rec_out, negs_out);
     } else {
       rc = run_slice(h, packed, pulses + first, count, false, rec_out + first,
                      negs_out ? negs_out + first * h->maxneg : nullptr, true, names);
@@ -727,7 +724,7 @@ extern "C" int pfb_mop_describe(const pfb_mop_config* cfg, pfb_mop_plan* plan_ou
     const int rc = mop_check(cfg);
     if (rc != PFB_OK) return rc;
     pfb_mop_plan plan{};
-    plan.scratch_bytes = Layout(cfg->max_negatives).bytes;
+    plan.scratch_bytes = Scratch(nullptr, cfg->max_negatives).bytes;
     plan.group_min = kGroupMin;
     plan.split_min = kSplitMin;
     plan.part_samples = kPart;
@@ -761,7 +758,7 @@ extern "C" int pfb_mop_create(const pfb_mop_config* cfg, pfb_mop_handle** out) {
     h->trim = cfg->trim_samples;
     h->maxneg = cfg->max_negatives;
     DeviceGuard g(dev);
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_scratch), Layout(h->maxneg).bytes);
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_scratch), Scratch(nullptr, h->maxneg).bytes);
     if (e != hipSuccess) {
       free_mop(h);
       return pfb::hip_fail(e, "hipMalloc(scratch)");

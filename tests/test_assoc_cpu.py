@@ -217,6 +217,9 @@ def test_describe():
     small, big = (am.describe_associator(num_items=n).scratch_bytes for n in (1, 1 << 20))
     assert small < 1 << 20 and 156 << 20 <= big <= 157 << 20         # 156 bytes an item
     assert am.describe_associator(num_items=1024).scratch_bytes == small
+    # the carving, to the byte: the sizes before the scratch was carved through the shared carver
+    got = tuple(am.describe_associator(num_items=n).scratch_bytes for n in (0, 1, 1024, 1025, 1 << 20))
+    assert got == (164352, 164352, 164352, 324096, 163582464), got
 
 
 def test_exports():

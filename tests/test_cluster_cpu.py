@@ -232,6 +232,12 @@ def test_describe():
     small, big = (cm.describe_clusterer(1024, 1024, num_items=n).scratch_bytes for n in (1, 1 << 20))
     assert big - small == ((1 << 20) - 1024) * (8 + 4 + 4 + 4 + 1) and 56 << 20 < small < 70 << 20   # 52 bytes a cell and the slots
     assert cm.describe_clusterer(1024, 1024, num_items=1024).scratch_bytes == small
+    # the carving, to the byte: the sizes before the scratch was carved through the shared carver
+    for (U, V), want in (((64, 1), (308992, 308992, 308992, 330496, 22307584)),
+                         ((1024, 8), (1435392, 1435392, 1435392, 1456896, 23433984)),
+                         ((1024, 1024), (60581632, 60581632, 60581632, 60603136, 82580224))):
+        got = tuple(cm.describe_clusterer(U, V, num_items=n).scratch_bytes for n in (0, 1, 1024, 1025, 1 << 20))
+        assert got == want, (U, V, got)
 
 
 def test_exports():
@@ -297,10 +303,19 @@ def test_cluster_entry_points_sit_under_the_abi_guard():
     from sdr_channelizer_amd import build
     assert "pfb_cluster.hip" in build.SOURCES
     code = re.sub(r"//.*", "", src)
-    device = code[:code.index("enum { kTierAuto")]
+    device = re.sub(r"//.*", "", src[:src.index("// host:")])
+    assert "__global__" in device and "__global__" not in re.sub(r"//.*", "", src[src.index("// host:"):])
     assert "atomicMin(" in device and "atomicAdd(" in device and "__ballot(" in device
     assert not re.search(r"\b(float|double)\b", device)                       # no float on the device
     assert "rocprim" not in code.lower() and "hipcub" not in code.lower()
+    # the same of the device part of the core it includes: the workgroup scan and the scan of the workgroups' counts
+    core = open(os.path.join(ROOT, "sdr_channelizer_amd", "csrc", "pfb_list.hpp")).read()
+    assert '#include "pfb_list.hpp"' in src
+    core_device = re.sub(r"//.*", "", core[:core.index("// host:")])
+    assert "block_scan(" in core_device and "void __launch_bounds__(kThreads) list_scan(" in core_device
+    assert "__global__" not in re.sub(r"//.*", "", core[core.index("// host:"):])
+    assert not re.search(r"\b(float|double)\b", core_device)
+    assert "rocprim" not in core.lower() and "hipcub" not in core.lower()
     # the partition ranks with ballots and LDS counts: the only atomic of its three kernels is the tile's digit count
     part = device[device.index("void __launch_bounds__(kThreads) part_scan"):device.index("template <class T>")]
     assert "atomic" not in part

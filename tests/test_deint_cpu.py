@@ -190,6 +190,11 @@ def test_describe():
     # 68 bytes a pulse, the histogram and the counts, and 20 kept jump tables of 4 bytes a pulse for the marking pass
     assert small < 1 << 20 and 148 << 20 <= big <= 150 << 20
     assert di.describe_deinterleaver(400, 8000, 4, num_pulses=1024).scratch_bytes == small
+    # the carving, to the byte: the sizes before the scratch was carved through the shared carver
+    c = DC.SMALL
+    got = tuple(di.describe_deinterleaver(c.pmin, c.pmax, c.W, num_pulses=n, **c.settings()).scratch_bytes
+                for n in (0, 1, 1024, 1025, 1 << 20))
+    assert got == (157440, 157440, 157440, 308992, 155195136), got
 
 
 def test_exports():

@@ -34,11 +34,14 @@ def test_the_boundaries_hold_one_another_and_the_source():
     assert SC.TILE * SC.SCAN_WAVE == SC.ARGMAX_STRIDE == 1 << 18
     assert SC.MAX_PULSES == di.MAX_PULSES == 1 << SC.MAX_ROUNDS == 4 * SC.ARGMAX_STRIDE
     assert SC.MAX_PULSES // SC.TILE == 4 * SC.SCAN_WAVE       # one workgroup of four waves scans every tile's count
-    src = re.sub(r"//.*", "", open(os.path.join(ROOT, "sdr_channelizer_amd", "csrc", "pfb_deint.hip")).read())
+    src, core = (re.sub(r"//.*", "", open(os.path.join(ROOT, "sdr_channelizer_amd", "csrc", name)).read())
+                 for name in ("pfb_deint.hip", "pfb_list.hpp"))
     assert "kMaxPulses = 1u << 20" in src and f"kMaxRounds = {SC.MAX_ROUNDS};" in src
-    assert f"kTile = {SC.TILE};" in src and "kThreads = 256;" in src
+    assert f"kTile = {SC.TILE};" in src and "kThreads = 256;" in core and '#include "pfb_list.hpp"' in src
     assert "deint_argmax, dim3(std::min((alive + kThreads - 1) / kThreads, 1024u)), dim3(kThreads)" in src
-    assert "const uint32_t i = threadIdx.x * 4 + k;" in src and "deint_scan, dim3(1), dim3(kThreads)" in src
+    # the scan of the tiles' counts is the list units' shared kernel, launched here
+    scan = core[core.index("void __launch_bounds__(kThreads) list_scan("):core.index("enum {")]
+    assert scan.count("const uint32_t i = threadIdx.x * 4 + k;") == 2 and "list_scan<false>, dim3(1), dim3(kThreads)" in src
     assert SC.SCAN_EDGES == (4097, 1 << 18, (1 << 18) + 1, (2 << 18) + 1, (3 << 18) + 1)
     assert [-(-n // SC.TILE) for n in SC.SCAN_EDGES] == [5, 256, 257, 513, 769]
 
@@ -47,7 +50,7 @@ def test_the_longest_list_is_accepted_and_its_scratch_reported():
     for c in (DC.SMALL, SC.FOUR, SC.FOUR_WIDE):
         plan = di.describe_deinterleaver(c.pmin, c.pmax, c.W, num_pulses=SC.MAX_PULSES, **c.settings())
         cap = SC.MAX_PULSES
-        # the carving of pfb_deint.hip's Layout: 68 bytes a pulse in 256-byte pieces, the tiles' counts, the histogram,
+        # the carving of pfb_deint.hip's scratch: 68 bytes a pulse in 256-byte pieces, the tiles' counts, the histogram,
         # the 64-byte control block; then level_bytes(): kMaxRounds jump tables of 4 bytes a pulse
         layout = sum(round_up(cap * b) for b in (8, 4, 8, 4, 4, 4, 4, 16, 16)) + round_up(cap // SC.TILE * 4) \
             + round_up(c.NB * 4) + round_up(64)

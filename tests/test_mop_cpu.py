@@ -188,6 +188,7 @@ def test_describe():
     # the work of a slice, the partial slots, and a host list's slice with its records; the lists scale with max_negatives
     small, big = pm.describe_modulation(max_negatives=0).scratch_bytes, pm.describe_modulation(max_negatives=128).scratch_bytes
     assert 9 << 20 <= small <= 11 << 20 and big - small == ((1 << 16) + 256 * 64) * 128 * 4
+    assert (small, big) == (10223872, 52166912)     # to the byte: the sizes before the scratch was carved through the shared carver
 
 
 def test_exports():
